@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- snapshot-sweep throughput of the HIP hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: rom_solve_batch of the workload's parameter sweep with the
 parameters already resident in HBM and the (M, dim) fp64 snapshot block left in HBM.  Workloads:
@@ -23,8 +23,17 @@ with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set; the parent never touches the
 way rank 0 prints ONE JSON line.
 
 The timed region (exactly K steps) is bracketed by a barrier + stream synchronisation on both sides (RCCL
-all-reduce for N > 1) and the reported time is the max over ranks.  It is repeated `--repeats` times (default 5):
-`value` / `ms_per_step` are those of the MEDIAN region, `repeats` lists all of them.
+all-reduce for N > 1) and the reported time is the max over ranks.  It is run `--repeats` times (default 1; 5 with
+--full): `value` / `ms_per_step` are those of the MEDIAN region, `repeats` lists all of them.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed region, the output dump (--dump-outputs) and
+the JSON line.  --full adds everything else, as one line: the CPU baselines, the per-kernel HIP-event pass with the
+roofline of the dominant kernel, the API / POD / greedy legs and, for c2 on one GPU, the compact C4 / C5 legs
+(--no-cpu-baseline, --no-extras, --no-pod-c3 and --no-other-configs trim a --full run).
+
+--dump-outputs DIR writes what the last timed step computed: `snapshots.npy`, a fixed sample of rows of the (M, dim) fp64
+snapshot block (at most 64 rows and 60 MB; the same rows for the same arguments), and `snapshot_rows.npy`, their row
+indices in the block (as float64).  The inputs are seeded, so two builds can be compared output for output.
 
 Host side is plain Python + ctypes (no torch): the rendezvous for the RCCL unique id goes through a launch-scoped
 file (romhighcontrast_amd/sweep.py).
@@ -256,12 +265,40 @@ def pod_accounting(M, dim, r):
     return float(M) * (M + 1) * dim + 2.0 * r * M * dim
 
 
+DUMP_MAX_ROWS = 64
+DUMP_MAX_BYTES = 60e6
+
+
+def dump_rows(M: int, dim: int) -> np.ndarray:
+    """The rows of the (M, dim) snapshot block that --dump-outputs writes: a seeded sample, the same for the same (M, dim)."""
+    k = int(max(1, min(M, DUMP_MAX_ROWS, DUMP_MAX_BYTES // (8 * dim))))
+    return np.sort(np.random.default_rng(SEED).choice(M, size=k, replace=False))
+
+
+def dump_outputs(out_dir: str, U, M: int, dim: int) -> None:
+    """DIR/snapshots.npy (the sampled rows of the block the last timed step left in HBM, fp64) and DIR/snapshot_rows.npy
+    (their indices, as float64)."""
+    rows = dump_rows(M, dim)
+    X = np.empty((len(rows), dim), dtype=np.float64)
+    for j, i in enumerate(rows):
+        X[j] = U.download(dim, offset=int(i) * dim)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "snapshots.npy"), X)
+    np.save(os.path.join(out_dir, "snapshot_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the K-step timed region is run (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the K-step timed region is run (median reported); default 1, 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the per-kernel pass and roofline, the API / POD / greedy legs and (c2) the "
+                         "C4 / C5 legs; a plain run times the sweep only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the snapshot rows of the last timed step to DIR/*.npy")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--M", type=int, default=None, help="parameters per GPU per step (default: the config's)")
     ap.add_argument("--N", type=int, default=None, help="cells per block per dimension (default: the config's)")
@@ -284,6 +321,10 @@ def main():
                     help="N>1: also expand the gathered factored block into snapshot rows on every rank (the literal "
                          "(M/G, dim) row block of SURVEY 8e, replicated)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:  # a plain run: the sweep line only
+        args.no_cpu_baseline = args.no_extras = True
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher.  Nothing below this line has run: no GPU call yet.
@@ -446,22 +487,25 @@ def main():
     order = np.argsort(walls)
     med = int(order[len(order) // 2])
     wall, ev_ms = walls[med], evs[med]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, U_loc, M, dim)
 
-    # one more pass of the same K steps with every kernel launch bracketed by a HIP-event pair on its
-    # launch stream (the per-kernel durations behind `roofline` / `kernels`).  Kept out of the timed
-    # regions above: ~70 event records per step cost ~8 % at 3 ms per step.
-    ctx.profile_reset()
-    ctx.profile(True)
-    tp = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    drain()
-    ctx.synchronize()
-    wall_prof = time.perf_counter() - tp
-    ctx.profile(False)
-    barrier()
+    if args.full:
+        # one more pass of the same K steps with every kernel launch bracketed by a HIP-event pair on its
+        # launch stream (the per-kernel durations behind `roofline` / `kernels`).  Kept out of the timed
+        # regions above: ~70 event records per step cost ~8 % at 3 ms per step.
+        ctx.profile_reset()
+        ctx.profile(True)
+        tp = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        drain()
+        ctx.synchronize()
+        wall_prof = time.perf_counter() - tp
+        ctx.profile(False)
+        barrier()
 
-    if comm:  # the gathered factored block must reproduce a plain local sweep bit for bit, on every rank
+    if comm and args.full:  # the gathered factored block must reproduce a plain local sweep bit for bit, on every rank
         ref = ctx.alloc(M * dim)
         fem.solve_batch(a_dev, M, ref)
         probe = [0, (M // 2) * dim + 17, M * dim - 1]
@@ -478,64 +522,11 @@ def main():
             ctx.comm_destroy()
         return
 
-    prof = ctx.profile_report()
     work = fem.solve_work()
     solves = world * M * args.steps
     value = solves / wall
-    kernels = {}
-    for name, v in prof.items():
-        if v["launches"] == 0:
-            continue
-        avg_ms = v["total_ms"] / v["launches"]
-        kernels[name] = {"launches_per_step": v["launches"] / args.steps, "avg_ms": round(avg_ms, 5),
-                         "ms_per_step": round(v["total_ms"] / args.steps, 4),
-                         "tflops": round(v["flops"] / v["total_ms"] * 1e-9, 3) if v["total_ms"] > 0 else 0.0,
-                         "gbs": round(v["bytes"] / v["total_ms"] * 1e-6, 1) if v["total_ms"] > 0 else 0.0}
-    dom = max((k for k in prof if k != "rccl_allgather"), key=lambda k: prof[k]["total_ms"])
-    d = prof[dom]
-    achieved = d["flops"] / d["total_ms"] * 1e-9  # algorithmic flops of the launches / their event time
-    nblk = blocks[0] * blocks[1]
-    roofline = {"kernel": dom, "bound": "mfma", "achieved": round(achieved, 3), "peak": FP64_MATRIX_PEAK_TFLOPS,
-                "unit": "TFLOP/s", "frac": round(achieved / FP64_MATRIX_PEAK_TFLOPS, 4), "traffic": None,
-                "avg_launch_ms": round(d["total_ms"] / d["launches"], 5),
-                "flops_per_launch": d["flops"] / d["launches"],
-                "store_bytes_per_launch": 8.0 * M * nblk * (N - 1) ** 2 if dom.startswith("extend") else None,
-                "sustained_mfma_tflops": 72.0,
-                "frac_of_sustained": round(achieved / 72.0, 4),
-                "store_floor_ms": round(8.0 * M * nblk * (N - 1) ** 2 / 6.0e9, 4) if dom.startswith("extend") else None,
-                "note": "ALGORITHMIC flops (no padding of K or of the tiles) of the fp64 MFMA kernel (v_mfma_f64_16x16x4_f64) "
-                        "against the spec fp64 matrix rate (64 cycles per instruction).  A register-only loop of that "
-                        "instruction (16 accumulators per wave) sustains 71-73 TFLOP/s on this part, 60-65 with a 6 TB/s store "
-                        "stream interleaved (profiles/r02_mfma_store_overlap_microbench.txt; round 1's 49 TFLOP/s came from a "
-                        "probe whose loop the compiler had filled with accumulator moves): sustained_mfma_tflops / "
-                        "frac_of_sustained.  The same launch writes the snapshot rows (store_bytes_per_launch; store_floor_ms = "
-                        "that at the 6 TB/s a store-only kernel reaches); DESIGN.md section 5"}
-    # PMC-measured memory-side traffic of the dominant kernel, if a summary of separate
-    # `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of this same command is committed
-    cfg_sizes = {"c2": ((2, 2), 128, 1024), "c4": ((3, 3), 171, 1024), "c5": ((4, 4), 256, 4096)}
-    pmc_files = {"c2": ("r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"),
-                 "c4": ("r05_pmc_traffic_c4.json", "r04_pmc_traffic_c4.json", "r03_pmc_traffic_c4.json", "r02_pmc_traffic_c4.json"),
-                 "c5": ("r05_pmc_traffic_c5.json", "r04_pmc_traffic_c5.json", "r03_pmc_traffic_c5.json", "r02_pmc_traffic_c5.json")}
-    for pmc_name in pmc_files.get(args.config, ()):
-        pmc_path = os.path.join(ROOT, "profiles", pmc_name)
-        if os.path.exists(pmc_path) and (blocks, N, M) == cfg_sizes[args.config]:
-            allk = json.load(open(pmc_path))["kernels"]
-            pmc = next((v for k, v in allk.items() if dom.startswith("extend") and k.startswith("k_extend")), None) \
-                if dom.startswith("extend") else allk.get("k_" + dom)
-            if pmc:
-                # a number from a COMMITTED profile, not from this run: say which build it was taken on (hash of the kernel
-                # sources, tools/pmc_summary.py) and withhold it when that is not the build running now
-                taken_on, now = json.load(open(pmc_path)).get("csrc_sha16"), csrc_sha16()
-                roofline["traffic_source"] = {"file": f"profiles/{pmc_name}", "csrc_sha16_of_profile": taken_on, "csrc_sha16_of_this_build": now,
-                                              "same_build": taken_on == now}
-                if taken_on == now:
-                    roofline["traffic"] = pmc["traffic_bytes_per_launch"]
-                else:
-                    roofline["traffic_of_other_build"] = pmc["traffic_bytes_per_launch"]
-                roofline["traffic_note"] = (f"bytes per launch from profiles/{pmc_name}: rocprofv3 --pmc FETCH_SIZE (x2, "
-                                            "gfx950) + WRITE_SIZE, separate passes of this same command; includes Infinity-Cache "
-                                            "hits; `traffic` is null when the profile was taken on other kernel sources")
-                break
+    if args.full:
+        kernels, roofline = kernel_records(ctx.profile_report(), args.config, args.steps, blocks, N, M)
     ms_all = [w / args.steps * 1e3 for w in walls]
     out = {
         "metric": "snapshot_solves_per_sec", "value": round(value, 1), "unit": "solves/s", "n_gpus": world,
@@ -558,14 +549,15 @@ def main():
         "preroll": {"seconds": args.preroll, "steps": preroll_steps,
                     "note": "untimed steps in front of the first region, on top of `warmup` (clocks settle after ~0.2 s of work)"},
         "event_ms_per_step": round(ev_ms / args.steps, 4),
-        "profiled_pass_ms_per_step": round(wall_prof / args.steps * 1e3, 4),
+        **({"profiled_pass_ms_per_step": round(wall_prof / args.steps * 1e3, 4)} if args.full else {}),
         "rccl_ranks": rccl_ranks if comm else 0,
         "exchange": ({"what": "compact interface vectors (factored snapshot block; the nodal part is recomputed by the expansion)",
                       "doubles_per_system": stride, "full_interface_vector_doubles": fem.reduced_stride, "steps_per_collective": every,
                       "sent_bytes_per_rank_per_step": M * stride * 8, "received_bytes_per_rank_per_step": world * M * stride * 8,
                       "row_block_bytes_per_rank": M * dim * 8, "replicated_rows": bool(args.replicate),
                       "preflight": exchange_note or "a peer's rows expanded from the gathered vectors equal a local sweep bit for bit "
-                                                    "(checked after the warm-up, whose last group is partial when warmup % every != 0, and again after the run)"} if comm else None),
+                                                    "(checked after the warm-up, whose last group is partial when warmup % every != 0"
+                                                    + (", and again after the run)" if args.full else ")")} if comm else None),
         "setup": {"setup_s": round(setup_s, 4),
                   "solves_per_sec_incl_setup_one_sweep": round(M / (setup_s + wall / args.steps), 1),
                   "note": "setup_s = SolutionsManagerFEM(...) = rom_fem_create (parameter-independent tables, once per FE "
@@ -575,10 +567,11 @@ def main():
                       "canonical_banded_flops_per_solve": work["flops_banded"],
                       "canonical_banded_bytes_per_solve": work["bytes_banded"],
                       "canonical_banded_equiv_gbs": round(value * work["bytes_banded"] * 1e-9, 1)},
-        "roofline": roofline, "kernels": kernels,
-        "kernels_note": "per-kernel HIP-event times of one extra pass of the same K steps with the sweep on ONE stream "
-                        "(rom_profile_enable): the stream the timed regions behind `value` use as well since round 5 (ROMHC_STREAMS=2..4 "
-                        "splits a sweep into concurrent sub-batches; no longer the default)",
+        **({"roofline": roofline, "kernels": kernels,
+            "kernels_note": "per-kernel HIP-event times of one extra pass of the same K steps with the sweep on ONE stream "
+                            "(rom_profile_enable): the stream the timed regions behind `value` use as well since round 5 (ROMHC_STREAMS=2..4 "
+                            "splits a sweep into concurrent sub-batches; no longer the default)"} if args.full else {}),
+        "full": bool(args.full),
     }
 
     if world == 1 and not args.no_extras:
@@ -629,7 +622,7 @@ def main():
                                        "sample": f"numpy.linalg.svd of the centred first {Ms} snapshots (the SVD inside "
                                                  f"sklearn PCA, src/lib/ReducedBasis.py:196), all LAPACK threads of the host"}
     if world == 1 and not args.no_extras and args.config == "c2" and not custom and not args.no_other_configs:
-        # the two other single-GPU workloads of SURVEY 8d, compact, in the SAME line (the driver runs `python bench.py`)
+        # the two other single-GPU workloads of SURVEY 8d, compact, in the SAME line (`python bench.py --full`)
         U_loc.free()
         a_dev.free()
         for other in ("c4", "c5"):
@@ -656,6 +649,66 @@ def csrc_sha16():
         h.update(name.encode())
         h.update(open(os.path.join(csrc, name), "rb").read())
     return h.hexdigest()[:16]
+
+
+def kernel_records(prof, config, steps, blocks, N, M):
+    """--full: per-kernel records of the profiled pass (HIP events of every launch) and the dominant kernel against its
+    roofline, with its memory-side traffic when a PMC summary of this same build is committed under profiles/."""
+    kernels = {}
+    for name, v in prof.items():
+        if v["launches"] == 0:
+            continue
+        avg_ms = v["total_ms"] / v["launches"]
+        kernels[name] = {"launches_per_step": v["launches"] / steps, "avg_ms": round(avg_ms, 5),
+                         "ms_per_step": round(v["total_ms"] / steps, 4),
+                         "tflops": round(v["flops"] / v["total_ms"] * 1e-9, 3) if v["total_ms"] > 0 else 0.0,
+                         "gbs": round(v["bytes"] / v["total_ms"] * 1e-6, 1) if v["total_ms"] > 0 else 0.0}
+    dom = max((k for k in prof if k != "rccl_allgather"), key=lambda k: prof[k]["total_ms"])
+    d = prof[dom]
+    achieved = d["flops"] / d["total_ms"] * 1e-9  # algorithmic flops of the launches / their event time
+    nblk = blocks[0] * blocks[1]
+    roofline = {"kernel": dom, "bound": "mfma", "achieved": round(achieved, 3), "peak": FP64_MATRIX_PEAK_TFLOPS,
+                "unit": "TFLOP/s", "frac": round(achieved / FP64_MATRIX_PEAK_TFLOPS, 4), "traffic": None,
+                "avg_launch_ms": round(d["total_ms"] / d["launches"], 5),
+                "flops_per_launch": d["flops"] / d["launches"],
+                "store_bytes_per_launch": 8.0 * M * nblk * (N - 1) ** 2 if dom.startswith("extend") else None,
+                "sustained_mfma_tflops": 72.0,
+                "frac_of_sustained": round(achieved / 72.0, 4),
+                "store_floor_ms": round(8.0 * M * nblk * (N - 1) ** 2 / 6.0e9, 4) if dom.startswith("extend") else None,
+                "note": "ALGORITHMIC flops (no padding of K or of the tiles) of the fp64 MFMA kernel (v_mfma_f64_16x16x4_f64) "
+                        "against the spec fp64 matrix rate (64 cycles per instruction).  A register-only loop of that "
+                        "instruction (16 accumulators per wave) sustains 71-73 TFLOP/s on this part, 60-65 with a 6 TB/s store "
+                        "stream interleaved (profiles/r02_mfma_store_overlap_microbench.txt; round 1's 49 TFLOP/s came from a "
+                        "probe whose loop the compiler had filled with accumulator moves): sustained_mfma_tflops / "
+                        "frac_of_sustained.  The same launch writes the snapshot rows (store_bytes_per_launch; store_floor_ms = "
+                        "that at the 6 TB/s a store-only kernel reaches); DESIGN.md section 5"}
+    # PMC-measured memory-side traffic of the dominant kernel, if a summary of separate
+    # `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of this same command is committed
+    cfg_sizes = {"c2": ((2, 2), 128, 1024), "c4": ((3, 3), 171, 1024), "c5": ((4, 4), 256, 4096)}
+    pmc_files = {"c2": ("r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"),
+                 "c4": ("r05_pmc_traffic_c4.json", "r04_pmc_traffic_c4.json", "r03_pmc_traffic_c4.json", "r02_pmc_traffic_c4.json"),
+                 "c5": ("r05_pmc_traffic_c5.json", "r04_pmc_traffic_c5.json", "r03_pmc_traffic_c5.json", "r02_pmc_traffic_c5.json")}
+    for pmc_name in pmc_files.get(config, ()):
+        pmc_path = os.path.join(ROOT, "profiles", pmc_name)
+        if os.path.exists(pmc_path) and (blocks, N, M) == cfg_sizes[config]:
+            allk = json.load(open(pmc_path))["kernels"]
+            pmc = next((v for k, v in allk.items() if dom.startswith("extend") and k.startswith("k_extend")), None) \
+                if dom.startswith("extend") else allk.get("k_" + dom)
+            if pmc:
+                # a number from a COMMITTED profile, not from this run: say which build it was taken on (hash of the kernel
+                # sources, tools/pmc_summary.py) and withhold it when that is not the build running now
+                taken_on, now = json.load(open(pmc_path)).get("csrc_sha16"), csrc_sha16()
+                roofline["traffic_source"] = {"file": f"profiles/{pmc_name}", "csrc_sha16_of_profile": taken_on, "csrc_sha16_of_this_build": now,
+                                              "same_build": taken_on == now}
+                if taken_on == now:
+                    roofline["traffic"] = pmc["traffic_bytes_per_launch"]
+                else:
+                    roofline["traffic_of_other_build"] = pmc["traffic_bytes_per_launch"]
+                roofline["traffic_note"] = (f"bytes per launch from profiles/{pmc_name}: rocprofv3 --pmc FETCH_SIZE (x2, "
+                                            "gfx950) + WRITE_SIZE, separate passes of this same command; includes Infinity-Cache "
+                                            "hits; `traffic` is null when the profile was taken on other kernel sources")
+                break
+    return kernels, roofline
 
 
 def _timed(ctx, f, reps=2):
@@ -838,10 +891,10 @@ def extras_greedy_c4(out, ctx, sm, fem, a_loc, a_dev, U_loc, M, dim, factored_to
 
 
 def other_config_leg(ctx, dev, config):
-    """Compact run of another single-GPU workload (C4 / C5) for the default line: sweep rate (median of 3 regions behind a
+    """Compact run of another single-GPU workload (C4 / C5) for the --full c2 line: sweep rate (median of 3 regions behind a
     pre-roll), per-kernel HIP events of one pass, dominant kernel against its roofline, and the workload's basis stage
     (C4: greedy n = 50 in both modes on rows, on the factored block and through the plain build() call on a block fresh from
-    the sweep; C5: 50-mode POD of the rows and of the interface vectors).  `python bench.py --config c4|c5` adds the CPU
+    the sweep; C5: 50-mode POD of the rows and of the interface vectors).  `python bench.py --full --config c4|c5` adds the CPU
     baselines and API rates."""
     from romhighcontrast_amd.lib.SolutionsManagers import SolutionsManagerFEM
     cfg = CONFIGS[config]
@@ -892,7 +945,7 @@ def other_config_leg(ctx, dev, config):
            "roofline": {"kernel": dom, "bound": "mfma", "achieved": round(ach, 3), "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
                         "frac": round(ach / FP64_MATRIX_PEAK_TFLOPS, 4), "avg_launch_ms": round(d["total_ms"] / d["launches"], 5)},
            "kernels": kernels,
-           "note": "compact leg of the default run: the timed regions run the sweep as the library does by default (one stream), "
+           "note": "compact leg of the --full c2 run: the timed regions run the sweep as the library does by default (one stream), "
                    "`kernels` is one extra pass with every launch bracketed by HIP events"}
     sub = {}
     if config == "c4":

@@ -1821,3 +1821,32 @@ def test_plain_c_caller_end_to_end(tmp_path):
     out = r.stdout.decode()
     assert r.returncode == 0 and out.rstrip().endswith("OK"), out
 
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (a plain run, in a fresh process): one JSON line of the sweep alone
+    over exactly K timed steps, and the dumped rows are the snapshots of the seeded parameters at their indices."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    blocks, N, M = (2, 2), 16, 100
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--blocks", "2", "2", "--N", str(N), "--M", str(M), "--dump-outputs", str(out_dir)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-4000:]
+    line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert line["metric"] == "snapshot_solves_per_sec" and line["unit"] == "solves/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["steps"] == 3 and line["repeats"]["regions"] == 1 and line["full"] is False
+    # value = solves per second of the timed steps; ms_per_step is printed to 4 decimals
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - M) <= M * (1e-3 + 6e-5 / line["ms_per_step"])
+    assert "kernels" not in line and "cpu_baseline" not in line
+    X = np.load(out_dir / "snapshots.npy")
+    rows = np.load(out_dir / "snapshot_rows.npy")
+    assert X.dtype == np.float64 and np.array_equal(rows, bench.dump_rows(M, X.shape[1]).astype(np.float64))
+    a = bench.workload_parameters("c2", blocks, M)[rows.astype(int)]
+    g = ro.Geometry(blocks, N)
+    observed("plain bench.py --dump-outputs: dumped rows vs oracle (rel H10)", relh10(g, X, ro.generate_solutions(g, a, "lsqsparse")),
+             SNAP_TOL)

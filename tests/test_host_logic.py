@@ -497,6 +497,33 @@ def test_bench_workloads_follow_survey_8d():
     assert c5.shape == (4096, 4, 4) and c5.max() <= 1000
 
 
+def test_bench_dump_is_a_fixed_bounded_sample(tmp_path):
+    """bench.py --dump-outputs: the same rows for the same (M, dim), at most 64 of them and 64 MB at the C2 / C4 / C5 sizes,
+    written as float64 .npy files with the rows' contents at their indices."""
+    import bench
+    for M, dim in ((1024, 65025), (1024, 262144), (4096, 1046529), (5, 10)):
+        rows = bench.dump_rows(M, dim)
+        assert np.array_equal(rows, bench.dump_rows(M, dim))
+        assert 1 <= len(rows) <= min(M, 64) and len(np.unique(rows)) == len(rows)
+        assert rows.min() >= 0 and rows.max() < M and len(rows) * dim * 8 <= 64e6
+
+    class HostBuffer:  # the download() of a device buffer, over a host array
+        def __init__(self, x):
+            self.x = x.ravel()
+
+        def download(self, n, offset=0):
+            assert 0 <= offset and offset + n <= self.x.size
+            return self.x[offset:offset + n].copy()
+
+    M, dim = 300, 7
+    U = np.random.default_rng(1).standard_normal((M, dim))
+    bench.dump_outputs(str(tmp_path / "out"), HostBuffer(U), M, dim)
+    X = np.load(tmp_path / "out" / "snapshots.npy")
+    idx = np.load(tmp_path / "out" / "snapshot_rows.npy")
+    assert X.dtype == np.float64 and idx.dtype == np.float64 and len(idx) == 64
+    assert np.array_equal(X, U[idx.astype(int)])
+
+
 def test_environment_switches_are_documented():
     """Every ROMHC_* variable the library reads (getenv in csrc/, os.environ in the Python layer) has a row in
     INTEGRATION.md, and the table names no variable that nothing reads."""

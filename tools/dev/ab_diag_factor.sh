@@ -16,9 +16,9 @@ d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=d.get('kernel
 print(sys.argv[1].split('/')[-1], d['value'], d['ms_per_step'], {n:v for n,v in k.items() if 'diag' in n} if isinstance(k,dict) else '')" $1; }
 for rep in 1 2; do
   for c in c4 c5; do
-    timeout -k 10 200 python3 bench.py --config $c --steps 20 --no-extras --no-cpu-baseline > $O/${c}_new_$rep.json 2> $O/err.txt
+    timeout -k 10 200 python3 bench.py --full --config $c --steps 20 --no-extras --no-cpu-baseline > $O/${c}_new_$rep.json 2> $O/err.txt
     line $O/${c}_new_$rep.json
-    timeout -k 10 200 python3 tools/dev/with_lib.py $L/libromhc_prev.so bench.py --config $c --steps 20 --no-extras --no-cpu-baseline > $O/${c}_prev_$rep.json 2> $O/err.txt
+    timeout -k 10 200 python3 tools/dev/with_lib.py $L/libromhc_prev.so bench.py --full --config $c --steps 20 --no-extras --no-cpu-baseline > $O/${c}_prev_$rep.json 2> $O/err.txt
     line $O/${c}_prev_$rep.json
   done
 done

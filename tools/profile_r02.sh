@@ -6,13 +6,13 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02prof
 rm -rf $O; mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+timeout -k 10 400 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --no-extras > $O/bench_c2_under_rocprof.json 2> $O/stats.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $O/bench_c2_under_rocprof.json 2> $O/stats.err
 find $O/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_c2_kernel_stats.csv
 rm -rf $O/stats
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/pmc_$c.err
+  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/pmc_$c.err
   find $O/pmc_$c -name "*counter_collection.csv" | head -1 | xargs -I{} cp {} $O/bench_c2_$c.csv
   rm -rf $O/pmc_$c
 done
@@ -35,7 +35,7 @@ done
 export ROMHC_STREAMS=1
 for cfg in c4 c5; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pc_$c -- python3 $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/pc_${cfg}_$c.err
+    timeout -k 10 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pc_$c -- python3 $R/bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/pc_${cfg}_$c.err
     find $O/pc_$c -name "*counter_collection.csv" | head -1 | xargs -I{} cp {} $O/bench_${cfg}_$c.csv
     rm -rf $O/pc_$c
   done
@@ -45,7 +45,7 @@ unset ROMHC_STREAMS
 # rocprofv3 per-kernel statistics of the C4 / C5 sweeps as they run by default (two concurrent sub-batches: a launch
 # covers half the systems, and kernels of the two halves overlap)
 for cfg in c4 c5; do
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$cfg -- python3 $R/bench.py --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_${cfg}_under_rocprof.json 2> $O/st_$cfg.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/st_$cfg -- python3 $R/bench.py --full --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_${cfg}_under_rocprof.json 2> $O/st_$cfg.err
   find $O/st_$cfg -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_${cfg}_kernel_stats.csv
   rm -rf $O/st_$cfg
 done

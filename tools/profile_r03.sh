@@ -8,15 +8,15 @@ O=$R/gpurun_out/r03prof
 if [ "$1" = "c45only" ]; then mkdir -p $O; set -- c45; else
 rm -rf $O; mkdir -p $O
 cd $R
-timeout -k 10 500 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err
-timeout -k 10 400 python bench.py --config c4 > $O/bench_c4.json 2> $O/bench_c4.err
-timeout -k 10 500 python bench.py --config c5 > $O/bench_c5.json 2> $O/bench_c5.err
+timeout -k 10 500 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
+timeout -k 10 400 python bench.py --full --config c4 > $O/bench_c4.json 2> $O/bench_c4.err
+timeout -k 10 500 python bench.py --full --config c5 > $O/bench_c5.json 2> $O/bench_c5.err
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --no-extras > $O/bench_c2_under_rocprof.json 2> $O/stats.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $O/bench_c2_under_rocprof.json 2> $O/stats.err
 find $O/stats -name "*kernel_stats.csv" | tail -1 | xargs -I{} cp {} $O/bench_c2_kernel_stats.csv
 rm -rf $O/stats
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/pmc_$c.err
+  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/pmc_$c.err
   find $O/pmc_$c -name "*counter_collection.csv" | tail -1 | xargs -I{} cp {} $O/bench_c2_$c.csv
   rm -rf $O/pmc_$c
 done
@@ -40,7 +40,7 @@ if [ "$1" = "c45" ] || [ "$1" = "all" ]; then
 cd /tmp
 for cfg in c4 c5; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    ROMHC_STREAMS=1 timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/p45_$c -- python3 $R/bench.py --config $cfg --steps 1 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/p45.err
+    ROMHC_STREAMS=1 timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/p45_$c -- python3 $R/bench.py --full --config $cfg --steps 1 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> $O/p45.err
     find $O/p45_$c -name "*counter_collection.csv" | tail -1 | xargs -I{} cp {} $O/p45_$c.csv
     rm -rf $O/p45_$c
   done

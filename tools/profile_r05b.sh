@@ -6,11 +6,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05prof
 rm -rf $O; mkdir -p $O
 cd $R
-timeout -k 10 600 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err
-timeout -k 10 400 python bench.py --config c4 --no-other-configs > $O/bench_c4.json 2> $O/bench_c4.err
-timeout -k 10 500 python bench.py --config c5 --no-other-configs > $O/bench_c5.json 2> $O/bench_c5.err
+timeout -k 10 600 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
+timeout -k 10 400 python bench.py --full --config c4 --no-other-configs > $O/bench_c4.json 2> $O/bench_c4.err
+timeout -k 10 500 python bench.py --full --config c5 --no-other-configs > $O/bench_c5.json 2> $O/bench_c5.err
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --no-extras --no-other-configs > $O/bench_c2_under_rocprof.json 2> $O/stats.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-extras --no-other-configs > $O/bench_c2_under_rocprof.json 2> $O/stats.err
 find $O/stats -name "*kernel_stats.csv" | tail -1 | xargs -I{} cp {} $O/bench_c2_kernel_stats.csv
 rm -rf $O/stats
 cd $R
