@@ -3,6 +3,7 @@
 #include "romhc_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -41,6 +42,7 @@ extern "C" int rom_init(int device, rom_ctx** out) {
   c->device = device;
   c->n_cu = prop.multiProcessorCount;
   ROM_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  c->home_stream = c->stream;
   for (int i = 0; i < 3; ++i) {
     ROM_HIP(hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));
     ROM_HIP(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
@@ -103,6 +105,9 @@ extern "C" int rom_device_name(rom_ctx* c, char* out, size_t cap) {
 }
 
 int rom_ctx_scratch(rom_ctx* c, size_t n, double** out) {
+  // (on a borrowed stream the area may still be in use by the home stream's kernels, and a reallocation below would
+  // synchronise the wrong stream before freeing it)
+  ROM_CHECK(c->stream == c->home_stream, "rom_ctx_scratch: scratch requested on a borrowed stream");
   if (c->scratch_doubles < n) {
     ROM_HIP(hipStreamSynchronize(c->stream));
     if (c->d_scratch) ROM_HIP(hipFree(c->d_scratch));
@@ -409,7 +414,7 @@ extern "C" int rom_buf_fill(rom_buf* b, size_t off, size_t n, double value) {
   ROM_CHECK(b, "bad arguments");
   ROM_CHECK(off + n <= b->n, "rom_buf_fill: range exceeds buffer");
   if (n == 0) return ROM_OK;
-  if (value == 0.0) {
+  if (value == 0.0 && !std::signbit(value)) {  // (+0.0 only: -0.0 == 0.0, but its bits are not all zero)
     ROM_HIP(hipMemsetAsync(b->p + off, 0, n * sizeof(double), b->ctx->stream));
     return ROM_OK;
   }

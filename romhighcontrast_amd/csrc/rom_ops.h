@@ -9,9 +9,11 @@ struct StencilGeom {
 };
 StencilGeom rom_make_geom(int nrb, int ncb, int N);
 
-// C[m,n] = alpha * A[m,k] B[k,n] + beta C
+// C[m,n] = alpha * A[m,k] B[k,n] + beta C.  A split-K product keeps its partials in the context's scratch, or in
+// `part_ws` (rom_gemm_nn_partial_doubles(m, n, k, lda, ldb) doubles) when one is given
 int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
-                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
+                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* part_ws = nullptr);
+size_t rom_gemm_nn_partial_doubles(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb);
 // C[m,m] = A A^T (lower tiles on MFMA + mirror)
 int rom_launch_gram(rom_ctx* ctx, int64_t m, int64_t k, const double* A, int64_t lda, double* C, int64_t ldc);
 // Y[k,:] = A(coef) X[k,:]; d_coef: kblk block coefficients ON THE DEVICE, or null for the unit operator A_1

@@ -841,12 +841,36 @@ __global__ __launch_bounds__(256) void k_gemm_nn(long long m, long long n, long 
     }
 }
 
+// the route of rom_launch_gemm_nn: the thin / lift kernel, else the general one with `splits` K slices of `kper`
+static bool gemm_nn_thin(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb) {
+  return (m <= 64 ? k >= 128 : (k >= 16 && k <= 256)) && n >= 1024 && size_t(lda) * 8 * 64 < (size_t(1) << 32) &&
+         size_t(ldb) * 8 * 16 + 1024 < (size_t(1) << 32) && (m + 63) / 64 <= 65535 && !no_thin_gemm();
+}
+static long long gemm_nn_splits(int64_t m, int64_t n, int64_t k, long long* kper_out) {
+  // a handful of output tiles under a long K (the sketches of a FACTORED block: 24 x 272 x 1024): split-K, 64 rows of B each
+  const long long tiles = ((n + 63) / 64) * ((m + 63) / 64);
+  long long splits = 1, kper = k;
+  if (tiles <= 32 && k >= 256) {
+    splits = std::min<long long>((256 + tiles - 1) / tiles, k / 64);
+    kper = ((k + splits - 1) / splits + BK - 1) / BK * BK;
+    splits = (k + kper - 1) / kper;
+  }
+  *kper_out = kper;
+  return splits;
+}
+
+size_t rom_gemm_nn_partial_doubles(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb) {
+  if (m <= 0 || n <= 0 || gemm_nn_thin(m, n, k, lda, ldb)) return 0;
+  long long kper = 0;
+  const long long splits = gemm_nn_splits(m, n, k, &kper);
+  return splits > 1 ? size_t(splits) * m * n : 0;
+}
+
 int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
-                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc) {
+                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* part_ws) {
   if (m <= 0 || n <= 0) return ROM_OK;
   static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;  // per-shape names in the profile records
-  if ((m <= 64 ? k >= 128 : (k >= 16 && k <= 256)) && n >= 1024 && size_t(lda) * 8 * 64 < (size_t(1) << 32) &&
-      size_t(ldb) * 8 * 16 + 1024 < (size_t(1) << 32) && (m + 63) / 64 <= 65535 && !no_thin_gemm()) {
+  if (gemm_nn_thin(m, n, k, lda, ldb)) {
     // thin A against the rows of a snapshot-wide B; or a tall A with a short K (the lift: output bound), in row tiles of 64
     char nm[64];
     detail ? snprintf(nm, sizeof nm, "gemm_nn_thin_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k) : snprintf(nm, sizeof nm, "gemm_nn");
@@ -862,17 +886,12 @@ int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alp
     return ROM_OK;
   }
   dim3 grid(unsigned((n + 63) / 64), unsigned((m + 63) / 64));
-  // a handful of output tiles under a long K (the sketches of a FACTORED block: 24 x 272 x 1024): split-K, 64 rows of B each
-  const long long tiles = (long long)grid.x * grid.y;
-  long long splits = 1, kper = k;
-  if (tiles <= 32 && k >= 256) {
-    splits = std::min<long long>((256 + tiles - 1) / tiles, k / 64);
-    kper = ((k + splits - 1) / splits + BK - 1) / BK * BK;
-    splits = (k + kper - 1) / kper;
-  }
+  long long kper = k;
+  const long long splits = gemm_nn_splits(m, n, k, &kper);
   double* part = nullptr;
   if (splits > 1) {
-    ROM_TRY(rom_ctx_scratch(ctx, size_t(splits) * m * n, &part));
+    if (part_ws) part = part_ws;  // (the caller's own partial buffer: a product enqueued on a borrowed stream)
+    else ROM_TRY(rom_ctx_scratch(ctx, size_t(splits) * m * n, &part));
     grid.z = unsigned(splits);
   }
   {
@@ -1503,7 +1522,9 @@ __global__ __launch_bounds__(256) void k_rows_sign_apply(double* __restrict__ X,
 __global__ void k_rows_sign_pivots(const double* __restrict__ X, long long dim, const long long* __restrict__ pi,
                                    double* __restrict__ pivot_vals, int count) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) pivot_vals[i] = X[(i / SIGN_SEGS) * dim + pi[i]];
+  // (an empty segment -- SIGN_SEGS * ceil(dim / SIGN_SEGS) - dim >= ceil(dim / SIGN_SEGS) -- has its candidate at its first
+  // column, at or behind the end of the row; it never wins the reduction in k_rows_sign_apply, and is not read)
+  if (i < count) pivot_vals[i] = pi[i] < dim ? X[(i / SIGN_SEGS) * dim + pi[i]] : 0.0;
 }
 
 int rom_launch_rows_sign_flip(rom_ctx* ctx, double* X, int rows, int64_t dim) {

@@ -789,7 +789,7 @@ int tall_svd_rotation(rom_ctx* ctx, double* Tt, int b, int M, double* Rt, double
 // the product enqueued in line; a guess of b that turns out wrong is discarded.
 struct SketchAhead {
   rom_ctx* ctx = nullptr;
-  Tmp Om, Q;
+  Tmp Om, Q, Part;   // Part: the split-K partials of the product (the context's scratch belongs to the main stream)
   int b = 0, seed = 0;
   bool pending = false;
   ~SketchAhead() {   // (an error return with the product still in flight: its buffers go back to the allocator only when it is done)
@@ -802,12 +802,16 @@ int sketch_ahead_start(rom_ctx* ctx, SketchAhead& sa, const double* X, int M, in
   sa.ctx = ctx;
   ROM_TRY(sa.Om.get(ctx, size_t(b) * M));
   ROM_TRY(sa.Q.get(ctx, size_t(b) * dim));
+  const size_t part_doubles = rom_gemm_nn_partial_doubles(b, dim, M, M, dim);
+  if (part_doubles) ROM_TRY(sa.Part.get(ctx, part_doubles));
+  else sa.Part.release();
   ROM_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
   ROM_HIP(hipStreamWaitEvent(ctx->aux[0], ctx->ev_fork, 0));
   hipStream_t main_stream = ctx->stream;
   ctx->stream = ctx->aux[0];
   int st = romb_fill_random(ctx, sa.Om, size_t(b) * M, 0xabcd0000ull + unsigned(seed) * 7919u, true);
-  if (st == ROM_OK) st = rom_launch_gemm_nn(ctx, b, dim, M, 1.0, sa.Om, M, X, dim, 0.0, sa.Q, dim);
+  if (st == ROM_OK) st = rom_launch_gemm_nn(ctx, b, dim, M, 1.0, sa.Om, M, X, dim, 0.0, sa.Q, dim,
+                                             part_doubles ? sa.Part.p() : nullptr);
   ctx->stream = main_stream;
   ROM_TRY(st);
   ROM_HIP(hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
@@ -1021,7 +1025,8 @@ extern "C" int rom_pod_ex(rom_ctx* ctx, rom_buf* Xb, int64_t x_row0, int M, int6
   int power = 1;   // power steps per pass: 2 once a pass has shown a spectrum too flat for one (best-effort regime below)
   SketchAhead ahead;
   // (blocks from 64 MB: below, the product is shorter than the stream hand-over.  dim >= 1024, M >= 128: the product then
-  // takes the thin LDS-DMA kernel, which needs no scratch -- the context's scratch area belongs to the kernels of the main stream)
+  // takes the thin LDS-DMA kernel; where it splits K instead, sketch_ahead_start gives it a partial buffer of its own --
+  // the context's scratch area belongs to the kernels of the main stream)
   const bool worth_ahead = size_t(M) * dim * sizeof(double) >= (size_t(64) << 20) && dim >= 1024 && M >= 128;
   // the sketch passes run until the request is filled or the spectrum has reached the floor; the budget below only guards
   // against a pass that makes no progress (every pass accepts at least one mode or ends the loop)

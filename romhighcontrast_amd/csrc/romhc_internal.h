@@ -53,6 +53,9 @@ struct rom_ctx {
   int device = 0;
   int n_cu = 0;  // compute units of the device (grid of the persistent kernels)
   hipStream_t stream = nullptr;
+  // the stream rom_init created for `stream`: code that borrows an aux stream swaps `stream` for a while, and the
+  // scratch area (rom_ctx_scratch) belongs to the kernels of this one -- it refuses to be handed out on a borrowed stream
+  hipStream_t home_stream = nullptr;
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};  // sub-batch streams of rom_solve_batch
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   // A sweep can be split into n_streams concurrent sub-batches on separate streams (ROMHC_STREAMS=1..4).  0 = the default:
