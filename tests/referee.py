@@ -167,3 +167,101 @@ def galerkin_truth_nested(g, a, C, U, sizes):
         e2 = (u2 - np.einsum("mk,mk->m", Pj, Pj)) + np.einsum("mk,mk->m", Pj - c, Pj - c)
         out[j] = np.asarray(np.sqrt(np.maximum(e2, 0) / u2), dtype=np.float64)
     return out
+
+
+# ---- the strong greedy along a given pick sequence, in extended precision -------------------------------------------
+def _grad_ld(g, X):
+    """Rows of X (FE vectors) -> long-double coordinates in which the A_1 inner product is Euclidean: the edge differences
+    and the boundary values, each scaled by the square root of its (nonnegative) edge weight."""
+    we, wn, wb = edge_weights(g, np.ones((g.nrb, g.ncb)))
+    assert we.min() >= 0 and wn.min() >= 0 and wb.min() >= 0
+    X3 = np.asarray(X).astype(LD).reshape(len(X), g.nr, g.nc)
+    return np.concatenate((((X3[:, :, :-1] - X3[:, :, 1:]) * np.sqrt(we)).reshape(len(X), -1),
+                           ((X3[:, :-1, :] - X3[:, 1:, :]) * np.sqrt(wn)).reshape(len(X), -1),
+                           (X3 * np.sqrt(wb)).reshape(len(X), -1)), axis=1)
+
+
+def greedy_ld(g, U, a, h1norm, picks, galerkin, drop=1e-16):
+    """The error vectors of the strong greedy (src/lib/ReducedBasis.py:112-139) along the pick sequence `picks` of a device
+    call, in 80-bit arithmetic from the fp64 rows U (M, dim): row i of the result (len(picks), M) holds the relative
+    errors e_i = ||u_m - approx_m|| / h1norm_m for the EXACT span of picks[:i] -- H^1_0 projection, or (galerkin) the
+    Galerkin ROM with parameters a (M, kblk): ||R_m||^2 + |p_m - c_m|^2 as in galerkin_truth_nested.
+
+    The span is carried as an A_1-orthonormal basis built incrementally (Gram-Schmidt twice per pick); the residuals of all
+    rows are updated by one vector per iteration, O(M dim) each.  A pick whose remainder is below `drop` of its own norm
+    enters as a zero direction (the device's dead-direction convention: no coupling, coefficient 0).  In Galerkin mode the
+    reduced matrices sum_b a_mb S_b (condition <= the contrast in this basis) grow by one row per iteration; their
+    Cholesky factors and the factors' inverses are bordered, O(M n^2) per iteration.  Returns (errors, live) with live[j]
+    False where pick j entered as a zero direction."""
+    U = np.asarray(U, dtype=np.float64)
+    M, n = U.shape[0], len(picks)
+    h1 = np.broadcast_to(np.asarray(h1norm, dtype=np.float64), (M,)).astype(LD)
+    GU = _grad_ld(g, U)
+    R = GU.copy()                                   # residuals of the projection, A_1 coordinates
+    nrm0 = np.sqrt(np.einsum("me,me->m", GU, GU))
+    out = np.zeros((n, M), dtype=LD)
+    live = np.ones(n, dtype=bool)
+    QF = np.zeros((max(n - 1, 0), U.shape[1]), dtype=LD)    # basis as FE vectors
+    QG = np.zeros((max(n - 1, 0), GU.shape[1]), dtype=LD)   # and in A_1 coordinates
+    if galerkin:
+        a = np.asarray(a, dtype=np.float64).reshape(M, -1).astype(LD)
+        k = a.shape[1]
+        blocks = [edge_weights(g, e) for _, _, e in ro._block_onehots(g)]
+        B = ro.load_vector(g).astype(LD)
+        nb = max(n - 1, 0)
+        Sb = np.zeros((k, nb, nb), dtype=LD)
+        Linv = np.zeros((M, nb, nb), dtype=LD)      # inverses of the Cholesky factors of the reduced matrices
+        y = np.zeros((M, nb), dtype=LD)             # L^-1 bhat
+        P = np.zeros((M, nb), dtype=LD)             # projection coefficients p_mj = <u_m, q_j>_A1
+    gap2 = np.zeros(M, dtype=LD)
+    for i in range(n):
+        e2 = np.einsum("me,me->m", R, R)
+        out[i] = np.sqrt(e2 + gap2) / h1
+        if i == n - 1:
+            break
+        p = picks[i]
+        qf, qg = U[p].astype(LD), GU[p].copy()
+        for _ in range(2):
+            if i:
+                h = QG[:i] @ qg
+                qf -= h @ QF[:i]
+                qg -= h @ QG[:i]
+        nq = np.sqrt(qg @ qg)
+        if not nq > drop * nrm0[p]:
+            live[i] = False
+            qf[:], qg[:] = 0, 0
+        else:
+            qf, qg = qf / nq, qg / nq
+        QF[i], QG[i] = qf, qg
+        pj = R @ qg
+        R -= pj[:, None] * qg[None, :]
+        if not galerkin:
+            continue
+        P[:, i] = pj
+        # the new row / column of every S_b (q_i^T A_b q_j, edge form) and of bhat
+        Q3 = QF[:i + 1].reshape(i + 1, g.nr, g.nc)
+        for b, (we, wn, wb) in enumerate(blocks):
+            Av = wb * Q3[i]
+            dh = Q3[i][:, :-1] - Q3[i][:, 1:]
+            Av[:, :-1] += we * dh
+            Av[:, 1:] -= we * dh
+            dv = Q3[i][:-1, :] - Q3[i][1:, :]
+            Av[:-1, :] += wn * dv
+            Av[1:, :] -= wn * dv
+            col = np.einsum("jrc,rc->j", Q3, Av)
+            Sb[b, i, :i + 1] = col
+            Sb[b, :i + 1, i] = col
+        bh = qf @ B
+        if not live[i]:                             # zero direction: unit diagonal, no coupling, coefficient 0
+            Linv[:, i, i] = 1
+            continue
+        Acol = (a[:, :, None] * Sb[None, :, :i + 1, i]).sum(axis=1)  # (M, i+1): column i of every reduced matrix
+        # (explicit products and sums: einsum on these strided long-double views has returned NaN at random)
+        l = (Linv[:, :i, :i] * Acol[:, None, :i]).sum(axis=2)          # L^-1 A[:i, i]
+        d = np.sqrt(Acol[:, i] - (l * l).sum(axis=1))
+        r = -(l[:, :, None] * Linv[:, :i, :i]).sum(axis=1) / d[:, None]
+        Linv[:, i, :i], Linv[:, i, i] = r, 1 / d
+        y[:, i] = (bh - (l * y[:, :i]).sum(axis=1)) / d
+        c = (Linv[:, :i + 1, :i + 1] * y[:, :i + 1, None]).sum(axis=1)  # L^-T y
+        gap2 = ((P[:, :i + 1] - c) ** 2).sum(axis=1)
+    return out, live
