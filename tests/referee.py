@@ -265,3 +265,105 @@ def greedy_ld(g, U, a, h1norm, picks, galerkin, drop=1e-16):
         c = (Linv[:, :i + 1, :i + 1] * y[:, :i + 1, None]).sum(axis=1)  # L^-T y
         gap2 = ((P[:, :i + 1] - c) ** 2).sum(axis=1)
     return out, live
+
+
+# ---- blocks whose SVD is known exactly ------------------------------------------------------------------------------
+def hadamard_columns(n, cols):
+    """Columns `cols` of the Sylvester Hadamard matrix H_n (n a power of two), as float64 +-1: H[i, j] = (-1)^popcount(i & j)."""
+    assert n >= 1 and n & (n - 1) == 0
+    cols = np.asarray(cols, dtype=np.int64)
+    x = np.arange(n, dtype=np.int64)[:, None] & cols[None, :]
+    par = np.zeros(x.shape, dtype=np.int64)
+    while x.any():
+        par ^= x & 1
+        x >>= 1
+    return 1.0 - 2.0 * par
+
+
+class ExactSVD:
+    """An (M, dim) fp64 block X = mean + sum_k s_k u_k v_k^T whose SVD is known exactly (tests/test_referee_pod.py proves it).
+
+    u_k = H_M[:, L_k] / sqrt(M) with L_k != 0 (the columns of H_M other than column 0 sum to zero: centring leaves the block
+    unchanged), v_k = the column R_k of H_D / sqrt(D) scattered into `dim` coordinates by a seeded injection, s_k = m_k 2^-e
+    with integers m_k.  With log2(M D) even, 1 / sqrt(M D) is a power of two; every entry is an integer multiple of
+    q = 2^-e / sqrt(M D) below 2^53 q (sum m_k + max |mean| < 2^53), so every partial sum of an entry, of a column sum or
+    of a product with the factors is exact in any order.  Rows past M (zero rows, `pad`) are for uncentred cases only.
+
+    Attributes: X (rows, dim) -- or None when built lazily (`factors` then holds F1 (rows, r), F2 (r, dim) with X = F1 F2
+    exactly, plus the mean); s (r,) descending; V (r, dim) the true right singular vectors; mean (dim,).
+
+    coherent=True: u_k = e_{L_k} instead, r distinct rows of any M (no mean, uncentred cases only), D a power of four.  Every
+    entry is then ONE term s_k (+-1) / sqrt(D), and the Gram matrix X X^T is diagonal: its pivoted Cholesky factor follows
+    the squared singular values exactly (Hadamard left vectors are incoherent -- every row mixes every mode -- and its
+    pivots fall much more slowly than the spectrum)."""
+
+    def __init__(self, M, D, dim, mant, e, seed=0, mean_int=None, pad=0, build=True, coherent=False):
+        if coherent:
+            assert D & (D - 1) == 0 and D.bit_length() % 2 == 1 and mean_int is None and pad == 0, "D a power of four"
+        else:
+            assert M & (M - 1) == 0 and D & (D - 1) == 0 and (M * D).bit_length() % 2 == 1, "log2(M D) must be even"
+        mant = np.asarray(mant, dtype=np.int64)
+        order = np.argsort(-mant, kind="stable")
+        mant = mant[order]
+        r = len(mant)
+        assert r < M and r <= D and dim >= D and mant.min() >= 0
+        rng = np.random.default_rng(seed)
+        self.L = rng.choice(M, size=r, replace=False) if coherent else 1 + rng.choice(M - 1, size=r, replace=False)
+        self.R = rng.choice(D, size=r, replace=False)
+        self.cols = np.sort(rng.choice(dim, size=D, replace=False)) if dim > D else np.arange(dim)
+        self.cols = rng.permutation(self.cols)
+        self.M, self.D, self.dim, self.r, self.pad, self.e, self.coherent = M, D, dim, r, pad, e, coherent
+        self.mant = mant
+        lg = ((1 if coherent else M) * D).bit_length() - 1
+        self.q = 2.0 ** (-e - lg // 2)                 # the quantum: 2^-e / sqrt(M D)
+        self.s = mant.astype(np.float64) * 2.0 ** -e
+        bound = int(mant.sum()) + (0 if mean_int is None else int(np.abs(mean_int).max()))
+        assert bound * M < 2 ** 53, "entries or column sums would not be exact"
+        self.mean_int = np.zeros(dim, dtype=np.int64) if mean_int is None else np.asarray(mean_int, dtype=np.int64)
+        self.mean = self.mean_int.astype(np.float64) * self.q
+        hd = hadamard_columns(D, self.R)               # (D, r)
+        self.F2 = np.zeros((r, dim))
+        self.F2[:, self.cols] = hd.T
+        self.V = self.F2 / np.sqrt(D)
+        if coherent:
+            self.F1 = np.zeros((M, r))
+            self.F1[self.L, np.arange(r)] = mant.astype(np.float64) * self.q
+        else:
+            self.F1 = hadamard_columns(M, self.L) * (mant.astype(np.float64) * self.q)[None, :]   # (M, r), exact
+        if pad:
+            self.F1 = np.vstack((self.F1, np.zeros((pad, r))))
+        self.X = self.dense() if build else None
+
+    @property
+    def rows(self):
+        return self.M + self.pad
+
+    def dense(self):
+        X = self.F1 @ self.F2                          # exact: integer multiples of q below 2^53 q in any order
+        if self.mean_int.any():
+            X[:self.M] += self.mean[None, :]
+        return X
+
+    def entry_int(self, i, j):
+        """X[i, j] / q in Python integer arithmetic (the proof of exactness)."""
+        if i >= self.M:
+            return 0
+        tot = int(self.mean_int[j])
+        where = np.flatnonzero(self.cols == j)
+        if where.size:
+            c = int(where[0])
+            for k in range(self.r):
+                if self.coherent:
+                    if i != int(self.L[k]):
+                        continue
+                    hm = 1
+                else:
+                    hm = -1 if bin(i & int(self.L[k])).count("1") & 1 else 1
+                hd = -1 if bin(c & int(self.R[k])).count("1") & 1 else 1
+                tot += hm * hd * int(self.mant[k])
+        return tot
+
+    def centred(self):
+        """The block after centring: the same product without the mean (u_k sum to zero)."""
+        assert self.pad == 0 and not self.coherent
+        return self.F1 @ self.F2
