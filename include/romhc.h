@@ -214,6 +214,21 @@ int rom_orthonormalize_rows(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int n, int
  * pick is index 0, as in the reference. */
 int rom_greedy(rom_fem* fem, rom_buf* U, int64_t u_row0, int M, rom_buf* a, const double* h1norm_host, int mode, int n,
                int64_t* picks_out, double* max_err_out);
+/* H^1_0 error curves of the nested spans of the basis rows C[c_row0 .. +N) over the snapshots U[u_row0 .. +M), for every
+ * dimension n = 0 .. N in one call (the statistics loop of the reference's experiment(), src/experiments/HighContrast.py:
+ * 176-214, for all n at once):
+ *   ERR[(0 * (N+1) + n) * M + m] = || u_m - P_n u_m ||_{H^1_0}      (P_n: A_1-orthogonal projector onto span C[0..n))
+ *   ERR[(1 * (N+1) + n) * M + m] = || u_m - G_n(a_m) ||_{H^1_0}     (Galerkin ROM on span C[0..n); only when a != NULL,
+ *                                                                    a: M x nrb*ncb parameters)
+ * n = 0 is the empty basis (||u_m||).  Absolute errors: divide by the snapshot norms for the reference's relative ones.
+ * Only the span counts: the call builds an A_1-orthonormal W row by row (two Gram-Schmidt rounds); a row whose residual
+ * is at roundoff of its norm (the greedy's dead-vector rule) adds no direction, its curve is flat at that n.
+ * P (M x N): p_mj = <u_m, w_j>_{A_1}, the coefficients of P_N u_m in W.  T (N x N, lower): C_i = sum_j T[i,j] w_j
+ * (column j is 0 for a dependent row j).  info_host (4 doubles, may be NULL): dependent rows, Galerkin route
+ * (-1 none, 0 reduced matrices in LDS, 1 in global memory: N > 64), passes over U, edge tiles per pass.
+ * One host synchronisation at the end.  ROM_ERR_NOT_SPD if a reduced matrix has a non-positive pivot. */
+int rom_error_curves(rom_fem* fem, rom_buf* U, int64_t u_row0, int M, rom_buf* C, int64_t c_row0, int N, rom_buf* a,
+                     rom_buf* ERR, rom_buf* P, rom_buf* T, double* info_host);
 /* PCA(n_components = n).fit (src/lib/ReducedBasis.py:196): leading n right singular vectors of the (M, dim) block
  * X[x_row0 ...] -- OVERWRITTEN when center != 0 (the column means are subtracted in place) -- into V[v_row0 ...] (n x dim, orthonormal rows,
  * scikit-learn's svd_flip(u_based_decision=False) signs) and their singular values into sigma_host (n).  Randomised

@@ -92,6 +92,7 @@ PROTOTYPES = {
     "rom_galerkin_rom": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, C.c_int, _vp, C.c_int64]),
     "rom_orthonormalize_rows": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, _vp, C.c_int64]),
     "rom_greedy": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "rom_error_curves": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "rom_pod": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp]),
     "rom_fem_energy_map": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rom_h10norm_factored": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp]),
@@ -514,6 +515,25 @@ class Fem:
         check(self.ctx.lib.rom_greedy(self.h, U.h, u_row0, M, a.h if a is not None else None, h1.ctypes.data,
                                       1 if galerkin else 0, n, picks.ctypes.data, errs.ctypes.data))
         return [int(p) for p in picks[:n]], [float(e) for e in errs[:n]]
+
+    def error_curves(self, U: Buffer, M: int, C: Buffer | None, N: int, a: Buffer | None = None, u_row0=0, c_row0=0):
+        """rom_error_curves: H^1_0 errors of the projection (and, with parameters ``a``, of the Galerkin ROM) onto the
+        nested spans of C[c_row0 .. +N) for every n = 0 .. N, over the snapshots U[u_row0 .. +M).  Returns NumPy arrays
+        (proj (N+1, M), galerkin (N+1, M) or None, P (M, N), T (N, N), info dict)."""
+        curves = 2 if a is not None else 1
+        ERR = self.ctx.alloc(max(curves * (N + 1) * M, 1))
+        Pb = self.ctx.alloc(max(M * N, 1))
+        Tb = self.ctx.alloc(max(N * N, 1))
+        info = np.zeros(4)
+        check(self.ctx.lib.rom_error_curves(self.h, U.h, u_row0, M, C.h if C is not None else None, c_row0, N,
+                                            a.h if a is not None else None, ERR.h, Pb.h, Tb.h, info.ctypes.data))
+        err = ERR.download(curves * (N + 1) * M, shape=(curves, N + 1, M)) if M else np.zeros((curves, N + 1, 0))
+        P = Pb.download(M * N, shape=(M, N)) if M * N else np.zeros((M, N))
+        T = Tb.download(N * N, shape=(N, N)) if N else np.zeros((0, 0))
+        routes = {-1: None, 0: "lds", 1: "global"}
+        inf = {"dependent_rows": int(info[0]), "galerkin_route": routes[int(info[1])], "passes": int(info[2]),
+               "edge_tiles": int(info[3])}
+        return err[0], (err[1] if a is not None else None), P, T, inf
 
     # -- basis stage on compact interface vectors (factored snapshot blocks: rom_factored.hip) --------------
     def energy_map(self, parts=7):

@@ -1140,6 +1140,22 @@ __global__ void kb_renormalise(double* __restrict__ w, long long dim, const doub
   for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < dim; j += (long long)gridDim.x * blockDim.x) w[j] *= a;
 }
 
+// One Gram-Schmidt round of w against the A_1-orthonormal rows W[0..j) (AW = A_1 W): t_i = <w_i, w>_A, w -= t^T W,
+// nrm = ||w||_A^2, then w <- w / sqrt(nrm), or 0 when degenerate[it] (the dead-vector rule of kb_take_pick).  The
+// re-orthogonalisation of the greedy and both rounds of rom_error_curves' CGS2 (rom_curves.hip).
+int romb_a1_reorth(rom_fem* f, const double* W, const double* AW, int j, double* w, double* t, double* nrm,
+                   const int* degenerate, int it) {
+  rom_ctx* ctx = f->ctx;
+  const int64_t dim = f->dim;
+  const unsigned vgrid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
+  ROM_TRY(rom_launch_rowdot(ctx, AW, j, dim, w, t));                                    // t_i = <w_i, w>_A
+  ROM_TRY(rom_launch_gemm_nn(ctx, 1, dim, j, -1.0, t, j, W, dim, 1.0, w, dim));         // w -= t^T W
+  ROM_TRY(rom_launch_h10norm(f, w, nullptr, 1, nrm, false));
+  kb_renormalise<<<vgrid, 256, 0, ctx->stream>>>(w, dim, nrm, degenerate, it);
+  ROM_HIP(hipGetLastError());
+  return ROM_OK;
+}
+
 // The pass of one greedy iteration over the training block (see above): d = Rs_m - p_prev[m] w_prev (written to Rout when
 // there is a previous update), partial sums of ||d||_A^2 in edge form and of d . z.  Layout of k_h10_partial
 // (rom_ops.hip): a thread owns a mesh column and walks down a slab of rows, every entry is read once, the halo row above
@@ -1395,13 +1411,7 @@ extern "C" int rom_greedy(rom_fem* f, rom_buf* U, int64_t u_row0, int M, rom_buf
     double* pj = P.p() + size_t(j) * M;
     kb_take_pick<<<vgrid, 256, 0, ctx->stream>>>(wj, Rs, w_prev, p_prev, dim, d_picks, it - 1, err2, norm0, d_dead);
     ROM_HIP(hipGetLastError());
-    if (j > 0) {  // one re-orthogonalisation against W in the A_1 inner product, then renormalise
-      ROM_TRY(rom_launch_rowdot(ctx, AW, j, dim, wj, t));                                    // t_i = <w_i, w>_A
-      ROM_TRY(rom_launch_gemm_nn(ctx, 1, dim, j, -1.0, t, j, W, dim, 1.0, wj, dim));         // w -= t^T W
-      ROM_TRY(rom_launch_h10norm(f, wj, nullptr, 1, nrm, false));
-      kb_renormalise<<<vgrid, 256, 0, ctx->stream>>>(wj, dim, nrm, d_dead, it - 1);
-      ROM_HIP(hipGetLastError());
-    }
+    if (j > 0) ROM_TRY(romb_a1_reorth(f, W, AW, j, wj, t, nrm, d_dead, it - 1));  // one re-orthogonalisation, renormalise
     ROM_TRY(rom_launch_stencil_apply(f, nullptr, wj, 1, zj));                                // z = A_1 w
     {
       ROM_PROF(ctx, w_prev ? "greedy_pass" : "greedy_pass_first", 16.0 * double(M) * dim, (w_prev ? 16.0 : 8.0) * double(M) * dim);

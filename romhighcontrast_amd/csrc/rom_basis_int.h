@@ -54,6 +54,10 @@ __global__ void kb_grow_ahat(double* __restrict__ Ahat, int k, int ld, int j, co
                              const int* __restrict__ degenerate, int it);
 __global__ void kb_galerkin_gap(int M, int n, const double* __restrict__ P, const double* __restrict__ c, double* __restrict__ extra2);
 __global__ void kb_ints_to_doubles(const int* __restrict__ src, double* __restrict__ dst, int n);
+__global__ void kb_renormalise(double* __restrict__ w, long long dim, const double* __restrict__ nrm2,
+                               const int* __restrict__ degenerate, int it);
+int romb_a1_reorth(rom_fem* f, const double* W, const double* AW, int j, double* w, double* t, double* nrm,
+                   const int* degenerate, int it);
 
 // ---- small dense problems and orthonormalisation helpers of rom_basis.hip, shared with rom_pod.hip ------------------
 enum { SE_EIG = 0, SE_WHITEN = 1, SE_LOWDIN = 2 };

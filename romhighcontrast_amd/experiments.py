@@ -12,8 +12,8 @@ from typing import Callable
 
 import numpy as np
 
-from .lib.ReducedBasis import INFINIT_A
-from .lib.SolutionsManagers import SolutionsManager, SolutionsManagerFEM
+from .lib.ReducedBasis import INFINIT_A, state_estimation_curves
+from .lib.SolutionsManagers import SolutionsManager, SolutionsManagerFEM, _as_device
 
 MachinePrecision = 1e-13  # (HighContrast.py:19)
 
@@ -94,12 +94,21 @@ def sample_parameters(blocks_geometry, high_contrast_blocks, diff_coef_refinemen
 
 
 def experiment_statistics(sm, a, reduced_basis_builders, vn_max_dim=20, num_measurements=50, vn_max_dim2do_stats=None,
-                          verbose=False, data=None, data_path=None):
+                          verbose=False, data=None, data_path=None, all_dims=False):
     """Snapshots, bases and the per-dimension error / time records of ``experiment()`` (:144-214),
     returned as the same ``data`` dictionary (keys ``solutions``, ``solutions_H1norm``,
     ``time2calculate_*`` and, per builder name, ``basis`` / ``time2build`` / ``errors`` / ``times``).
     Like the reference it draws the measurement points from NumPy's global RNG right after the sweep,
     so calling it after ``get_a2test_and_train(..., seed)`` reproduces the reference's points.
+
+    ``all_dims=True``: the same ``errors[n]`` records for every n <= ``vn_max_dim2do_stats`` from one error-curves call
+    per builder (rom_error_curves: projection and Galerkin errors of all nested sub-bases in one pass over the
+    snapshots, which are uploaded once for all builders); the state estimation per n on the host from that call's
+    outputs (``state_estimation_curves``: the reference's least-squares fit, error without forming the estimate) and
+    the two parameter estimators as in the per-n loop.  Timing: ``data[name]["time2curves"]`` holds the wall time of
+    the whole call (curves, point evaluation of the basis, state-estimation fits); ``times[n]`` holds that time divided
+    over the n it served in ``forward_modeling``, ``projection`` and ``state_estimation``, and the estimators' own time.
+    The default (False) runs the reference's per-n loop unchanged.
     """
     vn_max_dim2do_stats = vn_max_dim if vn_max_dim2do_stats is None else vn_max_dim2do_stats
     data = {} if data is None else data
@@ -116,6 +125,9 @@ def experiment_statistics(sm, a, reduced_basis_builders, vn_max_dim=20, num_meas
             data[builder.name] = {"errors": {}, "times": {}}
             data[builder.name]["time2build"], data[builder.name]["basis"] = calculate_time(builder.build, verbose)(
                 n=vn_max_dim, sm=sm, solutions2train=U, a2train=a, optim_method="lsq", solutions2train_h1norm=h1)
+    if all_dims:
+        _statistics_all_dims(sm, a, reduced_basis_builders, vn_max_dim, vn_max_dim2do_stats, verbose, data,
+                             measurement_points, measurements)
     for n in range(1, vn_max_dim + 1):
         for builder in reduced_basis_builders:
             rec = data[builder.name]
@@ -139,3 +151,44 @@ def experiment_statistics(sm, a, reduced_basis_builders, vn_max_dim=20, num_meas
     if data_path is not None:
         save_data(data, data_path)
     return data
+
+
+def _statistics_all_dims(sm, a, reduced_basis_builders, vn_max_dim, vn_max_dim2do_stats, verbose, data,
+                         measurement_points, measurements):
+    """The ``all_dims=True`` branch of ``experiment_statistics``: fills ``errors[n]`` / ``times[n]`` of every builder
+    for all missing n <= min(vn_max_dim, vn_max_dim2do_stats), which the per-n loop then skips."""
+    U, h1 = data["solutions"], data["solutions_H1norm"]
+    ctx = sm._ctx
+    Ud = a_dev = None
+    for builder in reduced_basis_builders:
+        rec = data[builder.name]
+        todo = [n for n in range(1, min(vn_max_dim, vn_max_dim2do_stats) + 1) if n not in rec["errors"]]
+        if not todo:
+            continue
+        if Ud is None:  # snapshots and parameters cross PCIe once for all builders
+            Ud = _as_device(ctx, U, sm.vspace_dim)
+            a_dev = ctx.upload(sm._a_batch(a))
+        basis = rec["basis"]
+        rows = np.asarray(basis.basis)
+        nmax = min(max(todo), basis.dim)  # (a basis shorter than n: basis[:n] is the whole basis, as in the per-n loop)
+        t0 = time()
+        if verbose:
+            print(f"calculating error curves of {builder.name}, n = 1 .. {nmax}")
+        proj, gal, P, T, _ = sm.error_curves(Ud, rows[:nmax], a=a_dev)
+        E = sm.evaluate_solutions(measurement_points, rows[:nmax])
+        se = state_estimation_curves(E, measurements, proj, P, T, sorted({min(n, nmax) for n in todo}))
+        rec["time2curves"] = time() - t0
+        share = rec["time2curves"] / len(todo)
+        for n in todo:
+            nn = min(n, nmax)
+            c, se_err = se[nn]
+            rb = basis[:n]
+            inv_time, inv = calculate_time(rb.parameter_estimation_inverse, verbose)(c=c)
+            lin_time, lin = calculate_time(rb.parameter_estimation_linear, verbose)(c=c)
+            rec["errors"][n] = TypeOfProblems(
+                forward_modeling=gal[nn] / h1,
+                projection=proj[nn] / h1,
+                state_estimation=se_err / h1,
+                parameter_estimation_inverse=np.abs(1 - np.array(inv) / a),
+                parameter_estimation_linear=np.abs(1 - np.array(lin) / a))
+            rec["times"][n] = TypeOfProblems(share, share, share, inv_time, lin_time)

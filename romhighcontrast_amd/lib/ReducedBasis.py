@@ -63,6 +63,25 @@ def sort_orthogonalize_base(a_selected, rb):
     return a_selected[order], orthonormalize_base(rb[order, :])
 
 
+def state_estimation_curves(E, measurements, proj, P, T, n_values):
+    """State estimation of ``BaseReducedBasis.state_estimation`` (:65-70) for every n in ``n_values`` from the outputs of
+    one error-curves call, on the host: ``{n: (c (n, M), absolute H^1_0 errors (M,))}``.
+
+    E (N, points): the N basis rows at the measurement points; measurements (M, points); proj (N+1, M): absolute
+    projection errors; P (M, N), T (N, N): the coefficients of the projections in the A_1-orthonormal basis W and
+    C = T W.  c is the reference's own least-squares fit on the first n rows (minimum norm when underdetermined); the
+    estimate c^T C[:n] = (T[:n, :n]^T c)^T W[:n] lies in span W[:n], so its error is
+    sqrt(proj_n^2 + ||T[:n, :n]^T c - p_{:n}||^2) (W is A_1-orthonormal; a dependent row has a zero column in T)."""
+    E, measurements = np.asarray(E, dtype=np.float64), np.asarray(measurements, dtype=np.float64)
+    proj, P, T = np.asarray(proj), np.asarray(P), np.asarray(T)
+    out = {}
+    for n in n_values:
+        c, *_ = np.linalg.lstsq(E[:n].T, measurements.T, rcond=-1)   # (n, M), as at :67
+        d = T[:n, :n].T @ c - P[:, :n].T
+        out[n] = (c, np.sqrt(proj[n] ** 2 + np.sum(d * d, axis=0)))
+    return out
+
+
 class BaseReducedBasis:
     """Container of a reduced basis (rows of ``basis``) and the parameters it came from, with the online
     operations of the reference (:32-98).  Pure host object: picklable, no device state."""
@@ -117,6 +136,13 @@ class BaseReducedBasis:
         c, *_ = np.linalg.lstsq(E.T, measurements.T, rcond=-1)              # (n, n_measured_states)
         estimates = c.T @ np.array(self.basis)
         return (c, estimates) if return_coefs else estimates
+
+    def error_curves(self, sm: SolutionsManager, true_solutions, a=None, n_max=None):
+        """Absolute H^1_0 errors of ``projection`` (and, with the snapshots' parameters ``a``, of ``forward_modeling``)
+        on the sub-bases ``self[:n]`` for every n = 0 .. n_max (default: all rows) in one device call; see
+        ``SolutionsManager.error_curves``."""
+        n_max = self.dim if n_max is None else min(int(n_max), self.dim)
+        return sm.error_curves(true_solutions, np.asarray(self.basis)[:n_max], a)
 
     def parameter_estimation_inverse(self, c):
         """(:72-78) harmonic-mean style estimate from the state-estimation coefficients."""

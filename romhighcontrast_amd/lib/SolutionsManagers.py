@@ -237,6 +237,26 @@ class SolutionsManager:
         """H^1_0-orthogonal projection onto span(coefficients_rom) (:108-139)."""
         return self.project_solutions_device(solutions, coefficients_rom).numpy()
 
+    def error_curves(self, solutions, coefficients_rom, a=None):
+        """H^1_0 errors of the projection onto span(coefficients_rom[:n]) -- and, with parameters ``a`` (one per
+        snapshot), of the Galerkin ROM on that span -- for every n = 0 .. N at once (one C call: rom_error_curves).
+        ``solutions``: host array or DeviceArray (a host array is uploaded once).  Absolute errors; divide by
+        ``H10norm(solutions)`` for the reference's relative ones.  Returns (proj (N+1, M), galerkin (N+1, M) or None,
+        P (M, N), T (N, N), info): P = coefficients of the projections in the A_1-orthonormal basis W the call builds,
+        coefficients_rom[i] = sum_j T[i, j] W[j]."""
+        _check_method(self.method)
+        ctx, dim = self._ctx, self.vspace_dim
+        U = _as_device(ctx, solutions, dim)
+        N = len(coefficients_rom)
+        C = _as_device(ctx, coefficients_rom, dim) if N else None
+        a_dev = None
+        if a is not None:
+            a_dev = a
+            if not isinstance(a, _ffi.Buffer):
+                ab = self._a_batch(a)
+                a_dev = ctx.upload(ab) if ab.size else ctx.alloc(1)
+        return self._fem.error_curves(U.buf, U.rows, C.buf if N else None, C.rows if N else 0, a_dev)
+
     def evaluate_solutions(self, points: np.ndarray, solutions: List[np.ndarray]) -> np.ndarray:
         raise Exception("Not implemented.")  # (:141-142)
 
