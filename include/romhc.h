@@ -190,6 +190,17 @@ int rom_rows_sign_flip(rom_ctx* ctx, rom_buf* X, int64_t row0, int rows, int64_t
  * local coordinates in the cell; out_host is (K, npts). */
 int rom_evaluate_points(rom_fem* fem, rom_buf* U, int64_t row0, int K, int npts, const int* ix_host,
                         const int* iy_host, const double* tx_host, const double* ty_host, double* out_host);
+/* H^1_0 Riesz representers of P1 point evaluations (generate_riesz, src/lib/SolutionsManagers.py:70-86, the h10
+ * branch the reference left unimplemented).  r_i = the (dim,) evaluation vector of point i, with exactly the locating
+ * convention and the domain checks of rom_evaluate_points (so r_i is row i of generate_riesz(x, "l2")).
+ * OMEGA[row0+i] = A_1^{-1} r_i for i < npts (OMEGA may be NULL: Gram only);
+ * gram_host (npts x npts, row-major, may be NULL) = r_i^T A_1^{-1} r_j, symmetric to the bit.
+ * A_1 is the 5-point Laplacian of the interior grid, diagonal in the 2-D sine basis: the representers are one sparse
+ * -> spectral kernel and two MFMA products for all points (the sine tables are built once per FE space), G one Gram
+ * product in spectral space.  A point whose three P1 weights all fall on the boundary has r_i = 0: omega_i = 0 and a
+ * zero row / column of G.  One host synchronisation at the end. */
+int rom_riesz_h10(rom_fem* fem, int npts, const int* ix_host, const int* iy_host, const double* tx_host,
+                  const double* ty_host, rom_buf* OMEGA, int64_t row0, double* gram_host);
 
 /* ---- the basis stage as single calls (rom_project_h10, rom_galerkin_rom, rom_greedy, rom_pod) --------
  * Each call enqueues all its kernels on the context's stream and waits for it once at its end (status word /

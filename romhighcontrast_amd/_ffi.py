@@ -88,6 +88,7 @@ PROTOTYPES = {
     "rom_rows_scale": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, _vp]),
     "rom_rows_sign_flip": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64]),
     "rom_evaluate_points": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "rom_riesz_h10": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "rom_project_h10": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, _vp, C.c_int64]),
     "rom_galerkin_rom": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, C.c_int, _vp, C.c_int64]),
     "rom_orthonormalize_rows": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, _vp, C.c_int64]),
@@ -574,6 +575,19 @@ class Fem:
         check(self.ctx.lib.rom_evaluate_points(self.h, U.h, row0, K, ix.size, ix.ctypes.data, iy.ctypes.data,
                                                tx.ctypes.data, ty.ctypes.data, out.ctypes.data))
         return out
+
+    def riesz_h10(self, ix, iy, tx, ty, OMEGA: Buffer | None = None, row0=0, gram=True):
+        """rom_riesz_h10: H^1_0 Riesz representers of the point evaluations (ix, iy, tx, ty as for evaluate_points) into
+        the rows OMEGA[row0 ...] when OMEGA is given; returns their Gram matrix G (npts, npts) if ``gram``, else None."""
+        ix = np.ascontiguousarray(ix, dtype=np.int32)
+        iy = np.ascontiguousarray(iy, dtype=np.int32)
+        tx, ty = _host(tx), _host(ty)
+        m = ix.size
+        G = np.empty((m, m)) if gram else None
+        check(self.ctx.lib.rom_riesz_h10(self.h, m, ix.ctypes.data, iy.ctypes.data, tx.ctypes.data, ty.ctypes.data,
+                                         OMEGA.h if OMEGA is not None else None, row0,
+                                         G.ctypes.data if gram and m else None))
+        return G
 
     def __del__(self):
         try:

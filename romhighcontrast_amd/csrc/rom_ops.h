@@ -10,12 +10,15 @@ struct StencilGeom {
 StencilGeom rom_make_geom(int nrb, int ncb, int N);
 
 // C[m,n] = alpha * A[m,k] B[k,n] + beta C.  A split-K product keeps its partials in the context's scratch, or in
-// `part_ws` (rom_gemm_nn_partial_doubles(m, n, k, lda, ldb) doubles) when one is given
+// `part_ws` (rom_gemm_nn_partial_doubles(m, n, k, lda, ldb) doubles) when one is given.  prof_name: the profile name
+// of the product (default "gemm_nn")
 int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
-                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* part_ws = nullptr);
+                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* part_ws = nullptr,
+                       const char* prof_name = nullptr);
 size_t rom_gemm_nn_partial_doubles(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb);
-// C[m,m] = A A^T (lower tiles on MFMA + mirror)
-int rom_launch_gram(rom_ctx* ctx, int64_t m, int64_t k, const double* A, int64_t lda, double* C, int64_t ldc);
+// C[m,m] = A A^T (lower tiles on MFMA + mirror); prof_name: the profile name of the product (default "gram")
+int rom_launch_gram(rom_ctx* ctx, int64_t m, int64_t k, const double* A, int64_t lda, double* C, int64_t ldc,
+                    const char* prof_name = nullptr);
 // Y[k,:] = A(coef) X[k,:]; d_coef: kblk block coefficients ON THE DEVICE, or null for the unit operator A_1
 int rom_launch_stencil_apply(rom_fem* f, const double* d_coef, const double* X, int K, double* Y);
 // the same on the interior mesh rows [row_lo, row_hi] only (Y is not written outside the slabs that cover them)

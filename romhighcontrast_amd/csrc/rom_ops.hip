@@ -459,7 +459,8 @@ __global__ void k_gram128_finish(long long m, int splits, const double* __restri
   if (c != r) C[c * ldc + r] = s;
 }
 
-static int launch_gram128(rom_ctx* ctx, int64_t m, int64_t k, const double* A, int64_t lda, double* C, int64_t ldc) {
+static int launch_gram128(rom_ctx* ctx, int64_t m, int64_t k, const double* A, int64_t lda, double* C, int64_t ldc,
+                          const char* prof_name) {
   const long long nt = (m + 127) / 128, tiles = nt * (nt + 1) / 2;
   // split K so that the grid fills whole rounds of the 512 resident workgroups (2 per CU) with little tail
   const long long smax = std::max<long long>(1, std::min<long long>(64, (k + 2047) / 2048));
@@ -475,22 +476,23 @@ static int launch_gram128(rom_ctx* ctx, int64_t m, int64_t k, const double* A, i
   double* part = nullptr;
   ROM_TRY(rom_ctx_scratch(ctx, size_t(splits) * m * m, &part));
   {
-    ROM_PROF(ctx, "gram128", double(tiles) * 2.0 * 128 * 128 * k, 8.0 * (2.0 * tiles * 128 * double(k) + double(m) * m));
+    ROM_PROF(ctx, prof_name ? prof_name : "gram128", double(tiles) * 2.0 * 128 * 128 * k, 8.0 * (2.0 * tiles * 128 * double(k) + double(m) * m));
     k_gram128<<<dim3(unsigned(tiles), 1, unsigned(splits)), 256, 0, ctx->stream>>>(m, k, kper, A, lda, part);
   }
   ROM_HIP(hipGetLastError());
   {
-    ROM_PROF(ctx, "gram128_finish", double(splits) * m * m, 8.0 * double(splits + 1) * m * m);
+    ROM_PROF(ctx, prof_name ? (std::string(prof_name) + "_finish").c_str() : "gram128_finish", double(splits) * m * m, 8.0 * double(splits + 1) * m * m);
     k_gram128_finish<<<unsigned((m * m + 255) / 256), 256, 0, ctx->stream>>>(m, splits, part, C, ldc);
   }
   ROM_HIP(hipGetLastError());
   return ROM_OK;
 }
 
-int rom_launch_gram(rom_ctx* ctx, int64_t m, int64_t k, const double* A, int64_t lda, double* C, int64_t ldc) {
+int rom_launch_gram(rom_ctx* ctx, int64_t m, int64_t k, const double* A, int64_t lda, double* C, int64_t ldc,
+                    const char* prof_name) {
   if (m <= 0) return ROM_OK;
-  if (m >= 512 && k >= 4096 && size_t(lda) * 8 * 128 < (size_t(1) << 32)) return launch_gram128(ctx, m, k, A, lda, C, ldc);
-  return rom_launch_gemm_nt_ex(ctx, m, m, k, 1.0, A, lda, A, lda, 0.0, C, ldc, "gram", 1);
+  if (m >= 512 && k >= 4096 && size_t(lda) * 8 * 128 < (size_t(1) << 32)) return launch_gram128(ctx, m, k, A, lda, C, ldc, prof_name);
+  return rom_launch_gemm_nt_ex(ctx, m, m, k, 1.0, A, lda, A, lda, 0.0, C, ldc, prof_name ? prof_name : "gram", 1);
 }
 
 extern "C" int rom_gram(rom_ctx* ctx, int64_t m, int64_t k, rom_buf* A, size_t a_off, int64_t lda, rom_buf* C,
@@ -867,13 +869,16 @@ size_t rom_gemm_nn_partial_doubles(int64_t m, int64_t n, int64_t k, int64_t lda,
 }
 
 int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
-                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* part_ws) {
+                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* part_ws,
+                       const char* prof_name) {
   if (m <= 0 || n <= 0) return ROM_OK;
   static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;  // per-shape names in the profile records
   if (gemm_nn_thin(m, n, k, lda, ldb)) {
     // thin A against the rows of a snapshot-wide B; or a tall A with a short K (the lift: output bound), in row tiles of 64
     char nm[64];
-    detail ? snprintf(nm, sizeof nm, "gemm_nn_thin_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k) : snprintf(nm, sizeof nm, "gemm_nn");
+    prof_name ? snprintf(nm, sizeof nm, "%s", prof_name)
+    : detail  ? snprintf(nm, sizeof nm, "gemm_nn_thin_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k)
+              : snprintf(nm, sizeof nm, "gemm_nn");
     ROM_PROF(ctx, nm, 2.0 * m * n * k, 8.0 * (double(m) * k + double(n) * k + double(m) * n));
     const dim3 grid{unsigned((n + 127) / 128), unsigned((m + 63) / 64)};
     switch (m > 64 ? 4 : (m + 15) / 16) {
@@ -896,7 +901,9 @@ int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alp
   }
   {
     char nm[64];
-    detail ? snprintf(nm, sizeof nm, "gemm_nn_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k) : snprintf(nm, sizeof nm, "gemm_nn");
+    prof_name ? snprintf(nm, sizeof nm, "%s", prof_name)
+    : detail  ? snprintf(nm, sizeof nm, "gemm_nn_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k)
+              : snprintf(nm, sizeof nm, "gemm_nn");
     ROM_PROF(ctx, nm, 2.0 * m * n * k, 8.0 * (double(m) * k + double(n) * k + double(m) * n));
     k_gemm_nn<<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, kper, part);
   }

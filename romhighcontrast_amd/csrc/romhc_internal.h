@@ -293,6 +293,9 @@ struct rom_fem {
   // work accounting
   double flops_solve = 0, bytes_solve = 0;
   void* fmap = nullptr;          // rom_factored_map: geometry of the snapshots in interface-vector coordinates (rom_factored.hip)
+  // rom_riesz_h10 (rom_riesz.hip): the sine tables S_r (nr x nr), S_c (nc x nc) and the 1-D eigenvalues lam_r (nr),
+  // lam_c (nc) of the unit stencil, in one block built on first use
+  double* d_riesz = nullptr;
   // factor workspace (grown on demand)
   double* d_L = nullptr;
   double* d_invL = nullptr;

@@ -13,7 +13,7 @@ return negative diagonals in R); every consumer in the reference is sign-invaria
 from __future__ import annotations
 
 from logging import warning
-from typing import List
+from typing import List, NamedTuple
 
 import numpy as np
 
@@ -82,6 +82,142 @@ def state_estimation_curves(E, measurements, proj, P, T, n_values):
     return out
 
 
+# ---- PBDW state estimation (parametrized-background data-weak; Maday, Patera, Penn, Yano 2015) --------------------------
+# The estimate from measurements y = l(u) at m points is u* = v* + eta*, v* in V_n = span(basis rows), eta* in W_m = span
+# of the H^1_0 Riesz representers omega_i of the point evaluations: u* interpolates the data and eta* is H^1_0-orthogonal
+# to V_n.  In coefficients, u* = c^T C + d^T Omega with the saddle-point system [[G, L], [L^T, 0]] [d; c] = [y; 0],
+# G = Gram matrix of the representers (G[i, j] = l_i(omega_j)), L[i, j] = l_i(C_j).
+_PBDW_PIVOT_TOL = 1e-13   # a Cholesky pivot of G below this fraction of its diagonal entry: not numerically SPD
+_PBDW_RANK_TOL = 1e-12    # sigma_min(B) / sigma_max(B) below this: the basis is not determined by the measurements
+
+
+def _pbdw_bad_points(G):
+    """Indices of the points that make the Gram matrix G singular: points whose functional vanishes (diagonal ~ 0, a point
+    on the boundary) and points that repeat another one (correlation ~ 1)."""
+    g = np.diag(G).copy()
+    bad = set(np.flatnonzero(g <= _PBDW_PIVOT_TOL * max(float(np.max(g)), np.finfo(float).tiny)).tolist())
+    ok = np.flatnonzero(g > 0)
+    s = np.sqrt(g[ok])
+    corr = G[np.ix_(ok, ok)] / s[:, None] / s[None, :]
+    i, j = np.nonzero(np.triu(np.abs(corr) >= 1.0 - 1e-10, 1))
+    bad.update(ok[i].tolist())
+    bad.update(ok[j].tolist())
+    return sorted(bad)
+
+
+def pbdw_solve(G, L, Y, A_V=None):
+    """PBDW coefficients on the host.  G (m, m): H^1_0 Gram matrix of the sensors' Riesz representers; L (m, n):
+    L[i, j] = l_i(C_j) (``evaluate_solutions(points, basis).T``); Y (K, m): measurements of K states; A_V (n, n), optional:
+    H^1_0 Gram matrix of the basis rows.
+
+    G = R^T R (Cholesky), B = R^-T L, y~ = R^-T Y^T; c = argmin ||y~ - B c|| (QR), d = R^-1 (y~ - B c).  With
+    A_V = K K^T, beta[n' - 1] = sigma_min((B K^-T)[:, :n']) for n' = 1 .. n: the inf-sup constant of V_n' against the
+    sensor space (the Cholesky factors nest, so every prefix is the constant of the first n' rows).
+
+    Returns (c (n, K), d (m, K), beta (n,) or None without A_V).  Raises ValueError if n > m, G is not numerically SPD
+    (coincident points, or a point on the boundary: named), B is rank-deficient, or A_V is not SPD."""
+    import scipy.linalg as sla
+    from scipy.linalg.lapack import dpotrf
+
+    G = np.asarray(G, dtype=np.float64)
+    L = np.asarray(L, dtype=np.float64)
+    m = G.shape[0]
+    L = L.reshape(m, -1)
+    n = L.shape[1]
+    Y = np.asarray(Y, dtype=np.float64).reshape(-1, m)
+    if n > m:
+        raise ValueError(f"PBDW needs at least as many measurements as basis vectors: n = {n} > m = {m}")
+    if m == 0:
+        return np.zeros((0, Y.shape[0])), np.zeros((0, Y.shape[0])), (np.zeros(0) if A_V is not None else None)
+    Rl, info = dpotrf(G, lower=1, clean=1)
+    piv2 = np.diag(Rl) ** 2 / np.where(np.diag(G) > 0, np.diag(G), 1.0) if info == 0 else None
+    if info != 0 or np.any(np.diag(G) <= 0) or np.min(piv2) <= _PBDW_PIVOT_TOL:
+        bad = _pbdw_bad_points(G)
+        if not bad:
+            bad = [info - 1] if info > 0 else np.flatnonzero(piv2 <= _PBDW_PIVOT_TOL).tolist()
+        raise ValueError(f"the Gram matrix of the measurement functionals is not numerically SPD: points {bad} "
+                         "(coincident points, or points whose functional vanishes on the boundary)")
+    B = sla.solve_triangular(Rl, L, lower=True)                   # R^-T L   (R = Rl^T)
+    yt = sla.solve_triangular(Rl, Y.T, lower=True)                # R^-T Y^T
+    if n:
+        sv = np.linalg.svd(B, compute_uv=False)
+        if not sv[-1] > _PBDW_RANK_TOL * sv[0]:
+            raise ValueError(f"the basis is not determined by the measurements: B = R^-T L is rank-deficient "
+                             f"(sigma_min / sigma_max = {sv[-1] / sv[0] if sv[0] > 0 else 0.0:.2e})")
+        Q, RB = np.linalg.qr(B)
+        c = sla.solve_triangular(RB, Q.T @ yt, lower=False)
+        res = yt - B @ c
+    else:
+        c = np.zeros((0, Y.shape[0]))
+        res = yt
+    d = sla.solve_triangular(Rl, res, lower=True, trans="T")       # R^-1 (y~ - B c)
+    beta = None
+    if A_V is not None:
+        A_V = np.asarray(A_V, dtype=np.float64).reshape(n, n)
+        try:
+            KV = np.linalg.cholesky(0.5 * (A_V + A_V.T)) if n else np.zeros((0, 0))
+        except np.linalg.LinAlgError as e:
+            raise ValueError(f"the H^1_0 Gram matrix of the basis is not SPD (dependent basis rows): {e}") from None
+        if n and not np.all(np.diag(KV) > 0):
+            raise ValueError("the H^1_0 Gram matrix of the basis is not SPD (dependent basis rows)")
+        BK = sla.solve_triangular(KV, B.T, lower=True).T if n else np.zeros((m, 0))   # B K^-T
+        beta = np.array([np.linalg.svd(BK[:, :k], compute_uv=False)[-1] for k in range(1, n + 1)])
+    return c, d, beta
+
+
+class PBDWResult(NamedTuple):
+    """``pbdw_state_estimation``: coefficients c (n, K) on the basis rows, d (m, K) on the representers, the inf-sup
+    constants beta (n,) of the nested sub-bases, and the K estimates c^T C + d^T Omega (K, dim)."""
+    c: np.ndarray
+    d: np.ndarray
+    beta: np.ndarray
+    estimates: object
+
+
+def _pbdw_operators(sm: SolutionsManager, basis, measurement_points, representers=True):
+    """On the device: the basis rows C (DeviceArray or None for n = 0), the representers Omega (DeviceArray or None), G,
+    L = l(C)^T and A_V = C A_1 C^T (rom_stencil_apply(unit) + rom_gemm_nt)."""
+    ctx, dim = sm._ctx, sm.vspace_dim
+    n = 0 if basis is None else len(basis)
+    C = _as_device(ctx, basis, dim) if n else None
+    Om, G = sm.riesz_h10_device(measurement_points, representers=representers)
+    m = G.shape[0]
+    if n:
+        L = sm.evaluate_solutions(measurement_points, C).T
+        AC = ctx.alloc(n * dim)
+        sm._fem.stencil_apply(C.buf, n, AC)
+        AVb = ctx.alloc(n * n)
+        ctx.gemm_nt(n, n, dim, AC, 0, dim, C.buf, 0, dim, AVb, 0, n)
+        A_V = AVb.download(n * n, shape=(n, n))
+    else:
+        L, A_V = np.zeros((m, 0)), np.zeros((0, 0))
+    return C, Om, G, L, A_V
+
+
+def pbdw_state_estimation(sm: SolutionsManager, basis, measurement_points, measurements, device=False) -> PBDWResult:
+    """PBDW estimates of the K states measured at the m points (measurements (K, m), one row per state) with the
+    background space spanned by the n rows of ``basis`` (ndarray or DeviceArray; n = 0 gives the minimum-norm interpolant
+    Omega^T G^-1 y).  G, Omega, L and A_V are formed on the device, the (m + n)-sized problem is solved on the host
+    (``pbdw_solve``), and the estimates are lifted on the device as c^T C + d^T Omega (two MFMA products into one buffer).
+    ``estimates`` is a DeviceArray if ``device``, else an ndarray."""
+    ctx, dim = sm._ctx, sm.vspace_dim
+    C, Om, G, L, A_V = _pbdw_operators(sm, basis, measurement_points)
+    m, n = G.shape[0], L.shape[1]
+    Y = np.asarray(measurements, dtype=np.float64).reshape(-1, m) if m else np.asarray(measurements).reshape(-1, 0)
+    c, d, beta = pbdw_solve(G, L, Y, A_V)
+    K = Y.shape[0]
+    est = ctx.alloc(max(K * dim, 1))
+    if K and n:
+        ctx.gemm_nn(K, dim, n, ctx.upload(np.ascontiguousarray(c.T)), 0, n, C.buf, 0, dim, est, 0, dim)
+    if K and m:
+        ctx.gemm_nn(K, dim, m, ctx.upload(np.ascontiguousarray(d.T)), 0, m, Om.buf, 0, dim, est, 0, dim,
+                    beta=1.0 if n else 0.0)
+    if K and not m:
+        est.fill(0.0)
+    out = DeviceArray(est, K, dim)
+    return PBDWResult(c, d, beta, out if device else out.numpy())
+
+
 class BaseReducedBasis:
     """Container of a reduced basis (rows of ``basis``) and the parameters it came from, with the online
     operations of the reference (:32-98).  Pure host object: picklable, no device state."""
@@ -136,6 +272,20 @@ class BaseReducedBasis:
         c, *_ = np.linalg.lstsq(E.T, measurements.T, rcond=-1)              # (n, n_measured_states)
         estimates = c.T @ np.array(self.basis)
         return (c, estimates) if return_coefs else estimates
+
+    def state_estimation_pbdw(self, sm: SolutionsManager, measurement_points: np.ndarray, measurements: np.ndarray,
+                              return_coefs=False):
+        """PBDW state estimation (``pbdw_state_estimation``): the estimates interpolate the measurements and differ from
+        the basis span by an H^1_0-orthogonal correction in the span of the sensors' Riesz representers.  c (n, K) as in
+        ``state_estimation``, so the parameter estimators accept it unchanged."""
+        r = pbdw_state_estimation(sm, self.basis, measurement_points, measurements)
+        return (r.c, r.estimates) if return_coefs else r.estimates
+
+    def pbdw_stability(self, sm: SolutionsManager, measurement_points: np.ndarray):
+        """beta_n, n = 1 .. dim: the inf-sup constants of the nested sub-bases self[:n] against the sensor space (the
+        PBDW error is at most dist(u, V_n) / beta_n)."""
+        _, _, G, L, A_V = _pbdw_operators(sm, self.basis, measurement_points, representers=False)
+        return pbdw_solve(G, L, np.zeros((0, G.shape[0])), A_V)[2]
 
     def error_curves(self, sm: SolutionsManager, true_solutions, a=None, n_max=None):
         """Absolute H^1_0 errors of ``projection`` (and, with the snapshots' parameters ``a``, of ``forward_modeling``)

@@ -325,10 +325,34 @@ class SolutionsManagerFEM(SolutionsManager):
 
     def evaluate_solutions(self, points: np.ndarray, solutions: List[np.ndarray]) -> np.ndarray:
         """P1 point evaluation (:221-244): (n_solutions, m) values at the m points (x, y)."""
-        P = np.asarray(points, dtype=np.float64).reshape(-1, 2)
         U = _as_device(self._ctx, solutions, self.vspace_dim)
+        return self._fem.evaluate_points(U.buf, U.rows, *self._locate(points))
+
+    def _locate(self, points):
+        """Cell indices and local coordinates (ix, iy, tx, ty) of the points (x, y), as evaluate_solutions locates them."""
+        P = np.asarray(points, dtype=np.float64).reshape(-1, 2)
         ix = np.searchsorted(self.points_c, P[:, 0]) - 1  # (:235)
         iy = np.searchsorted(self.points_r, P[:, 1]) - 1  # (:236)
         tx = (P[:, 0] - self.points_c[ix]) / (self.points_c[ix + 1] - self.points_c[ix])  # (:237)
         ty = (P[:, 1] - self.points_r[iy]) / (self.points_r[iy + 1] - self.points_r[iy])  # (:238)
-        return self._fem.evaluate_points(U.buf, U.rows, ix, iy, tx, ty)
+        return ix, iy, tx, ty
+
+    # -- H^1_0 Riesz representers of the point evaluations (rom_riesz_h10) ---------------------------------------------
+    def riesz_h10_device(self, points, representers=True):
+        """The H^1_0 Riesz representers omega_i = A_1^-1 r_i of the P1 evaluations at the m points (r_i: row i of
+        ``generate_riesz(points, "l2")``) and their Gram matrix G[i, j] = <omega_i, omega_j>_{H^1_0} = r_i^T A_1^-1 r_j,
+        in one device call.  Returns (DeviceArray (m, dim) or None when not ``representers``, G (m, m) ndarray)."""
+        ix, iy, tx, ty = self._locate(points)
+        m, dim = len(ix), self.vspace_dim
+        Om = self._ctx.alloc(max(m * dim, 1)) if representers else None
+        G = self._fem.riesz_h10(ix, iy, tx, ty, OMEGA=Om, gram=True)
+        return (DeviceArray(Om, m, dim) if representers else None), G
+
+    def generate_riesz_h10(self, points):
+        """(m, dim) ndarray of the H^1_0 representers, oriented as ``generate_riesz(points, "l2")`` (one row per point).
+        ``generate_riesz(x, "h10")`` itself keeps the reference's behaviour (it raises)."""
+        return self.riesz_h10_device(points)[0].numpy()
+
+    def riesz_gram_h10(self, points):
+        """G (m, m): the H^1_0 Gram matrix of the representers of the points, without forming the representers."""
+        return self.riesz_h10_device(points, representers=False)[1]
