@@ -201,6 +201,28 @@ int rom_evaluate_points(rom_fem* fem, rom_buf* U, int64_t row0, int K, int npts,
  * zero row / column of G.  One host synchronisation at the end. */
 int rom_riesz_h10(rom_fem* fem, int npts, const int* ix_host, const int* iy_host, const double* tx_host,
                   const double* ty_host, rom_buf* OMEGA, int64_t row0, double* gram_host);
+/* Greedy sensor selection for PBDW (the sampling question of the inverse-problem notebook, InverseProblemPipeline.ipynb;
+ * the experiment draws uniform random points, src/experiments/HighContrast.py:155).
+ * rom_riesz_norms_h10: out_host[i] = r_i^T A_1^{-1} r_i = ||omega_i||^2_{H^1_0} for npts points: the diagonal of
+ * rom_riesz_h10's G, without G or the representers (vertex-pair Green tables built once per FE space, at most nine
+ * table entries per point).  Same locating convention, domain check and boundary rule (a vanishing functional gives
+ * exactly 0).  One host synchronisation. */
+int rom_riesz_norms_h10(rom_fem* fem, int npts, const int* ix_host, const int* iy_host, const double* tx_host,
+                        const double* ty_host, double* out_host);
+/* Greedy selection (Binev, Cohen, Mula, Nichols 2018) of up to m of the ncand candidate points for PBDW on the span of
+ * the n rows C[c_row0 ..): W = the A_1-orthonormal basis of that span (CGS2 with the dead-row rule of rom_error_curves: a
+ * dead row gives a zero column of A), psi_k = the H^1_0-orthonormal basis of the picked points' representers in pick
+ * order, Res[i,x] = (w_i - P_{W_k} w_i)(x), nu_x = ||omega_x||^2.  Criterion: mode 0 = collective OMP,
+ * sum_i Res[i,x]^2 / nu_x; mode 1 = worst-case OMP, (sum_i alpha_i Res[i,x])^2 / nu_x with alpha a unit eigenvector of
+ * A_k^T A_k for its smallest eigenvalue; 0 where nu_x = 0.  The pick is the first maximum.  1 <= n <= 128 (96 in mode 1),
+ * 1 <= m <= 1024, ncand >= 1.  picks_out (m, int64; -1 past a stop), crit_out (m): best criterion per step,
+ * A_out (m x n): A[k,i] = <psi_k, w_i>_{H^1_0}, alpha_out (m x n, mode 1, may be NULL): the direction used at step k,
+ * info_host (4 doubles, may be NULL): dead basis rows, picks made, stop reason (0 m reached, 1 criterion below rel_tol x
+ * the first step's, 2 no candidate with a positive criterion left), host synchronisations.  One host synchronisation at
+ * the end. */
+int rom_sensor_greedy(rom_fem* fem, rom_buf* C, int64_t c_row0, int n, int ncand, const int* ix_host, const int* iy_host,
+                      const double* tx_host, const double* ty_host, int m, int mode, double rel_tol, int64_t* picks_out,
+                      double* crit_out, double* A_out, double* alpha_out, double* info_host);
 
 /* ---- the basis stage as single calls (rom_project_h10, rom_galerkin_rom, rom_greedy, rom_pod) --------
  * Each call enqueues all its kernels on the context's stream and waits for it once at its end (status word /

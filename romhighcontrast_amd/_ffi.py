@@ -89,6 +89,9 @@ PROTOTYPES = {
     "rom_rows_sign_flip": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64]),
     "rom_evaluate_points": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "rom_riesz_h10": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "rom_riesz_norms_h10": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "rom_sensor_greedy": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double,
+                                    _vp, _vp, _vp, _vp, _vp]),
     "rom_project_h10": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, _vp, C.c_int64]),
     "rom_galerkin_rom": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, C.c_int, _vp, C.c_int64]),
     "rom_orthonormalize_rows": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, _vp, C.c_int64]),
@@ -588,6 +591,33 @@ class Fem:
                                          OMEGA.h if OMEGA is not None else None, row0,
                                          G.ctypes.data if gram and m else None))
         return G
+
+    def riesz_norms_h10(self, ix, iy, tx, ty) -> np.ndarray:
+        """rom_riesz_norms_h10: ||omega_i||^2_{H^1_0} = r_i^T A_1^-1 r_i of the point evaluations (as for evaluate_points)."""
+        ix = np.ascontiguousarray(ix, dtype=np.int32)
+        iy = np.ascontiguousarray(iy, dtype=np.int32)
+        tx, ty = _host(tx), _host(ty)
+        out = np.empty(ix.size)
+        check(self.ctx.lib.rom_riesz_norms_h10(self.h, ix.size, ix.ctypes.data, iy.ctypes.data, tx.ctypes.data,
+                                               ty.ctypes.data, out.ctypes.data if ix.size else None))
+        return out
+
+    def sensor_greedy(self, Cb: Buffer, n: int, ix, iy, tx, ty, m: int, mode: int, rel_tol: float, c_row0=0):
+        """rom_sensor_greedy: greedy selection of up to m of the candidate points for PBDW on span C[c_row0 .. +n).
+        Returns (picks (m,) int64, -1 past a stop; crit (m,); A (m, n); alpha (m, n) in mode 1 else None; info dict)."""
+        ix = np.ascontiguousarray(ix, dtype=np.int32)
+        iy = np.ascontiguousarray(iy, dtype=np.int32)
+        tx, ty = _host(tx), _host(ty)
+        picks, crit = np.zeros(max(m, 1), dtype=np.int64), np.zeros(max(m, 1))
+        A = np.zeros((max(m, 1), max(n, 1)))
+        alpha = np.zeros((max(m, 1), max(n, 1))) if mode == 1 else None
+        info = np.zeros(4)
+        check(self.ctx.lib.rom_sensor_greedy(self.h, Cb.h if Cb is not None else None, c_row0, n, ix.size, ix.ctypes.data,
+                                             iy.ctypes.data, tx.ctypes.data, ty.ctypes.data, m, mode, float(rel_tol),
+                                             picks.ctypes.data, crit.ctypes.data, A.ctypes.data,
+                                             alpha.ctypes.data if alpha is not None else None, info.ctypes.data))
+        inf = {"dead_rows": int(info[0]), "picks": int(info[1]), "stop_reason": int(info[2]), "host_syncs": int(info[3])}
+        return picks[:m], crit[:m], A[:m, :n], (alpha[:m, :n] if alpha is not None else None), inf
 
     def __del__(self):
         try:

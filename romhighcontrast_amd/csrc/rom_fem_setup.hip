@@ -294,7 +294,7 @@ extern "C" int rom_fem_destroy(rom_fem* f) {
                   f->d_kptr, f->d_kpair, f->d_colptr, f->d_colrow, f->d_colti, f->d_sides, f->d_vmap, f->d_L,
                   f->d_invL, f->d_y, f->d_Bt, f->d_P, f->d_vec, f->d_rhs, f->d_pre, f->d_exp, f->d_xred, f->d_groups, f->d_cm,
                   f->d_item_group, f->d_item_k, f->d_item_cf, f->d_ctask, f->d_pairs, f->d_alist, f->d_aoff, f->d_pool_acc, f->d_wmeta, f->d_s1_items, f->d_s1_citems, f->d_lr_blocks, f->d_gen_blocks, f->d_scat, f->d_dgroups, f->d_dweight, f->d_ditem_group,
-                  f->d_ditem_k, f->d_dmat, f->d_scb, f->d_riesz};
+                  f->d_ditem_k, f->d_dmat, f->d_scb, f->d_riesz, f->d_green};
   for (void* p : ptrs)
     if (p) hipFree(p);
   rom_factored_map_free(f->fmap);

@@ -40,3 +40,39 @@ int rom_launch_rows_scale(rom_ctx* ctx, double* X, int rows, int64_t dim, const 
 int rom_launch_center_rows(rom_ctx* ctx, double* X, int M, int64_t dim, double* d_mean);
 int rom_launch_subtract_row(rom_ctx* ctx, double* X, int M, int64_t dim, const double* d_row);
 int rom_launch_rows_sign_flip(rom_ctx* ctx, double* X, int rows, int64_t dim);
+// evaluate_solutions' P1 gather (rom_ops.hip): out[k * npts + p] = U_k at point p; grid ((npts + 255) / 256, K) x 256
+__global__ void k_eval_points(int nr, int nc, long long dim, const double* __restrict__ U, int K, int npts,
+                              const int* __restrict__ ix, const int* __restrict__ iy,
+                              const double* __restrict__ tx, const double* __restrict__ ty,
+                              double* __restrict__ out);
+// the sine tables of rom_riesz_h10, built once per FE space into f->d_riesz: S_r (nr x nr), S_c (nc x nc), lam_r, lam_c
+int rom_riesz_tables(rom_fem* f);
+
+// P1 weights of a point on the interior dofs (rom_riesz.hip, rom_sensors.hip): the locating convention of k_eval_points (rom_ops.hip), vertex (y, x) of
+// the grid with its Dirichlet ring -> dof (y-1, x-1); weights on boundary vertices drop out (y = -1: none)
+struct PointWeights {
+  int y[3], x[3];
+  double w[3];
+};
+__device__ inline PointWeights point_weights(int nr, int nc, int x0, int y0, double qx, double qy) {
+  PointWeights pw;
+  if (qx + qy < 1) {
+    pw.w[0] = 1 - qx - qy; pw.y[0] = y0;     pw.x[0] = x0;
+    pw.w[1] = qx;          pw.y[1] = y0;     pw.x[1] = x0 + 1;
+    pw.w[2] = qy;          pw.y[2] = y0 + 1; pw.x[2] = x0;
+  } else {
+    pw.w[0] = qx + qy - 1; pw.y[0] = y0 + 1; pw.x[0] = x0 + 1;
+    pw.w[1] = 1 - qx;      pw.y[1] = y0 + 1; pw.x[1] = x0;
+    pw.w[2] = 1 - qy;      pw.y[2] = y0;     pw.x[2] = x0 + 1;
+  }
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    if (pw.y[t] >= 1 && pw.y[t] <= nr && pw.x[t] >= 1 && pw.x[t] <= nc) {
+      pw.y[t] -= 1;
+      pw.x[t] -= 1;
+    } else {
+      pw.y[t] = -1;
+    }
+  }
+  return pw;
+}

@@ -51,35 +51,6 @@ __global__ void kr_sine(double* __restrict__ S, double* __restrict__ lam, int n)
   }
 }
 
-// P1 weights of point i on the interior dofs: the locating convention of k_eval_points (rom_ops.hip), vertex (y, x) of
-// the grid with its Dirichlet ring -> dof (y-1, x-1); weights on boundary vertices drop out (y = -1: none)
-struct PointWeights {
-  int y[3], x[3];
-  double w[3];
-};
-__device__ inline PointWeights point_weights(int nr, int nc, int x0, int y0, double qx, double qy) {
-  PointWeights pw;
-  if (qx + qy < 1) {
-    pw.w[0] = 1 - qx - qy; pw.y[0] = y0;     pw.x[0] = x0;
-    pw.w[1] = qx;          pw.y[1] = y0;     pw.x[1] = x0 + 1;
-    pw.w[2] = qy;          pw.y[2] = y0 + 1; pw.x[2] = x0;
-  } else {
-    pw.w[0] = qx + qy - 1; pw.y[0] = y0 + 1; pw.x[0] = x0 + 1;
-    pw.w[1] = 1 - qx;      pw.y[1] = y0 + 1; pw.x[1] = x0;
-    pw.w[2] = 1 - qy;      pw.y[2] = y0;     pw.x[2] = x0 + 1;
-  }
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    if (pw.y[t] >= 1 && pw.y[t] <= nr && pw.x[t] >= 1 && pw.x[t] <= nc) {
-      pw.y[t] -= 1;
-      pw.x[t] -= 1;
-    } else {
-      pw.y[t] = -1;
-    }
-  }
-  return pw;
-}
-
 // Rhat_i[j,k] = sum_t w_t S_r[j, y_t] S_c[x_t, k].  Gs[i][j*nc + k] = Rhat / sqrt(Lambda); What[j][i][k] = Rhat / Lambda
 // (What may be null).  Thread: one (j, k); grid.y strides over the points.
 __global__ __launch_bounds__(256) void kr_spectral(int nr, int nc, int npts, const int* __restrict__ ix,
@@ -116,7 +87,10 @@ __global__ __launch_bounds__(256) void kr_permute(int nr, int nc, int npts, cons
   }
 }
 
-int riesz_tables(rom_fem* f) {
+}  // namespace
+
+// (shared with rom_sensors.hip, declared in rom_ops.h)
+int rom_riesz_tables(rom_fem* f) {
   if (f->d_riesz) return ROM_OK;
   rom_ctx* ctx = f->ctx;
   const size_t n = size_t(f->nr) * f->nr + size_t(f->nc) * f->nc + f->nr + f->nc;
@@ -135,8 +109,6 @@ int riesz_tables(rom_fem* f) {
   return ROM_OK;
 }
 
-}  // namespace
-
 extern "C" int rom_riesz_h10(rom_fem* f, int npts, const int* ix_host, const int* iy_host, const double* tx_host,
                              const double* ty_host, rom_buf* OMEGA, int64_t row0, double* gram_host) {
   ROM_CHECK(f && (npts == 0 || (ix_host && iy_host && tx_host && ty_host)), "rom_riesz_h10: null argument");
@@ -149,7 +121,7 @@ extern "C" int rom_riesz_h10(rom_fem* f, int npts, const int* ix_host, const int
               "rom_riesz_h10: point %d outside the domain", p);
   if (npts == 0 || (!OMEGA && !gram_host)) return ROM_OK;
   rom_ctx* ctx = f->ctx;
-  ROM_TRY(riesz_tables(f));
+  ROM_TRY(rom_riesz_tables(f));
   const double* Sr = f->d_riesz;
   const double* Sc = Sr + size_t(nr) * nr;
   const double* lr = Sc + size_t(nc) * nc;

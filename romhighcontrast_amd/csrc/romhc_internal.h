@@ -296,6 +296,9 @@ struct rom_fem {
   // rom_riesz_h10 (rom_riesz.hip): the sine tables S_r (nr x nr), S_c (nc x nc) and the 1-D eigenvalues lam_r (nr),
   // lam_c (nc) of the unit stencil, in one block built on first use
   double* d_riesz = nullptr;
+  // rom_riesz_norms_h10 / rom_sensor_greedy (rom_sensors.hip): the vertex-pair Green tables T_00, T_01, T_10, T_11
+  // (A_1^-1 between dof (y, x) and (y + dy, x + dx), each nr x nc), built on first use
+  double* d_green = nullptr;
   // factor workspace (grown on demand)
   double* d_L = nullptr;
   double* d_invL = nullptr;

@@ -218,6 +218,66 @@ def pbdw_state_estimation(sm: SolutionsManager, basis, measurement_points, measu
     return PBDWResult(c, d, beta, out if device else out.numpy())
 
 
+# ---- greedy sensor selection for PBDW (Binev, Cohen, Mula, Nichols 2018; rom_sensor_greedy) ------------------------------
+# From a dictionary of candidate points, the greedy adds the point whose representer best captures the part of V_n that
+# the chosen sensors do not see yet ("collective": all basis directions at once; "worst": the direction of V_n the sensors
+# see worst, the smallest singular direction of A).  The whole loop runs on the device in one call; beta is formed on the
+# host from A, A[j, i] = <psi_j, w_i>_{H^1_0} with psi_j / w_i orthonormal bases of W_k / V_n.
+_SENSOR_MODES = {"collective": 0, "worst": 1}
+_SENSOR_STOPS = {0: "m", 1: "captured", 2: "no_candidates"}
+
+
+class SensorSelection(NamedTuple):
+    """``select_sensors_pbdw``: the k picked points (k, 2) and their indices into the candidates (k,), in pick order;
+    beta (k,): beta(V_n, W_j) for j = 1 .. k (0 while j is below the number n' of independent basis rows); the greedy's
+    criterion at every pick (k,); and why the selection ended: "m" (m points picked), "captured" (the criterion fell below
+    rel_tol times the first one), "no_candidates" (no candidate with a positive criterion left) or "beta_target"."""
+    points: np.ndarray
+    picks: np.ndarray
+    beta: np.ndarray
+    criterion: np.ndarray
+    stop_reason: str
+
+
+def sensor_beta_prefix(A, n_live, beta_target=None):
+    """beta_j = beta(V_n, W_j) for j = 1 .. k from A (k, n), whose dead basis rows are zero columns: the n_live-th largest
+    singular value of A[:j] -- sigma_min(A[:j, live]), the dead columns only add zero singular values -- for j >= n_live,
+    0 below.  With ``beta_target``, the prefix up to the first j with beta_j >= beta_target (the greedy is sequential, so
+    that prefix is exactly what a run stopped there would pick).  Returns (beta (k',), k', whether the target was met)."""
+    A = np.asarray(A, dtype=np.float64)
+    k = A.shape[0]
+    beta = np.zeros(k)
+    if n_live > 0:
+        for j in range(n_live, k + 1):
+            beta[j - 1] = np.linalg.svd(A[:j], compute_uv=False)[n_live - 1]
+    if beta_target is not None:
+        hit = np.flatnonzero(beta >= beta_target)
+        if hit.size:
+            return beta[:hit[0] + 1], int(hit[0]) + 1, True
+    return beta, k, False
+
+
+def select_sensors_pbdw(sm: SolutionsManager, basis, candidates, m, mode="collective", beta_target=None,
+                        rel_tol=1e-10) -> SensorSelection:
+    """Greedy selection of up to m of the ``candidates`` (K, 2) as PBDW sensors for the span of the rows of ``basis``
+    (ndarray or DeviceArray); ``sm.interior_vertices()`` is the natural candidate set.  mode "collective" or "worst" (the
+    two OMP variants of Binev, Cohen, Mula and Nichols); the selection stops after m picks, when the criterion falls to
+    ``rel_tol`` times the first step's, when no candidate with a positive criterion is left, or -- with ``beta_target`` --
+    at the first j with beta(V_n, W_j) >= beta_target.  Raises ValueError for an empty basis or an unknown mode."""
+    if mode not in _SENSOR_MODES:
+        raise ValueError(f"mode must be one of {sorted(_SENSOR_MODES)}, not {mode!r}")
+    n = 0 if basis is None else len(basis)
+    if n == 0:
+        raise ValueError("sensor selection needs a basis: with n = 0 there is nothing to observe")
+    P = np.asarray(candidates, dtype=np.float64).reshape(-1, 2)
+    C = _as_device(sm._ctx, basis, sm.vspace_dim)
+    picks, crit, A, _, info = sm._fem.sensor_greedy(C.buf, n, *sm._locate(P), int(m), _SENSOR_MODES[mode], rel_tol)
+    k = info["picks"]
+    beta, k, reached = sensor_beta_prefix(A[:k], n - info["dead_rows"], beta_target)
+    stop = "beta_target" if reached else _SENSOR_STOPS[info["stop_reason"]]
+    return SensorSelection(P[picks[:k]], picks[:k].copy(), beta, crit[:k].copy(), stop)
+
+
 class BaseReducedBasis:
     """Container of a reduced basis (rows of ``basis``) and the parameters it came from, with the online
     operations of the reference (:32-98).  Pure host object: picklable, no device state."""
@@ -286,6 +346,10 @@ class BaseReducedBasis:
         PBDW error is at most dist(u, V_n) / beta_n)."""
         _, _, G, L, A_V = _pbdw_operators(sm, self.basis, measurement_points, representers=False)
         return pbdw_solve(G, L, np.zeros((0, G.shape[0])), A_V)[2]
+
+    def select_sensors(self, sm: SolutionsManager, candidates: np.ndarray, m: int, **kw) -> SensorSelection:
+        """Greedy PBDW sensor selection for this basis (``select_sensors_pbdw``; mode, beta_target, rel_tol as there)."""
+        return select_sensors_pbdw(sm, self.basis, candidates, m, **kw)
 
     def error_curves(self, sm: SolutionsManager, true_solutions, a=None, n_max=None):
         """Absolute H^1_0 errors of ``projection`` (and, with the snapshots' parameters ``a``, of ``forward_modeling``)

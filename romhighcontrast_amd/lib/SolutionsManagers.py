@@ -356,3 +356,14 @@ class SolutionsManagerFEM(SolutionsManager):
     def riesz_gram_h10(self, points):
         """G (m, m): the H^1_0 Gram matrix of the representers of the points, without forming the representers."""
         return self.riesz_h10_device(points, representers=False)[1]
+
+    def riesz_norms_h10(self, points):
+        """(K,) ||omega_x||_{H^1_0} of the representers of the K points: sqrt(diag(riesz_gram_h10(points))) without G,
+        from vertex-pair Green tables cached on the FE space (rom_riesz_norms_h10).  0 where the functional vanishes."""
+        return np.sqrt(self._fem.riesz_norms_h10(*self._locate(points)))
+
+    def interior_vertices(self):
+        """(dim, 2) coordinates (x, y) of the interior mesh vertices in dof order: the natural candidate set of the
+        sensor selection (``select_sensors_pbdw``)."""
+        X, Y = np.meshgrid(self.points_c[1:-1], self.points_r[1:-1])
+        return np.c_[X.ravel(), Y.ravel()]
