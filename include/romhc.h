@@ -282,6 +282,27 @@ int rom_pod(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int64_t dim, int n,
  * rel_floor <= 1e-13 is rom_pod. */
 int rom_pod_ex(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int64_t dim, int n, int center, double rel_floor, rom_buf* V,
                int64_t v_row0, double* sigma_host, double* info_host);
+/* PCA(n_components = n).fit + .transform of a TALL block (src/experiments/NonLinearROM.py:34-41: 25,000 x 81): ALL the
+ * information of the row-major (M, dim) block X[x_row0 ...], dim <= 1024, by a block one-sided Jacobi whose sweeps are Gram
+ * matrices of the rotated data -- Y = Xc V^T, G = Y^T Y (dim x dim, from the DATA, never as V C V^T), Jacobi of G with the
+ * relative stopping rule (rom_small_eig_host, gram_like = 2), V <- Q^T V -- until |g_ij| <= 64 eps max(d) max(d_i, d_j),
+ * d_i = sqrt(g_ii), for all i != j (at most 6 passes; 3 are typical).  No sqrt(eps) floor as in a one-pass covariance
+ * eigendecomposition: singular values come out to eps sigma_1 + M eps sigma_i over the whole fp64 range.
+ * dim <= 96: one fused MFMA kernel per pass (rotation + Gram matrix + scores, the block read once).  Larger dim: rom_gemm_nt
+ * + a TN Gram kernel; that form takes M <= 65535 * 64 rows and, unless S is given with n = dim, a temporary of M x dim doubles.
+ * center != 0 subtracts the column means in place (X is OVERWRITTEN with the centred block, as in rom_pod).
+ * V[v_row0 ...]: n x dim components, rows of a COMPLETE orthonormal basis (the rotation is square: nothing is completed
+ * with random directions), scikit-learn's svd_flip(u_based_decision=False) signs.
+ * S[s_row0 ...] (may be NULL): M x n scores Xc V^T (pca.transform).  mean (may be NULL): the dim column means (zeros when
+ * center = 0).  sigma_host (n): the measured 2-norm of score column i, descending, also below the noise floor.
+ * Meant for M >= dim, correct for any M >= 1 (a wide block has dim - rank modes at noise level); 0 <= n <= dim.
+ * info_host (8 doubles or NULL): resolved modes #{sigma_i > 1e-13 sigma_1} among the n, passes over the block, Jacobi
+ * decompositions, executed flops, largest |g_ij| / tol_ij of the last pass, stop reason (0 converged, 1 pass budget), host
+ * synchronisations, 0.  Host synchronisations: one per pass, one at the end, one where the modes are put in order; for
+ * dim > 96 the grid-wide Jacobi adds one per sweep and three per decomposition (DESIGN.md 5.6 gives typical counts).
+ * Deterministic (fixed-order partial sums, no floating-point atomics).  NaN / Inf entries are an error, as in rom_pod. */
+int rom_pca_tall(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int dim, int n, int center, rom_buf* V, int64_t v_row0,
+                 rom_buf* S, int64_t s_row0, rom_buf* mean, double* sigma_host, double* info_host);
 /* ---- the basis stage on a snapshot block held in FACTORED form ---------------------------------------------------------
  * A sweep gathered from several GPUs exists on every rank as interface vectors, not as rows (rom_comm_allgather_packed_
  * async); when rom_fem_expansion_is_linear() the rows are U = Y B^T with a fixed B, so the builders below work on the
@@ -311,7 +332,8 @@ int rom_complete_orthonormal(rom_ctx* ctx, rom_buf* V, int64_t v_row0, int found
  * the rank-revealing whitening transform [L_r^-1 0] P of the pivoted Cholesky factorisation P A P^T = L L^T (lam_host:
  * squared pivots), what the orthonormalisations of rom_pod use.
  * gram_like != 0: A is a Gram matrix of explicit rows (entries accurate relative to sqrt(a_pp a_qq): small eigenvalues
- * of graded matrices come out to high relative accuracy); 0: general symmetric matrix (absolute accuracy).  Test hook. */
+ * of graded matrices come out to high relative accuracy); 0: general symmetric matrix (absolute accuracy).  gram_like = 2:
+ * the same with the rotation threshold 16 eps sqrt(a_pp a_qq) instead of n eps (what rom_pca_tall uses).  Test hook. */
 int rom_small_eig_host(rom_ctx* ctx, int n, const double* A_host, int mode, double rel_tol, int gram_like,
                        double* lam_host, double* T_host);
 

@@ -103,6 +103,7 @@ PROTOTYPES = {
     "rom_greedy_factored": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "rom_pod_factored": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp]),
     "rom_pod_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, _vp, C.c_int64, _vp, _vp]),
+    "rom_pca_tall": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp]),
     "rom_symmetric_orthonormalize": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64]),
     "rom_complete_orthonormal": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "rom_small_eig_host": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_double, C.c_int, _vp, _vp]),
@@ -291,6 +292,16 @@ class Context:
                  stop_reason=("filled", "floor", "budget")[int(info[7])])
         return sigma[:n], d
 
+    def pca_tall(self, X: "Buffer", M, dim, n, V: "Buffer", S: "Buffer | None" = None, mean: "Buffer | None" = None, center=True,
+                 x_row0=0, v_row0=0, s_row0=0):
+        """rom_pca_tall: X is overwritten when center.  Returns (sigma (n,), info dict)."""
+        sigma, info = np.zeros(max(n, 1)), np.zeros(8)
+        check(self.lib.rom_pca_tall(self.h, X.h, x_row0, M, dim, n, 1 if center else 0, V.h, v_row0, S.h if S is not None else None,
+                                    s_row0, mean.h if mean is not None else None, sigma.ctypes.data, info.ctypes.data))
+        d = dict(resolved_modes=int(info[0]), passes=int(info[1]), decompositions=int(info[2]), executed_flops=float(info[3]),
+                 worst_ratio=float(info[4]), stop_reason=("converged", "budget")[int(info[5])], host_syncs=int(info[6]))
+        return sigma[:n], d
+
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):
         check(self.lib.rom_symmetric_orthonormalize(self.h, V.h, v_row0, n, dim))
 
@@ -301,7 +312,7 @@ class Context:
         A = _host(A)
         n = A.shape[0]
         lam, T = np.empty(n), np.empty((n, n))
-        check(self.lib.rom_small_eig_host(self.h, n, A.ctypes.data, mode, rel_tol, 1 if gram_like else 0, lam.ctypes.data,
+        check(self.lib.rom_small_eig_host(self.h, n, A.ctypes.data, mode, rel_tol, int(gram_like), lam.ctypes.data,
                                           T.ctypes.data))
         return lam, T
 

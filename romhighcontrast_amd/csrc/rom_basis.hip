@@ -254,7 +254,8 @@ __global__ __launch_bounds__(SE_TPB) void kb_small_eig(int n, const double* __re
       vj[u] = idx - vk[u] * n;
     }
   }
-  const double tol = double(n > 8 ? n : 8) * 1.1e-16, tol2 = tol * tol, floor_abs = fmax(1e-300, 1e-40 * dmax);
+  const double tol = (gram_like == 2 ? 16.0 : double(n > 8 ? n : 8)) * 1.1e-16;   // (gram_like == 2: romb_small_eig's `tight`)
+  const double tol2 = tol * tol, floor_abs = fmax(1e-300, 1e-40 * dmax);
   for (int i = t; i < n; i += SE_TPB) nu2[i] = gram_like ? fabs(As[i * ld + i]) : dmax;
   __syncthreads();
   for (int sweep = 0; sweep < 40; ++sweep) {
@@ -733,7 +734,7 @@ __global__ __launch_bounds__(256) void kb_jgrid_params(int n, int ne, const doub
   __syncthreads();
   dmax = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
   if (t == 0) {
-    const double tol = double(n > 8 ? n : 8) * 1.1e-16;
+    const double tol = (gram_like == 2 ? 16.0 : double(n > 8 ? n : 8)) * 1.1e-16;
     par[0] = dmax;
     par[1] = tol * tol;
     par[2] = fmax(1e-300, 1e-40 * dmax);
@@ -760,7 +761,7 @@ __global__ void kb_jgrid_gather(int n, int ne, const double* __restrict__ Vc, co
 // (mode / rel_tol as kb_small_eig: SE_EIG rows = eigenvectors, SE_WHITEN rows / sqrt(lam) -- zero rows below rel_tol x the
 // largest eigenvalue --, SE_LOWDIN the symmetric inverse square root over the same eigenpairs)
 static int jacobi_grid(rom_ctx* ctx, int n, const double* A, int lda, double* lam, double* T, int ldt, int mode, double rel_tol,
-                       bool gram_like) {
+                       int gram_like) {
   const int ne = n + (n & 1), half = ne / 2;
   const size_t nn = size_t(ne) * ne;
   Tmp A0, A1, V0, V1, nu0, nu1, par, diag, anyb, permb;
@@ -778,7 +779,7 @@ static int jacobi_grid(rom_ctx* ctx, int n, const double* A, int lda, double* la
   int* d_perm = reinterpret_cast<int*>(permb.p());
   ROM_PROF(ctx, "jacobi_grid", 30.0 * n * double(n) * n, 16.0 * double(n) * n);
   kb_jgrid_init<<<unsigned((nn + 255) / 256), 256, 0, ctx->stream>>>(n, ne, A, lda, A0, V0);
-  kb_jgrid_params<<<1, 256, 0, ctx->stream>>>(n, ne, A0, gram_like ? 1 : 0, par, nu0);
+  kb_jgrid_params<<<1, 256, 0, ctx->stream>>>(n, ne, A0, gram_like, par, nu0);
   ROM_HIP(hipGetLastError());
   double *Ac = A0, *An = A1, *Vc = V0, *Vn = V1, *nuc = nu0, *nun = nu1;
   const long long threads = (long long)half * half + (long long)half * ne;
@@ -795,12 +796,14 @@ static int jacobi_grid(rom_ctx* ctx, int n, const double* A, int lda, double* la
     int any = 0;
     ROM_HIP(hipMemcpyAsync(&any, d_any, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     ROM_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->host_syncs += 1;
     if (!any) break;
   }
   kb_jgrid_diag<<<unsigned((n + 255) / 256), 256, 0, ctx->stream>>>(n, ne, Ac, diag);
   ROM_HIP(hipGetLastError());
   std::vector<double> d(n);
   ROM_TRY(download(ctx, diag, d.data(), n));
+  ctx->host_syncs += 1;
   std::vector<int> perm(n);
   for (int i = 0; i < n; ++i) perm[i] = i;
   std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return d[a] > d[b]; });   // (descending, first index first on ties)
@@ -831,14 +834,18 @@ static int jacobi_grid(rom_ctx* ctx, int n, const double* A, int lda, double* la
     ROM_TRY(rom_launch_gemm_nt(ctx, n, n, n, 1.0, St, n, St, n, 0.0, T, ldt, "gemm_nt"));
   }
   ROM_HIP(hipStreamSynchronize(ctx->stream));   // (perm / scale are host memory of this frame)
+  ctx->host_syncs += 1;
   return ROM_OK;
 }
 
 int romb_small_eig(rom_ctx* ctx, int n, const double* A, int lda, double* lam, double* T, int ldt, int mode, double rel_tol,
-                     bool gram_like) {
+                     bool gram_like, bool tight) {
   if (n <= 0) return ROM_OK;
+  // what the kernels get: 0 general symmetric, 1 Gram-like, 2 Gram-like with the rotation threshold 16 eps instead of n eps
+  // (rom_pca_tall: its own convergence test, 64 eps max(d) max(d_i, d_j), must lie above what the sweeps leave behind)
+  const int gl = gram_like ? (tight ? 2 : 1) : 0;
   ROM_CHECK(n <= SE_GRID_MAX, "small symmetric eigenproblem: n = %d beyond %d", n, SE_GRID_MAX);
-  if (n > SE_LDS_MAX) return jacobi_grid(ctx, n, A, lda, lam, T, ldt, mode, rel_tol, gram_like);   // (one launch per round, the whole chip)
+  if (n > SE_LDS_MAX) return jacobi_grid(ctx, n, A, lda, lam, T, ldt, mode, rel_tol, gl);   // (one launch per round, the whole chip)
   const int ld = n | 1, half = (n + (n & 1)) / 2;
   const size_t vec = (2 * size_t(half) + 2 * size_t(n) + 8) * sizeof(double) + (2 * size_t(half) + n + 2) * sizeof(int);
   size_t lds = vec + 16 + 2 * size_t(n) * ld * sizeof(double);   // (n <= SE_LDS_MAX here: matrix + eigenvector rows in LDS)
@@ -856,8 +863,8 @@ int romb_small_eig(rom_ctx* ctx, int n, const double* A, int lda, double* lam, d
     ROM_PROF(ctx, nm, 30.0 * n * n * n, 16.0 * n * n);
     // n <= 32: ONE wave -- no barrier between the phases of a round and the item map divided out once: 5x the rounds per
     // microsecond of the 512-thread form on the same rotations (same results)
-    if (n <= 32 && mode == SE_EIG) kb_jacobi32<<<1, 256, 0, ctx->stream>>>(n, A, lda, lam, T, ldt, gram_like ? 1 : 0);
-    else kb_small_eig<512, false><<<1, 512, lds, ctx->stream>>>(n, A, lda, lam, T, ldt, mode, rel_tol, gram_like ? 1 : 0, nullptr, ns_ws);
+    if (n <= 32 && mode == SE_EIG) kb_jacobi32<<<1, 256, 0, ctx->stream>>>(n, A, lda, lam, T, ldt, gl);
+    else kb_small_eig<512, false><<<1, 512, lds, ctx->stream>>>(n, A, lda, lam, T, ldt, mode, rel_tol, gl, nullptr, ns_ws);
   }
   ROM_HIP(hipGetLastError());
   return ROM_OK;
@@ -875,7 +882,7 @@ extern "C" int rom_small_eig_host(rom_ctx* ctx, int n, const double* A_host, int
   ROM_TRY(T.get(ctx, size_t(n) * n));
   ROM_HIP(hipMemcpyAsync(A.p(), A_host, size_t(n) * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (mode == 3) ROM_TRY(romb_pivchol_whiten(ctx, n, A, n, lam, T, n, rel_tol));
-  else ROM_TRY(romb_small_eig(ctx, n, A, n, lam, T, n, mode, rel_tol, gram_like != 0));
+  else ROM_TRY(romb_small_eig(ctx, n, A, n, lam, T, n, mode, rel_tol, gram_like != 0, gram_like == 2));
   ROM_TRY(download(ctx, lam, lam_host, n));
   return download(ctx, T, T_host, size_t(n) * n);
 }

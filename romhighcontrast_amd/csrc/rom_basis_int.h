@@ -68,8 +68,9 @@ constexpr int SE_GRID_MAX = 2048;
 __global__ void kb_rows_axpy(double* __restrict__ out, const double* __restrict__ x, const double* __restrict__ y,
                              const double* __restrict__ f, double s, long long dim);
 int romb_fill_random(rom_ctx* ctx, double* p, size_t n, unsigned long long seed, bool gaussian);
+// tight (with gram_like): rotate down to |a_pq| <= 16 eps sqrt(a_pp a_qq) instead of n eps
 int romb_small_eig(rom_ctx* ctx, int n, const double* A, int lda, double* lam, double* T, int ldt, int mode, double rel_tol,
-                   bool gram_like = true);
+                   bool gram_like = true, bool tight = false);
 int romb_pivchol_whiten(rom_ctx* ctx, int n, const double* A, int lda, double* lam, double* T, int ldt, double rel_tol);
 int romb_gram_transform(rom_ctx* ctx, double* X, double* Y, int b, int64_t dim, int mode, double rel_tol, int rounds);
 int romb_orthonormalize_against(rom_ctx* ctx, double* V, int found, int take, int64_t dim);

@@ -81,7 +81,8 @@ __device__ inline bool jacobi32_run(int n, Jacobi32Lds& L, int gram_like, double
   if (t < 32) L.nu2[0][t] = t < n ? (gram_like ? fabs(L.As[t * LD + t]) : dmax) : 0.0;
   const bool on = t < half * half;
   const int bk = on ? t / half : 0, bl = on ? t - bk * half : 0;
-  const double tol = double(n > 8 ? n : 8) * 1.1e-16, tol2 = tol * tol, floor_abs = fmax(1e-300, 1e-40 * dmax);
+  const double tol = (gram_like == 2 ? 16.0 : double(n > 8 ? n : 8)) * 1.1e-16;   // (gram_like == 2: romb_small_eig's `tight`)
+  const double tol2 = tol * tol, floor_abs = fmax(1e-300, 1e-40 * dmax);
   __syncthreads();
   int cur = 0;
   bool ever = false;

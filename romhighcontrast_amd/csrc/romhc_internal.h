@@ -89,7 +89,10 @@ struct rom_ctx {
   const double* slot_hi[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
   bool slot_joined[2] = {true, true};
   // kernels that need more than 64 KB of dynamic LDS must opt in once per DEVICE (a context is one device)
-  bool lds_optin_reduced_solve = false, lds_optin_small_eig = false, lds_optin_pivchol = false;
+  // host synchronisations of the helpers that wait inside a call (the grid-wide Jacobi): callers that report their count
+  // read the difference
+  unsigned long long host_syncs = 0;
+  bool lds_optin_reduced_solve = false, lds_optin_small_eig = false, lds_optin_pivchol = false, lds_optin_pca_tall = false;
 };
 
 struct rom_buf {

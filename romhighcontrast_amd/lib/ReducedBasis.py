@@ -586,3 +586,107 @@ class ReducedBasisPCA(BaseReducedBasis):
         super().set(basis=np.vstack((basis, comps))[:n], a=np.vstack((a, a2train))[:n])
         warning("PCA method has not been adapted for inverse parameter estimation, the a coefficients are not correct.")
         return self
+
+
+# ---- full PCA of a tall block (M >> dim): rom_pca_tall ---------------------------------------------------------------------
+class TallPCA:
+    """Result of ``pca_tall``, with scikit-learn's attribute names: ``components_`` (n, dim), ``singular_values_`` (n,),
+    ``explained_variance_`` = sigma^2 / (M - 1), ``explained_variance_ratio_``, ``mean_`` (dim,), ``n_samples_``,
+    ``n_components_``; and ``resolved_modes_`` (modes above 1e-13 sigma_1: what the fp64 data determine), ``scores`` (M, n)
+    = ``pca.transform`` of the training block (a DeviceArray with ``download=False``, None when not asked for), ``info``
+    (pass and flop counts of the call).  ``explained_variance_ratio_`` is taken over the modes returned: scikit-learn's
+    ratio for n = dim (what ``do_pca`` asks for); for n < dim the variance of the modes left out is not in it."""
+
+    def __init__(self, components, singular_values, mean, n_samples, resolved_modes, scores=None, info=None, ctx=None):
+        self.components_ = components
+        self.singular_values_ = np.asarray(singular_values, dtype=np.float64)
+        self.mean_ = mean
+        self.n_samples_ = int(n_samples)
+        self.n_components_ = len(self.singular_values_)
+        self.resolved_modes_ = int(resolved_modes)
+        self.scores = scores
+        self.info = dict(info or {})
+        self._ctx = ctx
+
+    @property
+    def explained_variance_(self):
+        return self.singular_values_ ** 2 / max(self.n_samples_ - 1, 1)
+
+    @property
+    def explained_variance_ratio_(self):
+        ev = self.explained_variance_
+        total = float(ev.sum())
+        return ev / total if total > 0.0 else np.zeros_like(ev)
+
+    def transform(self, Y, download=True):
+        """Scores of new rows: (Y - mean_) components_^T, centred and multiplied (rom_gemm_nt) on the device."""
+        ctx = self._ctx if self._ctx is not None else _ffi.get_context()
+        n = self.n_components_
+        comps = self.components_
+        dim = comps.dim if isinstance(comps, DeviceArray) else np.shape(comps)[1]
+        if isinstance(Y, DeviceArray):   # a private copy: the caller's rows stay as they are
+            Yd = DeviceArray(ctx.alloc(max(Y.rows * dim, 1)).copy_from(Y.buf, Y.rows * dim), Y.rows, dim)
+        else:
+            Yd = _as_device(ctx, np.array(Y, dtype=np.float64), dim)
+        K = Yd.rows
+        if K == 0 or n == 0:
+            return np.zeros((K, n)) if download else DeviceArray(ctx.alloc(1), K, n)
+        Vd = comps if isinstance(comps, DeviceArray) else _as_device(ctx, comps, dim)
+        mean = self.mean_.numpy().ravel() if isinstance(self.mean_, DeviceArray) else np.asarray(self.mean_, dtype=np.float64)
+        if mean.any():
+            ctx.gemm_nn(K, dim, 1, ctx.upload(np.ones(K)), 0, 1, ctx.upload(mean), 0, dim, Yd.buf, 0, dim, alpha=-1.0, beta=1.0)
+        S = ctx.alloc(K * n)
+        ctx.gemm_nt(K, n, dim, Yd.buf, 0, dim, Vd.buf, 0, dim, S, 0, n)
+        return S.download(K * n, shape=(K, n)) if download else DeviceArray(S, K, n)
+
+
+_pca_tall_warned = set()
+
+
+def pca_tall(ctx: _ffi.Context, X, n=None, center=True, scores=True, download=True) -> TallPCA:
+    """Full PCA of a TALL block, M >> dim <= 1024 (``PCA(n).fit`` + ``.transform``, the reference's
+    src/experiments/NonLinearROM.py:34-41): one C call (rom_pca_tall).
+
+    Block one-sided Jacobi on Gram matrices of the ROTATED DATA (Y = Xc V^T, G = Y^T Y on MFMA, Jacobi of G with the
+    relative stopping rule, V <- Q^T V; three passes over the block are typical): singular values and scores are accurate
+    relative to each mode over the whole fp64 range, where a one-pass covariance eigendecomposition (what scikit-learn
+    picks for this shape) stops at sqrt(eps) sigma_1.  All ``n`` rows returned belong to one complete orthonormal basis;
+    nothing is completed with random directions.  ``n`` defaults to ``dim``.  A DeviceArray ``X`` is overwritten when
+    ``center`` (the column means are subtracted in place); a host array is uploaded into a private copy."""
+    if isinstance(X, DeviceArray):
+        Xd = X
+        if center:
+            Xd.factored = None   # (centred in place: the rows stop being the image of their interface vectors)
+    else:
+        arr = np.array(X, dtype=np.float64)
+        assert arr.ndim == 2, "pca_tall: a (M, dim) block"
+        Xd = _as_device(ctx, arr, arr.shape[1])
+    M, dim = Xd.rows, Xd.dim
+    n = dim if n is None else int(n)
+    V = ctx.alloc(max(n * dim, 1))
+    S = ctx.alloc(max(M * n, 1)) if scores else None
+    mean = ctx.alloc(dim)
+    try:
+        sig, info = ctx.pca_tall(Xd.buf, M, dim, n, V, S=S, mean=mean, center=center)
+    except _ffi.RomLibraryError as e:
+        if "NaN / Inf" in str(e) or "rescale the block" in str(e):   # (scikit-learn's PCA raises ValueError on such input)
+            raise ValueError(str(e)) from None
+        raise
+    if n > info["resolved_modes"]:
+        msg = (f"PCA: {n - info['resolved_modes']} of the {n} requested modes lie below the floor of the snapshot block "
+               f"(sigma < 1e-13 sigma_1: fp64 noise of the data): resolved_modes_ = {info['resolved_modes']}; the rows past "
+               "them are orthonormal directions measured at noise level, not determined by the data")
+        if msg not in _pca_tall_warned:
+            _pca_tall_warned.add(msg)
+            warning(msg)
+    if info["stop_reason"] != "converged":
+        warning(f"PCA: the rotations had not converged after {info['passes']} passes over the block (largest off-diagonal "
+                f"{info['worst_ratio']:.3g} x its tolerance)")
+    if download:
+        comps = V.download(n * dim, shape=(n, dim)) if n else np.zeros((0, dim))
+        sc = (S.download(M * n, shape=(M, n)) if n else np.zeros((M, 0))) if scores else None
+        mu = mean.download(dim)
+    else:
+        comps, mu = DeviceArray(V, n, dim), DeviceArray(mean, 1, dim)
+        sc = DeviceArray(S, M, n) if scores else None
+    return TallPCA(comps, sig, mu, M, info["resolved_modes"], scores=sc, info=info, ctx=ctx)
