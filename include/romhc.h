@@ -311,7 +311,8 @@ int rom_pca_tall(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int dim, int n
  * (src/lib/ReducedBasis.py:112-139, :189-200); same contracts, same picks / modes up to rounding.
  * rom_fem_energy_map builds (once per FE space, cached on the fem) the geometry of the snapshots in those coordinates:
  * parts 1 = H^1_0 inner product (norms, greedy), 2 = the block forms u^T A_b v and the load functional (Galerkin greedy),
- * 4 = Euclidean inner product (POD); the other calls build what they need themselves.  k_h10 / k_l2 (may be NULL): ranks. */
+ * 4 = Euclidean inner product (POD); part 1 keeps the way back from its coordinates (rom_pod_h10_factored), 8 is accepted as
+ * 1; the other calls build what they need themselves.  k_h10 / k_l2 (may be NULL): ranks. */
 int rom_fem_energy_map(rom_fem* fem, int parts, int* k_h10, int* k_l2);
 /* H10norm (src/lib/SolutionsManagers.py:56-58) of M snapshots from their compact interface vectors Yc[c_row0 ...] */
 int rom_h10norm_factored(rom_fem* fem, rom_buf* Yc, int64_t c_row0, int M, double* out_host);
@@ -321,6 +322,30 @@ int rom_greedy_factored(rom_fem* fem, rom_buf* Yc, int64_t c_row0, int M, rom_bu
 /* rom_pod on compact interface vectors (M x Kc, not modified): V[v_row0 ...] receives the n modes as ROWS (n x dim) */
 int rom_pod_factored(rom_fem* fem, rom_buf* Yc, int64_t c_row0, int M, int n, int center, rom_buf* V, int64_t v_row0,
                      double* sigma_host, double* info_host);
+/* ---- the H^1_0 inner product in spectral form: POD in the energy norm -----------------------------------------------------
+ * A_1 = S Lambda S with S = S_r (x) S_c the orthogonal 2-D sine transform of the interior grid and Lambda[j,k] = lam_r[j] +
+ * lam_c[k] (the tables of rom_riesz_h10, built once per FE space).  The reference's greedy is parameterised by norm
+ * (get_function_norm("l2" | "h10"), src/lib/ReducedBasis.py); its PCA (src/lib/ReducedBasis.py:189-200) is "optimal with
+ * respect to L2" only (InverseProblemPipeline.ipynb, "Optimal in which sense?"): these calls fill the {POD} x {H^1_0} cell. */
+/* OUT_i = Lambda^(post/2) o ( S_r (Lambda^(pre/2) o X_i) S_c ), i < K; pre, post in {-2,-1,0,1,2}; X not modified, OUT != X.
+ * (pre, post) = (0,1): H^1_0 -> Euclidean coordinates; (-1,0): the way back; (0,-2) then (0,0): A_1^{-1} of dense rows.
+ * X_i = row x_row0 + i as an nr x nc array.  Two MFMA products per row (the one over the grid rows a strided-batched kernel
+ * with the scalings fused); no floating-point atomics: the same bits on every call with the same arguments and workspace limit.
+ * Workspace: K x dim doubles, fewer rows at a time under rom_set_workspace_limit (the product over the columns may then take
+ * another route of rom_gemm_nn: equal to rounding).  One host synchronisation at the end. */
+int rom_sine_transform(rom_fem* fem, rom_buf* X, int64_t x_row0, int K, int pre, int post, rom_buf* OUT, int64_t out_row0);
+/* rom_pod_ex in the H^1_0 inner product; X is NOT modified; rows of V are A_1-orthonormal, svd_flip sign on the returned rows.
+ * The n-dimensional space that minimises sum_m ||x_m - P_n x_m||^2_{H^1_0}: the Euclidean POD (rom_pod_ex: same floor, same
+ * completion, same NaN / Inf error) of the block in energy coordinates W_m = sqrt(Lambda) o (S_r X_m S_c) -- an M x dim
+ * temporary, centred there when center != 0 -- with the modes taken back by v_i = S_r (Lambda^-1/2 o q_i) S_c.  sigma_host (n):
+ * singular values of the block in the H^1_0 geometry (sum_{i>n} sigma_i^2 = the squared H^1_0 projection error of the whole
+ * block); completed modes have sigma = 0.  info_host (8 doubles or NULL) as rom_pod, executed flops including the transforms. */
+int rom_pod_h10(rom_fem* fem, rom_buf* X, int64_t x_row0, int M, int n, int center, double rel_floor, rom_buf* V, int64_t v_row0,
+                double* sigma_host, double* info_host);
+/* the same on compact interface vectors (M x Kc, not modified; rom_pod_factored with the H^1_0 coordinates of
+ * rom_fem_energy_map, part 1, in place of the Euclidean ones): V[v_row0 ...] receives the n modes as ROWS (n x dim) */
+int rom_pod_h10_factored(rom_fem* fem, rom_buf* Yc, int64_t c_row0, int M, int n, int center, rom_buf* V, int64_t v_row0,
+                         double* sigma_host, double* info_host);
 /* n nearly orthonormal rows of V -> orthonormal rows, each as close as possible to what it was: V <- (V V^T)^(-1/2) V */
 int rom_symmetric_orthonormalize(rom_ctx* ctx, rom_buf* V, int64_t v_row0, int n, int64_t dim);
 /* rows V[v_row0+found .. +found+rest) <- deterministic pseudo-random directions, orthonormal and orthogonal to the

@@ -104,6 +104,9 @@ PROTOTYPES = {
     "rom_pod_factored": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp]),
     "rom_pod_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, _vp, C.c_int64, _vp, _vp]),
     "rom_pca_tall": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp]),
+    "rom_sine_transform": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int64]),
+    "rom_pod_h10": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _vp, C.c_int64, _vp, _vp]),
+    "rom_pod_h10_factored": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp, _vp]),
     "rom_symmetric_orthonormalize": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64]),
     "rom_complete_orthonormal": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "rom_small_eig_host": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_double, C.c_int, _vp, _vp]),
@@ -286,11 +289,7 @@ class Context:
         sigma, info = np.zeros(max(n, 1)), np.zeros(8)
         check(self.lib.rom_pod_ex(self.h, X.h, x_row0, M, dim, n, 1 if center else 0, float(rel_floor), V.h, v_row0,
                                   sigma.ctypes.data, info.ctypes.data))
-        keys = ("resolved_modes", "completed_modes", "gram_passes", "sketch_passes")
-        d = {k: int(info[i]) for i, k in enumerate(keys)}
-        d.update(executed_flops=float(info[4]), useful_flops=float(info[5]), subspace_iterations=int(info[6]),
-                 stop_reason=("filled", "floor", "budget")[int(info[7])])
-        return sigma[:n], d
+        return sigma[:n], _pod_info(info)
 
     def pca_tall(self, X: "Buffer", M, dim, n, V: "Buffer", S: "Buffer | None" = None, mean: "Buffer | None" = None, center=True,
                  x_row0=0, v_row0=0, s_row0=0):
@@ -346,6 +345,15 @@ class Context:
         v = _host(np.atleast_1d(vals)).copy()
         check(self.lib.rom_comm_allreduce_host(self.h, v.ctypes.data, v.size, 1 if op == "max" else 0))
         return v
+
+
+def _pod_info(info) -> dict:
+    """The info dict of the POD calls (rom_pod's eight doubles)."""
+    keys = ("resolved_modes", "completed_modes", "gram_passes", "sketch_passes")
+    d = {k: int(info[i]) for i, k in enumerate(keys)}
+    d.update(executed_flops=float(info[4]), useful_flops=float(info[5]), subspace_iterations=int(info[6]),
+             stop_reason=("filled", "floor", "budget")[int(info[7])])
+    return d
 
 
 D2H_BYTES = [0]  # bytes copied from device buffers to the host through Buffer.download (tests assert on it)
@@ -553,7 +561,7 @@ class Fem:
     # -- basis stage on compact interface vectors (factored snapshot blocks: rom_factored.hip) --------------
     def energy_map(self, parts=7):
         """rom_fem_energy_map: build / cache the geometry of the snapshots in interface-vector coordinates (1: H^1_0,
-        2: Galerkin forms, 4: Euclidean).  Returns the ranks (k_h10, k_l2)."""
+        2: Galerkin forms, 4: Euclidean; 1 keeps the way back from its coordinates).  Returns the ranks (k_h10, k_l2)."""
         k1, k2 = C.c_int(0), C.c_int(0)
         check(self.ctx.lib.rom_fem_energy_map(self.h, int(parts), C.byref(k1), C.byref(k2)))
         return k1.value, k2.value
@@ -580,6 +588,27 @@ class Fem:
         d = {k: int(info[i]) for i, k in enumerate(keys)}
         d.update(executed_flops=float(info[4]), subspace_iterations=int(info[6]), stop_reason=("filled", "floor", "budget")[int(info[7])])
         return sigma[:n], d
+
+    # -- the H^1_0 inner product in spectral form (rom_spectral.hip) ------------------------------------------
+    def sine_transform(self, X: Buffer, K: int, OUT: Buffer, pre=0, post=0, x_row0=0, out_row0=0):
+        """rom_sine_transform: OUT[k] = Lambda^(post/2) o (S_r (Lambda^(pre/2) o X[k]) S_c) for K rows; X is not modified.
+        (pre, post) = (0, 1): H^1_0 -> Euclidean coordinates, (-1, 0): the way back."""
+        check(self.ctx.lib.rom_sine_transform(self.h, X.h, x_row0, K, int(pre), int(post), OUT.h, out_row0))
+
+    def pod_h10(self, X: Buffer, M: int, n: int, V: Buffer, center=True, x_row0=0, v_row0=0, rel_floor=0.0):
+        """rom_pod_h10: POD in the H^1_0 inner product; X is NOT modified.  Returns (sigma (n,), info dict as Context.pod)."""
+        sigma, info = np.zeros(max(n, 1)), np.zeros(8)
+        check(self.ctx.lib.rom_pod_h10(self.h, X.h, x_row0, M, n, 1 if center else 0, float(rel_floor), V.h, v_row0,
+                                       sigma.ctypes.data, info.ctypes.data))
+        return sigma[:n], _pod_info(info)
+
+    def pod_h10_factored(self, Yc: Buffer, M: int, n: int, V: Buffer, center=True, c_row0=0, v_row0=0):
+        """rom_pod_h10_factored: the same from compact interface vectors, modes as rows into V.  Returns (sigma (n,), info
+        dict as Context.pod)."""
+        sigma, info = np.zeros(max(n, 1)), np.zeros(8)
+        check(self.ctx.lib.rom_pod_h10_factored(self.h, Yc.h, c_row0, M, n, 1 if center else 0, V.h, v_row0,
+                                                sigma.ctypes.data, info.ctypes.data))
+        return sigma[:n], _pod_info(info)
 
     def evaluate_points(self, U: Buffer, K: int, ix, iy, tx, ty, row0=0) -> np.ndarray:
         ix = np.ascontiguousarray(ix, dtype=np.int32)

@@ -36,12 +36,17 @@ struct rom_factored_map {
   int* piv2 = nullptr;      // (k2): pivot order
   double* d2 = nullptr;     // (Kc): equilibration
   double* Li2 = nullptr;    // (k2, k2): inverse of the pivot rows' triangle L1 (L1[r][c] = LT2[c][piv2[r]]): x L1 = v is x = v Li2
+  // the way back from the H^1_0 coordinates (rom_pod_h10_factored): the same pieces of the factor behind ET1, kept with it
+  int* piv1 = nullptr;      // (k1)
+  double* d1 = nullptr;     // (Kc)
+  double* Li1 = nullptr;    // (k1, k1)
 };
 
 void rom_factored_map_free(void* p) {
   auto* m = static_cast<rom_factored_map*>(p);
   if (!m) return;
-  for (void* q : {(void*)m->ET1, (void*)m->Sb, (void*)m->bt, (void*)m->ET2, (void*)m->LT2, (void*)m->piv2, (void*)m->d2, (void*)m->Li2})
+  for (void* q : {(void*)m->ET1, (void*)m->Sb, (void*)m->bt, (void*)m->ET2, (void*)m->LT2, (void*)m->piv2, (void*)m->d2, (void*)m->Li2,
+                  (void*)m->piv1, (void*)m->d1, (void*)m->Li1})
     if (q) hipFree(q);
   delete m;
 }
@@ -446,6 +451,20 @@ struct DevOwner {
   void release() { ptrs.clear(); }
 };
 
+// Li (rank x rank) = inverse of the pivot rows' triangle L1 of a pivoted factor LT (L1[r][c] = LT[c][piv[r]]); waits for the stream
+// (L1 is a temporary)
+int tri_inverse_of_pivot_rows(rom_ctx* ctx, int rank, int Kc, const double* LT, const int* piv, double* Li) {
+  Tmp L1;
+  ROM_TRY(L1.get(ctx, size_t(rank) * rank));
+  kf_gather_triangle<<<unsigned((size_t(rank) * rank + 255) / 256), 256, 0, ctx->stream>>>(rank, Kc, LT, piv, L1);
+  const int cpw = rank <= 1920 ? 4 : rank <= 3840 ? 2 : 1;   // columns (waves) per workgroup: their LDS stays below 64 KB
+  ROM_CHECK(size_t(cpw) * rank * sizeof(double) <= 62 * 1024, "factored map: rank %d beyond what the inverse kernel's LDS columns hold", rank);
+  kf_tri_inverse<<<unsigned((rank + cpw - 1) / cpw), 64 * cpw, size_t(cpw) * rank * sizeof(double), ctx->stream>>>(rank, L1, Li);
+  ROM_HIP(hipGetLastError());
+  ROM_HIP(hipStreamSynchronize(ctx->stream));
+  return ROM_OK;
+}
+
 int ensure_map(rom_fem* f, int parts) {
   int lin = 0;
   ROM_TRY(rom_fem_expansion_is_linear(f, &lin));
@@ -458,6 +477,7 @@ int ensure_map(rom_fem* f, int parts) {
   const int Kc = f->nGp - (f->xb0 - f->nGa);
   mp->Kc = Kc;
   const int kblk = f->nrb * f->ncb, N = f->N;
+  if (parts & 8) parts |= 1;   // (the way back from the H^1_0 coordinates is kept with part 1)
   const bool need1 = (parts & 1) && !mp->ET1, need2 = (parts & 2) && !mp->have_galerkin, need4 = (parts & 4) && !mp->ET2;
   if (!need1 && !need2 && !need4) return ROM_OK;
   const int64_t dim = f->dim;
@@ -529,13 +549,23 @@ int ensure_map(rom_fem* f, int parts) {
     ROM_TRY(pivoted_factor(ctx, Kc, Sm, LT, reinterpret_cast<int*>(pv.p()), dd, &rank));
     ROM_CHECK(rank >= 1, "factored map: the H^1_0 form of the expansion has rank 0");
     DevOwner own;
-    double* ET1 = nullptr;
+    double *ET1 = nullptr, *d1 = nullptr, *Li1 = nullptr;
+    int* piv1 = nullptr;
     ROM_TRY(own.alloc(&ET1, size_t(rank) * Kc));
+    ROM_TRY(own.alloc(&piv1, size_t(rank)));
+    ROM_TRY(own.alloc(&d1, size_t(Kc)));
+    ROM_TRY(own.alloc(&Li1, size_t(rank) * rank));
     kf_scale_cols<<<unsigned((size_t(rank) * Kc + 255) / 256), 256, 0, ctx->stream>>>(rank, Kc, LT, dd, ET1);
     ROM_HIP(hipGetLastError());
-    ROM_HIP(hipStreamSynchronize(ctx->stream));
+    // the way back from these coordinates (rom_pod_h10_factored), from the same factor: pivots, equilibration, L1^-1
+    ROM_HIP(hipMemcpyAsync(piv1, pv.p(), size_t(rank) * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+    ROM_HIP(hipMemcpyAsync(d1, dd.p(), size_t(Kc) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    ROM_TRY(tri_inverse_of_pivot_rows(ctx, rank, Kc, LT, piv1, Li1));
     mp->ET1 = ET1;
     mp->k1 = rank;
+    mp->piv1 = piv1;
+    mp->d1 = d1;
+    mp->Li1 = Li1;
     own.release();
   }
   if (need4) {
@@ -557,17 +587,7 @@ int ensure_map(rom_fem* f, int parts) {
     ROM_HIP(hipMemcpyAsync(piv2, pv.p(), size_t(rank) * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
     ROM_HIP(hipMemcpyAsync(d2, dd.p(), size_t(Kc) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     // the way back from the factor's coordinates needs L1^-1 (L1 = the pivot rows' triangle): once here, a product per call
-    {
-      Tmp L1;
-      ROM_TRY(L1.get(ctx, size_t(rank) * rank));
-      kf_gather_triangle<<<unsigned((size_t(rank) * rank + 255) / 256), 256, 0, ctx->stream>>>(rank, Kc, LT2, piv2, L1);
-      const int cpw = rank <= 1920 ? 4 : rank <= 3840 ? 2 : 1;   // columns (waves) per workgroup: their LDS stays below 64 KB
-      ROM_CHECK(size_t(cpw) * rank * sizeof(double) <= 62 * 1024, "factored map: rank %d beyond what the inverse kernel's LDS columns hold", rank);
-      kf_tri_inverse<<<unsigned((rank + cpw - 1) / cpw), 64 * cpw, size_t(cpw) * rank * sizeof(double), ctx->stream>>>(rank, L1, Li2);
-      ROM_HIP(hipGetLastError());
-      ROM_HIP(hipStreamSynchronize(ctx->stream));   // (L1 is a temporary)
-    }
-    ROM_HIP(hipStreamSynchronize(ctx->stream));
+    ROM_TRY(tri_inverse_of_pivot_rows(ctx, rank, Kc, LT2, piv2, Li2));
     mp->ET2 = ET2;
     mp->LT2 = LT2;
     mp->piv2 = piv2;
@@ -582,7 +602,7 @@ int ensure_map(rom_fem* f, int parts) {
 }  // namespace
 
 // parts: 1 = H^1_0 geometry (norms, greedy), 2 = the block forms u^T A_b v and the load functional (Galerkin greedy),
-// 4 = Euclidean geometry (POD).  Builds what is missing, once per FE space; ranks of the two geometries on return.
+// 4 = Euclidean geometry (POD); 8 is accepted as 1 (the way back from the H^1_0 coordinates is kept with it).  Builds what is missing, once per FE space; ranks of the two geometries on return.
 extern "C" int rom_fem_energy_map(rom_fem* f, int parts, int* k_h10, int* k_l2) {
   ROM_CHECK(f, "rom_fem_energy_map: null fem");
   ROM_TRY(ensure_map(f, parts));
@@ -704,22 +724,31 @@ extern "C" int rom_greedy_factored(rom_fem* f, rom_buf* Yc, int64_t c_row0, int 
 }
 
 // PCA(n_components = n).fit (src/lib/ReducedBasis.py:196) of a snapshot block held as compact interface vectors
-// Yc[c_row0 ...] (M x Kc, not modified): the rows of Z = Yc E2 (M x k2, k2 <= Kc) have the Euclidean geometry of the snapshot
-// rows, so the POD of the block IS the POD of Z (rom_pod, on a matrix dim / k2 times narrower); a mode is taken back to
-// coordinates by one triangular substitution and expanded like any interface vector.  V[v_row0 ...]: (n, dim) rows;
-// sigma_host / info_host as rom_pod (info: of the inner call; completed modes include those beyond the rank of the map).
-extern "C" int rom_pod_factored(rom_fem* f, rom_buf* Yc, int64_t c_row0, int M, int n, int center, rom_buf* V, int64_t v_row0,
-                                double* sigma_host, double* info_host) {
-  ROM_CHECK(f && Yc && V && (sigma_host || n == 0), "rom_pod_factored: null argument");
-  ROM_CHECK(M >= 1 && n >= 0 && c_row0 >= 0 && v_row0 >= 0, "rom_pod_factored: bad sizes");
+// Yc[c_row0 ...] (M x Kc, not modified), in the Euclidean (rom_pod_factored) or the H^1_0 (rom_pod_h10_factored) inner product.
+// The rows of Z = Yc E (M x k, k <= Kc; E = E2 / E1) have that geometry of the snapshot rows, so the POD of the block IS the POD
+// of Z (rom_pod, on a matrix dim / k times narrower); a mode is taken back to coordinates by one triangular substitution and
+// expanded like any interface vector.  V[v_row0 ...]: (n, dim) rows; sigma_host / info_host as rom_pod (info: of the inner
+// call; completed modes include those beyond the rank of the map).
+// The expanded rows are orthonormal to the accuracy of the map's factor (~1e-9 relative to the leading directions): one
+// symmetric orthonormalisation (eigen-decomposition of the n x n Gram matrix: exact for any defect) cleans that up -- on the rows
+// themselves in the Euclidean case, in energy coordinates (rom_launch_sine_transform there and back, so that the rows come out
+// A_1-orthonormal) in the H^1_0 case; modes beyond the rank of the map are completed in the same coordinates.
+namespace {
+
+int pod_factored(rom_fem* f, bool h10, const char* who, rom_buf* Yc, int64_t c_row0, int M, int n, int center, rom_buf* V,
+                 int64_t v_row0, double* sigma_host, double* info_host) {
+  ROM_CHECK(f && Yc && V && (sigma_host || n == 0), "%s: null argument", who);
+  ROM_CHECK(M >= 1 && n >= 0 && c_row0 >= 0 && v_row0 >= 0, "%s: bad sizes", who);
   const int64_t dim = f->dim;
-  ROM_CHECK(n <= std::min<int64_t>(M, dim), "rom_pod_factored: %d modes requested from a %d x %lld block", n, M, (long long)dim);
-  ROM_CHECK(size_t(v_row0 + n) * dim <= V->n, "rom_pod_factored: mode buffer too small");
-  ROM_TRY(ensure_map(f, 4));
+  ROM_CHECK(n <= std::min<int64_t>(M, dim), "%s: %d modes requested from a %d x %lld block", who, n, M, (long long)dim);
+  ROM_CHECK(size_t(v_row0 + n) * dim <= V->n, "%s: mode buffer too small", who);
+  ROM_TRY(ensure_map(f, h10 ? 1 : 4));
   auto* mp = static_cast<rom_factored_map*>(f->fmap);
   rom_ctx* ctx = f->ctx;
-  const int Kc = mp->Kc, k2 = mp->k2, kblk = f->nrb * f->ncb;
-  ROM_CHECK(size_t(c_row0 + M) * Kc <= Yc->n, "rom_pod_factored: buffer too small");
+  const int Kc = mp->Kc, k = h10 ? mp->k1 : mp->k2, kblk = f->nrb * f->ncb;
+  const double *ET = h10 ? mp->ET1 : mp->ET2, *Li = h10 ? mp->Li1 : mp->Li2, *dq = h10 ? mp->d1 : mp->d2;
+  const int* piv = h10 ? mp->piv1 : mp->piv2;
+  ROM_CHECK(size_t(c_row0 + M) * Kc <= Yc->n, "%s: buffer too small", who);
   for (int i = 0; i < n; ++i) sigma_host[i] = 0.0;
   if (n == 0) return ROM_OK;
   Tmp Ycc, mean, Z, Vz, Wc, Yfull, ones;
@@ -729,21 +758,21 @@ extern "C" int rom_pod_factored(rom_fem* f, rom_buf* Yc, int64_t c_row0, int M, 
     ROM_TRY(mean.get(ctx, Kc));
     ROM_TRY(rom_launch_center_rows(ctx, Ycc, M, Kc, mean));
   }
-  ROM_TRY(Z.get(ctx, size_t(M) * k2));
-  ROM_TRY(rom_launch_gemm_nt(ctx, M, k2, Kc, 1.0, Ycc, Kc, mp->ET2, Kc, 0.0, Z, k2, "gemm_nt"));
-  const int nz = std::min(n, std::min(k2, M));
-  ROM_TRY(Vz.get(ctx, size_t(nz) * k2));
+  ROM_TRY(Z.get(ctx, size_t(M) * k));
+  ROM_TRY(rom_launch_gemm_nt(ctx, M, k, Kc, 1.0, Ycc, Kc, ET, Kc, 0.0, Z, k, "gemm_nt"));
+  const int nz = std::min(n, std::min(k, M));
+  ROM_TRY(Vz.get(ctx, size_t(nz) * k));
   double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  ROM_TRY(rom_pod(ctx, Z.b, 0, M, k2, nz, 0, Vz.b, 0, sigma_host, info));
+  ROM_TRY(rom_pod(ctx, Z.b, 0, M, k, nz, 0, Vz.b, 0, sigma_host, info));
   // modes as coordinate vectors, then as rows
   ROM_TRY(Wc.get(ctx, size_t(nz) * Kc));
   ROM_HIP(hipMemsetAsync(Wc.p(), 0, size_t(nz) * Kc * sizeof(double), ctx->stream));
   {
     // x L1 = v  =>  x = v L1^-1 (the inverse is part of the map); w[piv[r]] = x[r] / d[piv[r]]
     Tmp Xs;
-    ROM_TRY(Xs.get(ctx, size_t(nz) * k2));
-    ROM_TRY(rom_launch_gemm_nn(ctx, nz, k2, k2, 1.0, Vz, k2, mp->Li2, k2, 0.0, Xs, k2));
-    kf_scatter_pivots<<<dim3(unsigned((k2 + 255) / 256), unsigned(nz)), 256, 0, ctx->stream>>>(k2, Kc, mp->piv2, mp->d2, Xs, Wc);
+    ROM_TRY(Xs.get(ctx, size_t(nz) * k));
+    ROM_TRY(rom_launch_gemm_nn(ctx, nz, k, k, 1.0, Vz, k, Li, k, 0.0, Xs, k));
+    kf_scatter_pivots<<<dim3(unsigned((k + 255) / 256), unsigned(nz)), 256, 0, ctx->stream>>>(k, Kc, piv, dq, Xs, Wc);
     ROM_HIP(hipGetLastError());
   }
   ROM_TRY(Yfull.get(ctx, size_t(nz) * f->nGp));
@@ -752,23 +781,38 @@ extern "C" int rom_pod_factored(rom_fem* f, rom_buf* Yc, int64_t c_row0, int M, 
   ROM_HIP(hipGetLastError());
   ROM_TRY(rom_fem_unpack_reduced_async(f, Wc.b, 0, nz, Yfull.b, 0));
   ROM_TRY(rom_expand_batch_async(f, ones.b, nz, Yfull.b, 0, V, v_row0));
-  // the map is orthonormal to the accuracy of its factor (~1e-9 relative to the leading directions): clean up (symmetric
-  // orthonormalisation through the eigen-decomposition of the n x n Gram matrix: exact for any defect, one round)
-  {
-    Tmp Ys;
-    ROM_TRY(Ys.get(ctx, size_t(nz) * dim));
-    ROM_TRY(romb_gram_transform(ctx, V->p + v_row0 * dim, Ys, nz, dim, SE_LOWDIN, 1e-30, 1));
+  // clean-up of the factor's defect and completion, in the coordinates in which the inner product is Euclidean
+  double* Vr = V->p + v_row0 * dim;
+  Tmp Ys, Q;
+  ROM_TRY(Ys.get(ctx, size_t(nz) * dim));
+  if (h10) {
+    ROM_TRY(Q.get(ctx, size_t(n) * dim));
+    ROM_TRY(rom_launch_sine_transform(f, Vr, nz, 0, 1, Q));
   }
+  ROM_TRY(romb_gram_transform(ctx, h10 ? Q.p() : Vr, Ys, nz, dim, SE_LOWDIN, 1e-30, 1));
   if (nz < n) {  // more modes requested than the snapshot manifold has dimensions: completed like rom_pod completes
-    ROM_TRY(rom_complete_orthonormal(ctx, V, v_row0, nz, n - nz, dim));
+    ROM_TRY(rom_complete_orthonormal(ctx, h10 ? Q.b : V, h10 ? 0 : v_row0, nz, n - nz, dim));
     info[1] += n - nz;
     if (info[7] == 0.0) info[7] = 1.0;   // (not "filled": the completed modes lie beyond the rank of the snapshot manifold)
   }
-  ROM_TRY(rom_launch_rows_sign_flip(ctx, V->p + v_row0 * dim, n, dim));  // svd_flip(u_based_decision=False)
+  if (h10) ROM_TRY(rom_launch_sine_transform(f, Q, n, -1, 0, Vr));
+  ROM_TRY(rom_launch_rows_sign_flip(ctx, Vr, n, dim));  // svd_flip(u_based_decision=False) on the returned rows
   ROM_TRY(rom_solve_status(ctx));   // (synchronises; the status word of the expansion)
   if (info_host) {
-    info[4] += 2.0 * M * double(Kc) * k2 + 2.0 * nz * double(Kc) * double(dim);
+    info[4] += 2.0 * M * double(Kc) * k + 2.0 * nz * double(Kc) * double(dim) + (h10 ? rom_sine_transform_flops(f, nz + n) : 0.0);
     memcpy(info_host, info, sizeof(info));
   }
   return ROM_OK;
+}
+
+}  // namespace
+
+extern "C" int rom_pod_factored(rom_fem* f, rom_buf* Yc, int64_t c_row0, int M, int n, int center, rom_buf* V, int64_t v_row0,
+                                double* sigma_host, double* info_host) {
+  return pod_factored(f, false, "rom_pod_factored", Yc, c_row0, M, n, center, V, v_row0, sigma_host, info_host);
+}
+
+extern "C" int rom_pod_h10_factored(rom_fem* f, rom_buf* Yc, int64_t c_row0, int M, int n, int center, rom_buf* V, int64_t v_row0,
+                                    double* sigma_host, double* info_host) {
+  return pod_factored(f, true, "rom_pod_h10_factored", Yc, c_row0, M, n, center, V, v_row0, sigma_host, info_host);
 }

@@ -47,6 +47,10 @@ __global__ void k_eval_points(int nr, int nc, long long dim, const double* __res
                               double* __restrict__ out);
 // the sine tables of rom_riesz_h10, built once per FE space into f->d_riesz: S_r (nr x nr), S_c (nc x nc), lam_r, lam_c
 int rom_riesz_tables(rom_fem* f);
+// the 2-D sine transform of K dense rows (rom_spectral.hip): OUT[k] = Lambda^(post/2) o (S_r (Lambda^(pre/2) o X[k]) S_c) on raw
+// device rows, OUT != X; its flop count (both factors)
+int rom_launch_sine_transform(rom_fem* f, const double* X, int K, int pre, int post, double* OUT);
+double rom_sine_transform_flops(rom_fem* f, int K);
 
 // P1 weights of a point on the interior dofs (rom_riesz.hip, rom_sensors.hip): the locating convention of k_eval_points (rom_ops.hip), vertex (y, x) of
 // the grid with its Dirichlet ring -> dof (y-1, x-1); weights on boundary vertices drop out (y = -1: none)

@@ -38,7 +38,8 @@ class ExpansionMap:
 
     def build(self, parts=7):
         """rom_fem_energy_map: the geometry of the snapshots in compact coordinates (1: H^1_0, 2: Galerkin forms,
-        4: Euclidean), built once per FE space and cached by the library.  Returns the ranks (k_h10, k_l2)."""
+        4: Euclidean; 1 keeps the way back from its coordinates), built once per FE space and cached by the library.
+        Returns the ranks (k_h10, k_l2)."""
         return self.fem.energy_map(parts)
 
     @property
@@ -130,18 +131,22 @@ class FactoredSnapshots:
         return G
 
 
-def pod_modes_factored(fs: FactoredSnapshots, n: int, center=True):
+def pod_modes_factored(fs: FactoredSnapshots, n: int, center=True, inner="l2"):
     """Leading ``n`` POD modes / singular values of the snapshot block ``fs`` without ever forming it: ONE C call
     (``rom_pod_factored``).  With U = Y B^T and B^T B = E E^T the rows of Z = Yc E (M x k', k' <= a few hundred / thousand)
     have the Euclidean geometry of the snapshot rows, so the POD of the block IS the POD of Z -- ``rom_pod`` on a matrix
     dim / k' times narrower -- and a mode is expanded like any interface vector.  Returns (modes (n, dim) NumPy,
     singular values); rows follow scikit-learn's ``svd_flip(u_based_decision=False)`` sign convention (the PCA call at
-    src/lib/ReducedBasis.py:196)."""
+    src/lib/ReducedBasis.py:196).  ``inner="h10"``: the POD in the H^1_0 inner product (``rom_pod_h10_factored``: the same
+    with the H^1_0 geometry of the rows; the modes are A_1-orthonormal)."""
+    if inner not in ("l2", "h10"):
+        raise Exception(f"Not implemented POD for the inner product {inner}, should be one of [l2, h10]")
     em, M = fs.map, fs.M
     ctx, dim = em.ctx, em.dim
     n = min(n, M, dim)
     V = ctx.alloc(max(n * dim, 1))
-    sig, info = em.fem.pod_factored(fs.Yc, M, n, V, center=center)
+    call = em.fem.pod_h10_factored if inner == "h10" else em.fem.pod_factored
+    sig, info = call(fs.Yc, M, n, V, center=center)
     pod_modes_factored.last_info = info
     if info["completed_modes"]:
         from .lib.ReducedBasis import warn_completed_modes

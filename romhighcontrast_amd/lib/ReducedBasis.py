@@ -529,17 +529,60 @@ def pod_modes(ctx: _ffi.Context, X: DeviceArray, n: int, center=True, rel_floor=
     return (V.download(n * dim, shape=(n, dim)) if download else DeviceArray(V, n, dim)), sig
 
 
-class ReducedBasisPCA(BaseReducedBasis):
-    """(:183-200) mean-centred PCA of the training snapshots (INFINIT_A ones peeled off first)."""
+def pod_modes_h10(sm: SolutionsManager, X: DeviceArray, n: int, center=True, rel_floor=0.0, download=True):
+    """Leading ``n`` modes / singular values of the (M, dim) snapshot block in the H^1_0 inner product: one C call
+    (rom_pod_h10).  The n-dimensional space that minimises sum_m ||u_m - P_n u_m||^2_{H^1_0} -- the lower envelope of the
+    mean-square curves of ``error_curves`` -- where ``pod_modes`` minimises the Euclidean sum (the reference's notebook:
+    "PCA (optimal with respect to L2)").  The block goes to the coordinates in which the H^1_0 inner product is Euclidean
+    (the 2-D sine transform that diagonalises A_1, on MFMA), ``rom_pod_ex`` runs there with its full range, and the modes
+    come back A_1-orthonormal; singular values are those of the block in the H^1_0 geometry.  The contract of ``pod_modes``
+    (completion below the floor with its warning, sign rule on the returned rows, ``pod_modes_h10.last_info``), except that
+    ``X`` -- and ``X.factored`` -- are left untouched: the centring happens in the transformed copy."""
+    M, dim = X.rows, X.dim
+    assert dim == sm.vspace_dim, "pod_modes_h10: rows of the manager's FE space"
+    n = min(n, M, dim)
+    ctx = sm._ctx
+    V = ctx.alloc(max(n * dim, 1))
+    try:
+        sig, info = sm._fem.pod_h10(X.buf, M, n, V, center=center, rel_floor=rel_floor)
+    except _ffi.RomLibraryError as e:
+        if "NaN / Inf" in str(e) or "rescale the block" in str(e):   # (as pod_modes)
+            raise ValueError(str(e)) from None
+        raise
+    pod_modes_h10.last_info = info
+    pod_modes_h10.resolved = info["resolved_modes"]
+    if info["completed_modes"]:
+        warn_completed_modes(info, n, rel_floor)
+    elif info["stop_reason"] == "budget":
+        warning("POD: the eigenpairs of the Gram matrix did not converge (a spectrum so flat that the subspace iteration "
+                f"stalls, with more than 1024 snapshots: M = {M}); the trailing modes of the request are approximate")
+    if n == 0:
+        return (np.zeros((0, dim)) if download else DeviceArray(V, 0, dim)), sig
+    return (V.download(n * dim, shape=(n, dim)) if download else DeviceArray(V, n, dim)), sig
 
-    def __init__(self, add_inf_solutions=True):
+
+PCA_INNER_L2 = "l2"
+PCA_INNER_H10 = "h10"
+
+
+class ReducedBasisPCA(BaseReducedBasis):
+    """(:183-200) mean-centred PCA of the training snapshots (INFINIT_A ones peeled off first).  ``inner_product="h10"``:
+    the POD in the H^1_0 inner product (``pod_modes_h10`` / ``pod_modes_factored(inner="h10")``), the basis that is optimal
+    in the norm the errors are reported in; the default is the reference's Euclidean PCA."""
+
+    def __init__(self, add_inf_solutions=True, inner_product=PCA_INNER_L2):
         self.add_inf_solutions = add_inf_solutions
-        self.name = "PCA" + (r" $\infty$" if add_inf_solutions else "")
+        self.inner_product = inner_product
+        self.name = ("PCA $H^1_0$" if inner_product == PCA_INNER_H10 else "PCA") + (r" $\infty$" if add_inf_solutions else "")
         super().__init__()
 
     def build(self, n: int, sm: SolutionsManager, solutions2train, a2train: List[np.ndarray] = (()),
               solutions2train_h1norm=1, add_inf_solutions=True, seed=42, **kwargs):
         from ..factored import FactoredSnapshots, pod_modes_factored
+        if self.inner_product not in (PCA_INNER_L2, PCA_INNER_H10):
+            raise Exception(f"Not implemented PCA for the inner product {self.inner_product}, "
+                            f"should be one of [{PCA_INNER_L2}, {PCA_INNER_H10}]")
+        h10 = self.inner_product == PCA_INNER_H10
         if isinstance(solutions2train, FactoredSnapshots):
             # the training block in factored form (e.g. gathered from several GPUs): the same peel-off of the
             # INFINIT_A snapshots by index, POD on the interface vectors, only the basis rows are materialised
@@ -547,7 +590,7 @@ class ReducedBasisPCA(BaseReducedBasis):
             has_inf = (a2train == INFINIT_A).reshape(len(a2train), -1).any(axis=1)
             lead_idx = np.flatnonzero(has_inf) if self.add_inf_solutions else np.zeros(0, dtype=np.int64)
             pool = fs.take(np.flatnonzero(~has_inf))
-            comps, sigma = pod_modes_factored(pool, n)
+            comps, sigma = pod_modes_factored(pool, n, inner="h10") if h10 else pod_modes_factored(pool, n)
             self.singular_values_ = sigma
             self.resolved_modes_ = pod_modes_factored.last_info.get("resolved_modes", n)
             lead = fs.take(lead_idx).rows().numpy() if lead_idx.size else np.empty((0, sm.vspace_dim))
@@ -567,9 +610,12 @@ class ReducedBasisPCA(BaseReducedBasis):
             pool_idx = np.flatnonzero(~has_inf)
             lead_idx = np.flatnonzero(has_inf) if self.add_inf_solutions else np.zeros(0, dtype=np.int64)
             X = ctx.alloc(max(len(pool_idx) * dim, 1)).gather_rows_from(Ud.buf, pool_idx, dim)
-            comps, sigma = pod_modes(ctx, DeviceArray(X, len(pool_idx), dim), n, center=True)
+            if h10:
+                comps, sigma = pod_modes_h10(sm, DeviceArray(X, len(pool_idx), dim), n, center=True)
+            else:
+                comps, sigma = pod_modes(ctx, DeviceArray(X, len(pool_idx), dim), n, center=True)
             self.singular_values_ = sigma
-            self.resolved_modes_ = pod_modes.resolved
+            self.resolved_modes_ = pod_modes_h10.resolved if h10 else pod_modes.resolved
             if lead_idx.size:
                 lead = DeviceArray(ctx.alloc(lead_idx.size * dim).gather_rows_from(Ud.buf, lead_idx, dim), lead_idx.size, dim).numpy()
             else:
@@ -580,9 +626,9 @@ class ReducedBasisPCA(BaseReducedBasis):
         basis, a, solutions2train, a2train = get_starting_basis(solutions2train, a2train, self.add_inf_solutions)
         ctx = sm._ctx
         X = _as_device(ctx, np.array(solutions2train, dtype=np.float64), sm.vspace_dim)  # private copy
-        comps, sigma = pod_modes(ctx, X, n, center=True)
+        comps, sigma = pod_modes_h10(sm, X, n, center=True) if h10 else pod_modes(ctx, X, n, center=True)
         self.singular_values_ = sigma
-        self.resolved_modes_ = pod_modes.resolved  # modes above the fp64 noise floor of the block (the rest: see pod_modes)
+        self.resolved_modes_ = pod_modes_h10.resolved if h10 else pod_modes.resolved  # modes above the fp64 noise floor of the block (the rest: see pod_modes)
         super().set(basis=np.vstack((basis, comps))[:n], a=np.vstack((a, a2train))[:n])
         warning("PCA method has not been adapted for inverse parameter estimation, the a coefficients are not correct.")
         return self
