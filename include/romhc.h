@@ -361,6 +361,47 @@ int rom_complete_orthonormal(rom_ctx* ctx, rom_buf* V, int64_t v_row0, int found
  * the same with the rotation threshold 16 eps sqrt(a_pp a_qq) instead of n eps (what rom_pca_tall uses).  Test hook. */
 int rom_small_eig_host(rom_ctx* ctx, int n, const double* A_host, int mode, double rel_tol, int gram_like,
                        double* lam_host, double* T_host);
+/* ---- residual error bounds of the Galerkin ROM and the weak greedy (no truth snapshots) ------------------------------------
+ * A(a) = sum_q a_q A_q (k = nrb*ncb blocks, A_q positive semidefinite, sum_q A_q = A_1), so for the Galerkin solution u_n(a)
+ * on span C[0..n):   ||r|| / max_q a_q <= ||u(a) - u_n(a)||_{H^1_0} <= ||r|| / min_q a_q ,  r = f - A(a) u_n in the H^-1 norm.
+ * With W the A_1-orthonormal basis of the span (CGS2, the dead-row rule of rom_error_curves), r = sum_j z_j g_j over the
+ * P = 1 + k n functionals g_0 = f, g_{1+ik+q} = A_q w_i with z = (1, -c_i a_q), c the solution of the reduced system in W.
+ * The handle keeps the g_j in H^-1 coordinates (rom_sine_transform (0, -1)) ORTHONORMALISED: g^_j = sum_i R_ij q_i with
+ * Euclidean-orthonormal rows q_i, and ||r|| = ||R z||_2 -- the form z^T G z with the Gram matrix of the g^_j stops at
+ * sqrt(eps) ||f|| and is never formed.  A functional whose remainder after two Gram-Schmidt rounds is below 1e-14 of its norm
+ * adds no row (the g_j are rank deficient by construction).  The ordering is i-major: the first 1 + k n' functionals are
+ * those of the nested basis n'.  No floating-point atomics anywhere: the same bits on a repeated call. */
+typedef struct rom_resid rom_resid;
+/* an empty estimator (n = 0: ||f||) for at most n_cap basis rows; workspace (2 n_cap + 2 k + P_cap) dim doubles */
+int rom_resid_create(rom_fem* fem, int n_cap, rom_resid** out);
+int rom_resid_destroy(rom_resid* h);
+/* extend the basis by the rows C[c_row0 .. +rows) (not modified).  One host synchronisation per functional (k per row) and one
+ * per row. */
+int rom_resid_append(rom_resid* h, rom_buf* C, int64_t c_row0, int rows);
+/* out8: rows n, live rows, P, rank, n_cap, k, dim, host synchronisations so far */
+int rom_resid_query(rom_resid* h, int64_t* out8);
+/* test hook, host copies: what = 0 R (rank x P), 1 Q (rank x dim), 2 the reduced tensor W A_q W^T (k x n x n, a dead direction
+ * has a unit diagonal), 3 W f (n), 4 W (n x dim), 5 the rank after n' rows for n' = 0 .. n (n + 1), 6 dead flags (n).
+ * count must be the size of the part. */
+int rom_resid_download(rom_resid* h, int what, double* host, size_t count);
+/* OUT[out_row0 .. +n) = W: u_n = c W through rom_gemm_nn with the COEF of rom_resid_eval */
+int rom_resid_basis(rom_resid* h, rom_buf* OUT, int64_t out_row0);
+/* DELTA[d_off + m] = weights[m] ||r(a_m)||_{H^-1} (weights NULL: 1) for the parameters a[a_row0 .. +M) (M x k) and the
+ * nested basis of the first n <= built rows; n = 0 gives ||f||_{H^-1}.  COEF (may be NULL) receives c, the coordinates of
+ * u_n in W (M x n from row coef_row0: ||u_n||_{H^1_0} = ||c||_2); without it the call takes M x n doubles of workspace.
+ * Reduced solves: one launch per 2^18 parameters; then one MFMA kernel whose A operand z is formed as it is staged.
+ * One host synchronisation.  ROM_ERR_NOT_SPD if a reduced matrix has a non-positive pivot. */
+int rom_resid_eval(rom_resid* h, rom_buf* a, int64_t a_row0, int64_t M, int n, rom_buf* weights, rom_buf* DELTA, int64_t d_off,
+                   rom_buf* COEF, int64_t coef_row0);
+/* Weak greedy over the M parameters a (M x k) with a fresh handle h of capacity >= n_max.  Per step: evaluate all M with the
+ * basis so far; the first maximum of weights[m] ||r(a_m)|| among the parameters not yet picked (np.argmax); stop when it is
+ * <= rel_tol times the first step's; solve the picked parameter (rom_solve_batch) into BASIS[basis_row0 + step] -- raw
+ * snapshots in pick order -- and append it to h.  picks_out / crit_out (n_max entries): picks and their criteria.
+ * info_host (6 doubles or NULL): picks made, dead rows, stop reason (0 n_max, 1 rel_tol, 2 every parameter picked), final
+ * rank, host synchronisations, the last criterion evaluated.  Workspace M (n_max + 1) doubles besides the handle's: no
+ * M x dim block exists.  ROM_ERR_NOT_SPD as rom_resid_eval. */
+int rom_weak_greedy(rom_fem* fem, rom_buf* a, int64_t M, rom_buf* weights, int n_max, double rel_tol, rom_resid* h,
+                    rom_buf* BASIS, int64_t basis_row0, int64_t* picks_out, double* crit_out, double* info_host);
 
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */

@@ -110,6 +110,14 @@ PROTOTYPES = {
     "rom_symmetric_orthonormalize": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64]),
     "rom_complete_orthonormal": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "rom_small_eig_host": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_double, C.c_int, _vp, _vp]),
+    "rom_resid_create": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    "rom_resid_destroy": (C.c_int, [_vp]),
+    "rom_resid_append": (C.c_int, [_vp, _vp, C.c_int64, C.c_int]),
+    "rom_resid_query": (C.c_int, [_vp, _vp]),
+    "rom_resid_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
+    "rom_resid_basis": (C.c_int, [_vp, _vp, C.c_int64]),
+    "rom_resid_eval": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64]),
+    "rom_weak_greedy": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int, C.c_double, _vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "rom_comm_unique_id": (C.c_int, [C.c_char_p, C.c_size_t]),
     "rom_comm_init": (C.c_int, [_vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int]),
     "rom_comm_destroy": (C.c_int, [_vp]),
@@ -659,10 +667,83 @@ class Fem:
         inf = {"dead_rows": int(info[0]), "picks": int(info[1]), "stop_reason": int(info[2]), "host_syncs": int(info[3])}
         return picks[:m], crit[:m], A[:m, :n], (alpha[:m, :n] if alpha is not None else None), inf
 
+    # -- residual error bounds and the weak greedy (rom_resid.hip) ---------------------------------------------
+    def resid(self, n_cap: int) -> "Resid":
+        """rom_resid_create: an empty residual estimator for at most n_cap basis rows."""
+        return Resid(self, n_cap)
+
+    def weak_greedy(self, a: Buffer, M: int, n_max: int, resid: "Resid", BASIS: Buffer, weights: Buffer | None = None,
+                    rel_tol=0.0, basis_row0=0):
+        """rom_weak_greedy on a fresh estimator: (picks list, criteria list, info dict); the snapshots of the picks are
+        the rows BASIS[basis_row0 ...] and ``resid`` holds the estimator of the basis built."""
+        picks, crit = np.zeros(max(n_max, 1), dtype=np.int64), np.zeros(max(n_max, 1))
+        info = np.zeros(6)
+        check(self.ctx.lib.rom_weak_greedy(self.h, a.h, M, weights.h if weights is not None else None, n_max, float(rel_tol),
+                                           resid.h, BASIS.h, basis_row0, picks.ctypes.data, crit.ctypes.data,
+                                           info.ctypes.data))
+        made = int(info[0])
+        inf = {"picks": made, "dead_rows": int(info[1]), "stop_reason": ("n_max", "rel_tol", "exhausted")[int(info[2])],
+               "rank": int(info[3]), "host_syncs": int(info[4]), "last_criterion": float(info[5])}
+        return [int(p) for p in picks[:made]], [float(c) for c in crit[:made]], inf
+
     def __del__(self):
         try:
             if getattr(self, "h", None):
                 self.ctx.lib.rom_fem_destroy(self.h)
                 self.h = None
+        except Exception:
+            pass
+
+
+class Resid:
+    """Handle of a residual estimator (rom_resid_*): the offline state of the bound ||r(a)||_{H^-1} of a Galerkin ROM."""
+
+    _PARTS = {"R": 0, "Q": 1, "Ahat": 2, "bhat": 3, "W": 4, "ranks": 5, "dead": 6}
+
+    def __init__(self, fem: Fem, n_cap: int):
+        self.fem, self.ctx = fem, fem.ctx
+        h = _vp()
+        check(self.ctx.lib.rom_resid_create(fem.h, int(n_cap), C.byref(h)))
+        self.h = h
+
+    def append(self, Cb: Buffer, rows: int, c_row0=0):
+        check(self.ctx.lib.rom_resid_append(self.h, Cb.h, c_row0, rows))
+        return self
+
+    def query(self) -> dict:
+        out = np.zeros(8, dtype=np.int64)
+        check(self.ctx.lib.rom_resid_query(self.h, out.ctypes.data))
+        keys = ("n", "n_live", "P", "rank", "n_cap", "k", "dim", "host_syncs")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def download(self, part: str) -> np.ndarray:
+        """Host copy of "R" (rank, P), "Q" (rank, dim), "Ahat" (k, n, n), "bhat" (n,), "W" (n, dim), "ranks" (n + 1,)
+        or "dead" (n,)."""
+        q = self.query()
+        n, k, dim, rank, P = q["n"], q["k"], q["dim"], q["rank"], q["P"]
+        shape = {"R": (rank, P), "Q": (rank, dim), "Ahat": (k, n, n), "bhat": (n,), "W": (n, dim), "ranks": (n + 1,),
+                 "dead": (n,)}[part]
+        out = np.zeros(shape)
+        check(self.ctx.lib.rom_resid_download(self.h, self._PARTS[part], out.ctypes.data if out.size else None, out.size))
+        return out
+
+    def basis(self, OUT: Buffer, out_row0=0):
+        """OUT[out_row0 ...] = W (n rows): u_n = c W with the coefficients of ``eval``."""
+        check(self.ctx.lib.rom_resid_basis(self.h, OUT.h, out_row0))
+
+    def eval(self, a: Buffer, M: int, n: int, DELTA: Buffer, weights: Buffer | None = None, COEF: Buffer | None = None,
+             a_row0=0, d_off=0, coef_row0=0):
+        """rom_resid_eval: DELTA[d_off + m] = weights[m] ||r(a_m)||_{H^-1} on the nested basis of the first n rows."""
+        check(self.ctx.lib.rom_resid_eval(self.h, a.h, a_row0, M, n, weights.h if weights is not None else None, DELTA.h,
+                                          d_off, COEF.h if COEF is not None else None, coef_row0))
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.rom_resid_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass

@@ -25,6 +25,7 @@ INFINIT_A = 1e10  # (:11)
 
 GREEDY_FOR_H10 = r"$H^1_0$"  # (:101)
 GREEDY_FOR_GALERKIN = "galerkin"  # (:102)
+GREEDY_FOR_RESIDUAL = "residual"  # weak greedy on the residual error bound: no training snapshots (rom_weak_greedy)
 
 
 def get_high_contrast_coefficient(a):
@@ -278,6 +279,62 @@ def select_sensors_pbdw(sm: SolutionsManager, basis, candidates, m, mode="collec
     return SensorSelection(P[picks[:k]], picks[:k].copy(), beta, crit[:k].copy(), stop)
 
 
+# ---- residual error bounds of the Galerkin ROM (rom_resid_*) -----------------------------------------------------------------
+class ResidualBound(NamedTuple):
+    """``ResidualEstimator.bound`` / ``.curves``: ||r(a)||_{H^-1} and the two sides of
+    residual / a_max <= ||u(a) - u_n(a)||_{H^1_0} <= residual / a_min; (M,) arrays, or (N + 1, M) for the curves."""
+    residual: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+
+
+class ResidualEstimator:
+    """A-posteriori error bound of the Galerkin ROM on the rows of ``basis`` for parameters nobody has solved: the H^-1 norm
+    of the residual r = f - A(a) u_n from offline quantities of size 1 + k n (k blocks), in the orthonormalised form that
+    keeps its accuracy below sqrt(eps) ||f||.  The offline state lives on the device (not picklable; rebuild it from the
+    basis).  Effectivity of the upper bound: between 1 and a_max / a_min."""
+
+    def __init__(self, sm: SolutionsManager, basis, n_cap=None):
+        self.sm = sm
+        n = 0 if basis is None else len(basis)
+        self.handle = sm._fem.resid(max(n, n_cap or 0))
+        if n:
+            self.handle.append(_as_device(sm._ctx, basis, sm.vspace_dim).buf, n)
+
+    @property
+    def n(self):
+        return self.handle.query()["n"]
+
+    def _eval(self, a, n_values, coefficients=False):
+        sm, ctx = self.sm, self.sm._ctx
+        a = sm._a_batch(a)
+        M = a.shape[0]
+        res = np.zeros((len(n_values), M))
+        coefs = []
+        if M:
+            a_dev, D = ctx.upload(a), ctx.alloc(M)
+            for i, n in enumerate(n_values):
+                Cf = ctx.alloc(max(M * n, 1)) if coefficients else None
+                self.handle.eval(a_dev, M, n, D, COEF=Cf)
+                res[i] = D.download(M)
+                if coefficients:
+                    coefs.append(Cf.download(M * n, shape=(M, n)) if n else np.zeros((M, 0)))
+        return a, res, coefs
+
+    def bound(self, a, n=None, return_coefs=False):
+        """(||r||_{H^-1}, lower = ||r|| / a_max, upper = ||r|| / a_min) for the parameters ``a`` on the first n rows (default:
+        all).  ``return_coefs``: also c (M, n), the coordinates of u_n in the A_1-orthonormal basis (||u_n||_{H^1_0} = ||c||_2)."""
+        n = self.n if n is None else int(n)
+        a, res, coefs = self._eval(a, [n], coefficients=return_coefs)
+        out = ResidualBound(res[0], res[0] / a.max(axis=1), res[0] / a.min(axis=1))
+        return (out, coefs[0]) if return_coefs else out
+
+    def curves(self, a):
+        """The same for every n = 0 .. N through the nested evaluation: (N + 1, M) arrays."""
+        a, res, _ = self._eval(a, list(range(self.n + 1)))
+        return ResidualBound(res, res / a.max(axis=1)[None, :], res / a.min(axis=1)[None, :])
+
+
 class BaseReducedBasis:
     """Container of a reduced basis (rows of ``basis``) and the parameters it came from, with the online
     operations of the reference (:32-98).  Pure host object: picklable, no device state."""
@@ -358,6 +415,12 @@ class BaseReducedBasis:
         n_max = self.dim if n_max is None else min(int(n_max), self.dim)
         return sm.error_curves(true_solutions, np.asarray(self.basis)[:n_max], a)
 
+    def error_bound(self, sm: SolutionsManager, a, n=None):
+        """Residual bounds of ``forward_modeling`` for the parameters ``a`` without their truth (``ResidualEstimator.bound``
+        on the first n rows, default all): (||r||_{H^-1}, lower, upper)."""
+        n = self.dim if n is None else min(int(n), self.dim)
+        return ResidualEstimator(sm, np.asarray(self.basis)[:n]).bound(a)
+
     def parameter_estimation_inverse(self, c):
         """(:72-78) harmonic-mean style estimate from the state-estimation coefficients."""
         return self.inverse_parameter_estimator.estimate_parameter(c_values=c)
@@ -381,8 +444,10 @@ class ReducedBasisGreedy(BaseReducedBasis):
         self.linestyle = "solid" if greedy_for == GREEDY_FOR_H10 else "dashed"
         super().__init__()
 
-    def build(self, n: int, sm: SolutionsManager, solutions2train, a2train: List[np.ndarray] = (()),
+    def build(self, n: int, sm: SolutionsManager, solutions2train=None, a2train: List[np.ndarray] = (()),
               solutions2train_h1norm=1, **kwargs):
+        if self.greedy_for == GREEDY_FOR_RESIDUAL:
+            return self._build_weak(n, sm, a2train, kwargs.get("criterion", "bound"), kwargs.get("rel_tol", 0.0))
         if self.greedy_for not in (GREEDY_FOR_H10, GREEDY_FOR_GALERKIN):
             raise Exception(f"Not implemented greedy for {self.greedy_for}, "
                             f"should be one of [{GREEDY_FOR_H10}, {GREEDY_FOR_GALERKIN}]")
@@ -434,6 +499,30 @@ class ReducedBasisGreedy(BaseReducedBasis):
         else:
             basis = np.asarray(solutions2train)[picks].reshape(len(picks), -1)
         super().set(basis=basis, a=[a2train[i] for i in picks])  # raw snapshots in pick order (:138)
+        return self
+
+
+    def _build_weak(self, n, sm, a2train, criterion, rel_tol):
+        """Weak greedy on the residual bound (rom_weak_greedy): the training set is the (M, k) parameters alone; n truth
+        solves.  criterion "bound" (residual / a_min, the upper bound), "residual", or an array of M weights."""
+        ctx, dim = sm._ctx, sm.vspace_dim
+        a2train = np.asarray(a2train, dtype=np.float64)
+        a = sm._a_batch(a2train)
+        M = a.shape[0]
+        if isinstance(criterion, str):
+            if criterion not in ("bound", "residual"):
+                raise ValueError(f"criterion must be 'bound', 'residual' or an array of {M} weights, not {criterion!r}")
+            w = 1.0 / a.min(axis=1) if criterion == "bound" else None
+        else:
+            w = np.ascontiguousarray(np.asarray(criterion, dtype=np.float64).reshape(M))
+        n = min(int(n), M)
+        resid = sm._fem.resid(n)
+        basis = ctx.alloc(max(n * dim, 1))
+        picks, crit, info = sm._fem.weak_greedy(ctx.upload(a), M, n, resid, basis, weights=ctx.upload(w) if w is not None else None,
+                                                rel_tol=rel_tol)
+        resid.free()
+        self.picks, self.max_errors, self.info = picks, crit, info
+        super().set(basis=DeviceArray(basis, len(picks), dim).numpy(), a=[a2train[i] for i in picks])
         return self
 
 
