@@ -930,10 +930,12 @@ int romb_orthonormalize_against(rom_ctx* ctx, double* V, int found, int take, in
   return romb_gram_transform(ctx, Vn, Y, take, dim, SE_LOWDIN, 1e-30, 1);
 }
 
-// kb_cgs_finish: v <- v / ||v||_2 (norm squared given on the device), zero row if the norm underflows
+// kb_cgs_finish: v <- v / ||v||_2 (norm squared given on the device), zero row if the norm underflows or if what
+// Gram-Schmidt left of the row is at roundoff of the row it was (nrm2[1]: its norm squared before; a dependent row --
+// the dead-direction rule of kb_take_pick)
 __global__ void kb_scale_by_inv_norm(double* __restrict__ v, long long dim, const double* __restrict__ nrm2) {
-  const double n2 = *nrm2;
-  const double a = (n2 > 0.0 && sqrt(n2) > 1e-300) ? 1.0 / sqrt(n2) : 0.0;
+  const double n2 = nrm2[0];
+  const double a = (n2 > 0.0 && sqrt(n2) > 1e-300 && n2 > 1e-26 * nrm2[1]) ? 1.0 / sqrt(n2) : 0.0;
   for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < dim; j += (long long)gridDim.x * blockDim.x) v[j] *= a;
 }
 
@@ -950,10 +952,11 @@ extern "C" int rom_orthonormalize_rows(rom_ctx* ctx, rom_buf* X, int64_t x_row0,
     ROM_HIP(hipMemcpyAsync(q, X->p + x_row0 * dim, size_t(n) * dim * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   Tmp h, nrm;
   ROM_TRY(h.get(ctx, n));
-  ROM_TRY(nrm.get(ctx, 1));
+  ROM_TRY(nrm.get(ctx, 2));
   const unsigned grid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
   for (int j = 0; j < n; ++j) {
     double* v = q + size_t(j) * dim;
+    ROM_TRY(rom_launch_l2norm(ctx, v, 1, dim, nrm.p() + 1, false));  // the row as given: what "dependent" is measured against
     for (int r = 0; r < 2 && j > 0; ++r) {  // "twice is enough"
       ROM_TRY(rom_launch_gemm_nt(ctx, j, 1, dim, 1.0, q, dim, v, dim, 0.0, h, 1, "gemm_nt"));   // h = Q[:j] v
       ROM_TRY(rom_launch_gemm_nn(ctx, 1, dim, j, -1.0, h, j, q, dim, 1.0, v, dim));              // v -= h^T Q[:j]

@@ -51,10 +51,13 @@ extern "C" int rom_assemble_batch(rom_fem* f, rom_buf* a, int M, rom_buf* diag, 
             "rom_assemble_batch: output buffers too small");
   if (M == 0) return ROM_OK;
   FemDev d = make_dev(f);
-  dim3 grid(unsigned((f->dim + 255) / 256), M);
-  {
-    ROM_PROF(f->ctx, "assemble_stencil", 7.0 * f->dim * M, 24.0 * f->dim * M);
-    k_assemble_stencil<<<grid, 256, 0, f->ctx->stream>>>(d, a->p, M, diag->p, east->p, north->p);
+  const size_t ne = size_t(f->nr) * (f->nc - 1), nn = size_t(f->nr - 1) * f->nc;
+  for (int m0 = 0; m0 < M; m0 += 65535) {  // grid.y holds at most 65535 parameters per launch
+    const int Mc = std::min(65535, M - m0);
+    dim3 grid(unsigned((f->dim + 255) / 256), Mc);
+    ROM_PROF(f->ctx, "assemble_stencil", 7.0 * f->dim * Mc, 24.0 * f->dim * Mc);
+    k_assemble_stencil<<<grid, 256, 0, f->ctx->stream>>>(d, a->p + size_t(m0) * kblk, Mc, diag->p + size_t(m0) * f->dim,
+                                                         east->p + size_t(m0) * ne, north->p + size_t(m0) * nn);
   }
   ROM_HIP(hipGetLastError());
   return ROM_OK;

@@ -1251,8 +1251,8 @@ extern "C" int rom_l2norm(rom_ctx* ctx, rom_buf* U, int64_t row0, int K, int64_t
 }
 
 // ============================================================================================
-// batched reduced SPD solves: one workgroup per system.  The n x n matrix lives in LDS while it fits (n <= 140 with
-// the 160 KB of a gfx950 CU opted in; n <= 88 inside the default 64 KB), otherwise in a per-system slab of global
+// batched reduced SPD solves: one workgroup per system.  The n x n matrix lives in LDS while it fits (n <= 141 with
+// the 160 KB of a gfx950 CU opted in; n <= 89 inside the default 64 KB), otherwise in a per-system slab of global
 // memory (L2 resident: 200 x 200 doubles = 320 KB per system) -- the reference's galerkin() takes any n
 // (src/lib/SolutionsManagers.py:17-40).  Same elimination order either way.
 // ============================================================================================
@@ -1604,10 +1604,11 @@ extern "C" int rom_evaluate_points(rom_fem* f, rom_buf* U, int64_t row0, int K, 
   ROM_HIP(hipMemcpyAsync(d_i + npts, iy_host, npts * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   ROM_HIP(hipMemcpyAsync(d_t, tx_host, npts * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ROM_HIP(hipMemcpyAsync(d_t + npts, ty_host, npts * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  {
-    ROM_PROF(ctx, "eval_points", 8.0 * K * npts, 32.0 * K * npts);
-    k_eval_points<<<dim3((npts + 255) / 256, K), 256, 0, ctx->stream>>>(f->nr, f->nc, f->dim, U->p + row0 * f->dim,
-                                                                       K, npts, d_i, d_i + npts, d_t, d_t + npts, d_out);
+  for (int k0 = 0; k0 < K; k0 += 65535) {  // grid.y holds at most 65535 solutions per launch
+    const int Kc = std::min(65535, K - k0);
+    ROM_PROF(ctx, "eval_points", 8.0 * Kc * npts, 32.0 * Kc * npts);
+    k_eval_points<<<dim3((npts + 255) / 256, Kc), 256, 0, ctx->stream>>>(f->nr, f->nc, f->dim, U->p + (row0 + k0) * f->dim, Kc, npts,
+                                                                        d_i, d_i + npts, d_t, d_t + npts, d_out + size_t(k0) * npts);
   }
   ROM_HIP(hipGetLastError());
   ROM_HIP(hipMemcpyAsync(out_host, d_out, size_t(K) * npts * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -917,10 +917,10 @@ def test_basis_stage_calls_edge_cases(api):
     assert lib.rom_project_h10(fem.h, X.h, 0, M, X.h, 5, M, X.h, 0) != 0                        # basis rows out of range
 
 
-@pytest.mark.parametrize("n", [1, 64, 88, 89, 100, 140, 141, 150, 260])
+@pytest.mark.parametrize("n", [1, 64, 88, 89, 90, 100, 140, 141, 142, 150, 260])
 def test_reduced_solves_of_any_size(api, n):
     """galerkin() takes any n in the reference (src/lib/SolutionsManagers.py:17-40): the batched reduced solve keeps the
-    matrix in LDS up to n = 140 (64 KB default up to 88, the CU's 160 KB beyond) and in global memory after that."""
+    matrix in LDS up to n = 141 (64 KB default up to 89, the CU's 160 KB from 90 on) and in global memory from 142 on."""
     SM, _ = api
     from romhighcontrast_amd import _ffi
     ctx = _ffi.get_context()
