@@ -24,15 +24,34 @@ __global__ void kb_fill(double* p, size_t n, double v) {
   for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) p[i] = v;
 }
 
-static int fill(rom_ctx* ctx, double* p, size_t n, double v) {
+int romb_fill(rom_ctx* ctx, double* p, size_t n, double v) {
   if (n == 0) return ROM_OK;
-  if (v == 0.0) {
+  if (v == 0.0 && !std::signbit(v)) {  // (+0.0 only: -0.0 == 0.0, but its bits are not all zero)
     ROM_HIP(hipMemsetAsync(p, 0, n * sizeof(double), ctx->stream));
     return ROM_OK;
   }
   kb_fill<<<unsigned(std::min<size_t>((n + 255) / 256, 2048)), 256, 0, ctx->stream>>>(p, n, v);
   ROM_HIP(hipGetLastError());
   return ROM_OK;
+}
+
+__global__ void kb_identity(double* __restrict__ E, int k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < k * k) E[i] = (i / k == i % k) ? 1.0 : 0.0;
+}
+
+int romb_onehot(rom_ctx* ctx, int k, double* out) {
+  kb_identity<<<blocks_for(size_t(k) * k), 256, 0, ctx->stream>>>(out, k);
+  ROM_HIP(hipGetLastError());
+  return ROM_OK;
+}
+
+// B_total = h^2 in every inner entry (:177-185)
+int romb_load_vector(rom_fem* f, double* out) { return romb_fill(f->ctx, out, size_t(f->dim), 1.0 / (double(f->N) * f->N)); }
+
+__global__ void kb_ints_to_doubles(const int* __restrict__ src, double* __restrict__ dst, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = double(src[i]);
 }
 
 // counter-based generator (splitmix64 of seed and index): the same numbers whatever the launch shape
@@ -68,7 +87,6 @@ __global__ void kb_rows_axpy(double* __restrict__ out, const double* __restrict_
     out[o + j] = (x ? x[o + j] : 0.0) + a * y[o + j];
 }
 
-// dst (cols x rows, ld ldd) = transpose of src (rows x cols, ld lds): small matrices only
 __global__ void kb_transpose(double* __restrict__ dst, long long ldd, const double* __restrict__ src, long long lds,
                              int rows, int cols) {
   const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -77,7 +95,7 @@ __global__ void kb_transpose(double* __restrict__ dst, long long ldd, const doub
   dst[c * ldd + r] = src[r * lds + c];
 }
 
-static int transpose(rom_ctx* ctx, double* dst, long long ldd, const double* src, long long lds, int rows, int cols) {
+int romb_transpose(rom_ctx* ctx, double* dst, long long ldd, const double* src, long long lds, int rows, int cols) {
   if (rows <= 0 || cols <= 0) return ROM_OK;
   kb_transpose<<<unsigned(((long long)rows * cols + 255) / 256), 256, 0, ctx->stream>>>(dst, ldd, src, lds, rows, cols);
   ROM_HIP(hipGetLastError());
@@ -829,8 +847,8 @@ static int jacobi_grid(rom_ctx* ctx, int n, const double* A, int lda, double* la
     double* S = An;
     double* St = Vn;
     kb_jgrid_gather<<<gg, 256, 0, ctx->stream>>>(n, ne, Vc, diag, d_perm, scb, S, n, lam);
-    kb_transpose<<<gg, 256, 0, ctx->stream>>>(St, n, S, n, n, n);
     ROM_HIP(hipGetLastError());
+    ROM_TRY(romb_transpose(ctx, St, n, S, n, n, n));
     ROM_TRY(rom_launch_gemm_nt(ctx, n, n, n, 1.0, St, n, St, n, 0.0, T, ldt, "gemm_nt"));
   }
   ROM_HIP(hipStreamSynchronize(ctx->stream));   // (perm / scale are host memory of this frame)
@@ -932,10 +950,10 @@ int romb_orthonormalize_against(rom_ctx* ctx, double* V, int found, int take, in
 
 // kb_cgs_finish: v <- v / ||v||_2 (norm squared given on the device), zero row if the norm underflows or if what
 // Gram-Schmidt left of the row is at roundoff of the row it was (nrm2[1]: its norm squared before; a dependent row --
-// the dead-direction rule of kb_take_pick)
+// a1_dead in the Euclidean norm)
 __global__ void kb_scale_by_inv_norm(double* __restrict__ v, long long dim, const double* __restrict__ nrm2) {
   const double n2 = nrm2[0];
-  const double a = (n2 > 0.0 && sqrt(n2) > 1e-300 && n2 > 1e-26 * nrm2[1]) ? 1.0 / sqrt(n2) : 0.0;
+  const double a = (!a1_dead(n2, nrm2[1]) && sqrt(n2) > 1e-300) ? 1.0 / sqrt(n2) : 0.0;
   for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < dim; j += (long long)gridDim.x * blockDim.x) v[j] *= a;
 }
 
@@ -953,7 +971,7 @@ extern "C" int rom_orthonormalize_rows(rom_ctx* ctx, rom_buf* X, int64_t x_row0,
   Tmp h, nrm;
   ROM_TRY(h.get(ctx, n));
   ROM_TRY(nrm.get(ctx, 2));
-  const unsigned grid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
+  const unsigned grid = vector_grid(dim);
   for (int j = 0; j < n; ++j) {
     double* v = q + size_t(j) * dim;
     ROM_TRY(rom_launch_l2norm(ctx, v, 1, dim, nrm.p() + 1, false));  // the row as given: what "dependent" is measured against
@@ -1008,7 +1026,7 @@ extern "C" int rom_project_h10(rom_fem* f, rom_buf* U, int64_t u_row0, int M, ro
   rom_ctx* ctx = f->ctx;
   if (M == 0) return ROM_OK;
   double* out = OUT->p + out_row0 * dim;
-  if (n == 0) return fill(ctx, out, size_t(M) * dim, 0.0);  // (:109-111)
+  if (n == 0) return romb_fill(ctx, out, size_t(M) * dim, 0.0);  // (:109-111)
   const double* u = U->p + u_row0 * dim;
   const double* c = C->p + c_row0 * dim;
   Tmp AC, G, R, ones, coef;
@@ -1020,7 +1038,7 @@ extern "C" int rom_project_h10(rom_fem* f, rom_buf* U, int64_t u_row0, int M, ro
   ROM_TRY(rom_launch_stencil_apply(f, nullptr, c, n, AC));                                           // A_1 C^T (:123)
   ROM_TRY(rom_launch_gemm_nt(ctx, n, n, dim, 1.0, AC, dim, c, dim, 0.0, G, n, "gemm_nt"));            // C A_1 C^T (:136)
   ROM_TRY(rom_launch_gemm_nt(ctx, M, n, dim, 1.0, u, dim, AC, dim, 0.0, R, n, "gemm_nt"));            // rhs (:113-124)
-  ROM_TRY(fill(ctx, ones, M, 1.0));
+  ROM_TRY(romb_fill(ctx, ones, M, 1.0));
   ROM_HIP(hipMemsetAsync(ctx->d_status, 0, sizeof(int), ctx->stream));
   ROM_TRY(rom_launch_reduced_solve(ctx, n, n, 1, M, G, ones, R, 1, coef));                            // (:135-138)
   ROM_TRY(rom_launch_gemm_nn(ctx, M, dim, n, 1.0, coef, n, c, dim, 0.0, out, dim));                   // (:139)
@@ -1028,23 +1046,19 @@ extern "C" int rom_project_h10(rom_fem* f, rom_buf* U, int64_t u_row0, int M, ro
 }
 
 // reduced tensor Ahat[b] = C A_b C^T (k, n, n) and b_hat = C B_total of generate_fm_solutions (:93-103)
-static int reduced_tensor(rom_fem* f, const double* c, int n, double* Ahat, double* bhat) {
+int romb_reduced_tensor(rom_fem* f, const double* c, int n, double* AC, double* Ahat, double* bhat) {
   rom_ctx* ctx = f->ctx;
   const int k = f->nrb * f->ncb;
   const int64_t dim = f->dim;
-  Tmp AC, onehot, Bt;
-  ROM_TRY(AC.get(ctx, size_t(n) * dim));
+  Tmp onehot, Bt;
   ROM_TRY(onehot.get(ctx, size_t(k) * k));
   ROM_TRY(Bt.get(ctx, dim));
-  std::vector<double> eye(size_t(k) * k, 0.0);
-  for (int b = 0; b < k; ++b) eye[size_t(b) * k + b] = 1.0;
-  ROM_HIP(hipMemcpyAsync(onehot.p(), eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ROM_HIP(hipStreamSynchronize(ctx->stream));  // (the host vector goes out of scope)
+  ROM_TRY(romb_onehot(ctx, k, onehot));
   for (int b = 0; b < k; ++b) {
     ROM_TRY(rom_launch_stencil_apply(f, onehot.p() + size_t(b) * k, c, n, AC));
     ROM_TRY(rom_launch_gemm_nt(ctx, n, n, dim, 1.0, AC, dim, c, dim, 0.0, Ahat + size_t(b) * n * n, n, "gemm_nt"));
   }
-  ROM_TRY(fill(ctx, Bt, dim, 1.0 / (double(f->N) * f->N)));  // B_total = h^2 (:177-185)
+  ROM_TRY(romb_load_vector(f, Bt));
   return rom_launch_gemm_nt(ctx, n, 1, dim, 1.0, c, dim, Bt, dim, 0.0, bhat, 1, "gemm_nt");
 }
 
@@ -1060,13 +1074,14 @@ extern "C" int rom_galerkin_rom(rom_fem* f, rom_buf* a, int M, rom_buf* C, int64
   rom_ctx* ctx = f->ctx;
   if (M == 0) return ROM_OK;
   double* out = OUT->p + out_row0 * dim;
-  if (n == 0) return fill(ctx, out, size_t(M) * dim, 0.0);  // (:89-91)
+  if (n == 0) return romb_fill(ctx, out, size_t(M) * dim, 0.0);  // (:89-91)
   const double* c = C->p + c_row0 * dim;
-  Tmp Ahat, bhat, coef;
+  Tmp Ahat, bhat, coef, AC;
   ROM_TRY(Ahat.get(ctx, size_t(k) * n * n));
   ROM_TRY(bhat.get(ctx, n));
   ROM_TRY(coef.get(ctx, size_t(M) * n));
-  ROM_TRY(reduced_tensor(f, c, n, Ahat, bhat));
+  ROM_TRY(AC.get(ctx, size_t(n) * dim));
+  ROM_TRY(romb_reduced_tensor(f, c, n, AC, Ahat, bhat));
   ROM_HIP(hipMemsetAsync(ctx->d_status, 0, sizeof(int), ctx->stream));
   ROM_TRY(rom_launch_reduced_solve(ctx, n, n, k, M, Ahat, a->p, bhat, 0, coef));   // (:104-105)
   ROM_TRY(rom_launch_gemm_nn(ctx, M, dim, n, 1.0, coef, n, c, dim, 0.0, out, dim));  // (:106)
@@ -1133,7 +1148,7 @@ __global__ void kb_take_pick(double* __restrict__ w, const double* __restrict__ 
                              const double* __restrict__ err2, const double* __restrict__ norm0sq, int* __restrict__ degenerate) {
   const int p = picks[it];
   const double e2 = err2[p];
-  const bool dead = !(e2 > 1e-26 * norm0sq[p]) || !(e2 > 0.0);
+  const bool dead = a1_dead(e2, norm0sq[p]);
   const double a = dead ? 0.0 : 1.0 / sqrt(e2);
   if (blockIdx.x == 0 && threadIdx.x == 0) degenerate[it] = dead ? 1 : 0;
   const double* r = Rs + (long long)p * dim;
@@ -1150,20 +1165,43 @@ __global__ void kb_renormalise(double* __restrict__ w, long long dim, const doub
   for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < dim; j += (long long)gridDim.x * blockDim.x) w[j] *= a;
 }
 
-// One Gram-Schmidt round of w against the A_1-orthonormal rows W[0..j) (AW = A_1 W): t_i = <w_i, w>_A, w -= t^T W,
-// nrm = ||w||_A^2, then w <- w / sqrt(nrm), or 0 when degenerate[it] (the dead-vector rule of kb_take_pick).  The
-// re-orthogonalisation of the greedy and both rounds of rom_error_curves' CGS2 (rom_curves.hip).
-int romb_a1_reorth(rom_fem* f, const double* W, const double* AW, int j, double* w, double* t, double* nrm,
-                   const int* degenerate, int it) {
+// The projection of a Gram-Schmidt round of w against the A_1-orthonormal rows W[0..j) (AW = A_1 W): t_i = <w_i, w>_A,
+// w -= t^T W, nrm = ||w||_A^2
+static int a1_project(rom_fem* f, const double* W, const double* AW, int j, double* w, double* t, double* nrm) {
   rom_ctx* ctx = f->ctx;
   const int64_t dim = f->dim;
-  const unsigned vgrid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
   ROM_TRY(rom_launch_rowdot(ctx, AW, j, dim, w, t));                                    // t_i = <w_i, w>_A
   ROM_TRY(rom_launch_gemm_nn(ctx, 1, dim, j, -1.0, t, j, W, dim, 1.0, w, dim));         // w -= t^T W
-  ROM_TRY(rom_launch_h10norm(f, w, nullptr, 1, nrm, false));
-  kb_renormalise<<<vgrid, 256, 0, ctx->stream>>>(w, dim, nrm, degenerate, it);
+  return rom_launch_h10norm(f, w, nullptr, 1, nrm, false);
+}
+
+// One Gram-Schmidt round, then w <- w / sqrt(nrm), or 0 when degenerate[it]: the re-orthogonalisation of the greedy and
+// the second round of romb_a1_append.
+static int romb_a1_reorth(rom_fem* f, const double* W, const double* AW, int j, double* w, double* t, double* nrm,
+                   const int* degenerate, int it) {
+  ROM_TRY(a1_project(f, W, AW, j, w, t, nrm));
+  kb_renormalise<<<vector_grid(f->dim), 256, 0, f->ctx->stream>>>(w, f->dim, nrm, degenerate, it);
   ROM_HIP(hipGetLastError());
   return ROM_OK;
+}
+
+__global__ void kb_a1_decide(const double* __restrict__ nrm1, const double* __restrict__ norm0, int i, int* __restrict__ dead) {
+  dead[i] = a1_dead(*nrm1, norm0[i]) ? 1 : 0;
+}
+
+int romb_a1_append(rom_fem* f, double* W, double* AW, int i, const double* norm0, double* t1, double* t2, double* nrm1,
+                   double* nrm2, int* dead) {
+  rom_ctx* ctx = f->ctx;
+  const int64_t dim = f->dim;
+  double* wi = W + size_t(i) * dim;
+  if (i == 0) ROM_HIP(hipMemcpyAsync(nrm1, norm0, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  else ROM_TRY(a1_project(f, W, AW, i, wi, t1, nrm1));
+  kb_a1_decide<<<1, 1, 0, ctx->stream>>>(nrm1, norm0, i, dead);
+  ROM_HIP(hipGetLastError());
+  kb_renormalise<<<vector_grid(dim), 256, 0, ctx->stream>>>(wi, dim, nrm1, dead, i);
+  ROM_HIP(hipGetLastError());
+  if (i > 0) ROM_TRY(romb_a1_reorth(f, W, AW, i, wi, t2, nrm2, dead, i));
+  return rom_launch_stencil_apply(f, nullptr, wi, 1, AW + size_t(i) * dim);  // z_i = A_1 w_i
 }
 
 // The pass of one greedy iteration over the training block (see above): d = Rs_m - p_prev[m] w_prev (written to Rout when
@@ -1340,11 +1378,6 @@ __global__ void kb_galerkin_gap(int M, int n, const double* __restrict__ P, cons
   extra2[m] = s;
 }
 
-__global__ void kb_ints_to_doubles(const int* __restrict__ src, double* __restrict__ dst, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = double(src[i]);
-}
-
 // mode 0: greedy for the H^1_0 projection error; 1: for the Galerkin error.  h1norm: the normalisation the caller passes
 // as solutions2train_h1norm (M doubles on the host).  picks_out / max_err_out: n entries.
 extern "C" int rom_greedy(rom_fem* f, rom_buf* U, int64_t u_row0, int M, rom_buf* a, const double* h1norm_host, int mode,
@@ -1391,12 +1424,9 @@ extern "C" int rom_greedy(rom_fem* f, rom_buf* U, int64_t u_row0, int M, rom_buf
     ROM_TRY(col.get(ctx, size_t(nb) * k));
     ROM_TRY(onehot.get(ctx, size_t(k) * k));
     ROM_TRY(Bt.get(ctx, dim));
-    ROM_TRY(fill(ctx, Ahat, size_t(k) * nb * nb, 0.0));
-    ROM_TRY(fill(ctx, Bt, dim, 1.0 / (double(f->N) * f->N)));
-    std::vector<double> eye(size_t(k) * k, 0.0);
-    for (int b = 0; b < k; ++b) eye[size_t(b) * k + b] = 1.0;
-    ROM_HIP(hipMemcpyAsync(onehot.p(), eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ROM_HIP(hipStreamSynchronize(ctx->stream));
+    ROM_TRY(romb_fill(ctx, Ahat, size_t(k) * nb * nb, 0.0));
+    ROM_TRY(romb_load_vector(f, Bt));
+    ROM_TRY(romb_onehot(ctx, k, onehot));
   }
   ROM_HIP(hipMemcpyAsync(h1.p(), h1norm_host, size_t(M) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ROM_HIP(hipStreamSynchronize(ctx->stream));  // the caller's array is free again
@@ -1413,7 +1443,7 @@ extern "C" int rom_greedy(rom_fem* f, rom_buf* U, int64_t u_row0, int M, rom_buf
   const double* Rs = u;  // the block in HBM: all updates but the latest applied (the snapshots themselves are never written)
   double* bufs[2] = {Ra.p(), Rb.p()};
   const double *w_prev = nullptr, *p_prev = nullptr;
-  const unsigned vgrid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
+  const unsigned vgrid = vector_grid(dim);
   for (int it = 1; it < n; ++it) {
     const int j = it - 1;  // index of the basis vector built from pick it - 1
     double* wj = W.p() + size_t(j) * dim;

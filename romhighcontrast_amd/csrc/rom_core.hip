@@ -1,6 +1,6 @@
 #include <mutex>
 // Context, device buffers, error strings, HIP-event stopwatch and per-kernel profiling.
-#include "romhc_internal.h"
+#include "rom_basis_int.h"
 
 #include <algorithm>
 #include <cmath>
@@ -404,24 +404,10 @@ extern "C" int rom_buf_download(rom_buf* b, size_t off, double* host, size_t n) 
   return ROM_OK;
 }
 
-__global__ void k_fill(double* p, size_t n, double v) {
-  size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
-  size_t stride = size_t(gridDim.x) * blockDim.x;
-  for (; i < n; i += stride) p[i] = v;
-}
-
 extern "C" int rom_buf_fill(rom_buf* b, size_t off, size_t n, double value) {
   ROM_CHECK(b, "bad arguments");
   ROM_CHECK(off + n <= b->n, "rom_buf_fill: range exceeds buffer");
-  if (n == 0) return ROM_OK;
-  if (value == 0.0 && !std::signbit(value)) {  // (+0.0 only: -0.0 == 0.0, but its bits are not all zero)
-    ROM_HIP(hipMemsetAsync(b->p + off, 0, n * sizeof(double), b->ctx->stream));
-    return ROM_OK;
-  }
-  int grid = int(std::min<size_t>((n + 255) / 256, 2048));
-  k_fill<<<grid, 256, 0, b->ctx->stream>>>(b->p + off, n, value);
-  ROM_HIP(hipGetLastError());
-  return ROM_OK;
+  return romb_fill(b->ctx, b->p + off, n, value);
 }
 
 extern "C" int rom_buf_copy(rom_buf* dst, size_t dst_off, rom_buf* src, size_t src_off, size_t n) {

@@ -3,9 +3,9 @@
 // The statistics loop of the reference's experiment() (src/experiments/HighContrast.py:176-214) measures, for every
 // n = 1 .. vn_max_dim, the H^1_0 error of the projection onto span C[0..n) and of the Galerkin ROM on that span.  Both
 // depend on the span only, so the call
-//   1. builds an A_1-orthonormal W with span W[0..n) = span C[0..n) for every n: CGS2 in the A_1 inner product, both
-//      rounds the greedy's re-orthogonalisation step (romb_a1_reorth); a row whose residual after the first round is
-//      below 1e-13 of its norm (the dead-vector rule of kb_take_pick) becomes 0 and adds no direction.  C = T W, T lower;
+//   1. builds an A_1-orthonormal W with span W[0..n) = span C[0..n) for every n: CGS2 in the A_1 inner product
+//      (romb_a1_append); a row whose residual after the first round is at roundoff of its norm (a1_dead) becomes 0 and
+//      adds no direction.  C = T W, T lower;
 //   2. takes the projection coefficients P = U (A_1 W)^T with one MFMA product (P_n u_m = sum_{j<n} p_mj w_j);
 //   3. forms, in ONE pass over U, every residual u_m - P_n u_m explicitly and its edge-form H^1_0 norm for all n
 //      (kc_curve: the per-edge differences of the basis rows, DW, precomputed; lanes run over snapshots, each lane
@@ -25,12 +25,6 @@
 namespace {
 
 // ---- small kernels ------------------------------------------------------------------------------------------------
-// dead[i] = residual after the first Gram-Schmidt round at roundoff of the row (nrm1 <= 1e-26 ||C_i||_A^2), or 0
-__global__ void kc_decide(const double* __restrict__ nrm1, const double* __restrict__ norm0, int i, int* __restrict__ dead) {
-  const double e2 = *nrm1;
-  dead[i] = (!(e2 > 1e-26 * norm0[i]) || !(e2 > 0.0)) ? 1 : 0;
-}
-
 // row i of T (N x N, lower): C_i = sum_{j<i} (t1_j + s1 t2_j) w_j + s1 s2 w_i with s1 = sqrt(nrm1), s2 = sqrt(nrm2)
 __global__ void kc_trow(double* __restrict__ T, int N, int i, const double* __restrict__ t1, const double* __restrict__ t2,
                         const double* __restrict__ nrm1, const double* __restrict__ nrm2, const int* __restrict__ dead) {
@@ -53,23 +47,6 @@ __global__ void kc_count_dead(const int* __restrict__ dead, int N, double* __res
 
 __global__ void kc_status(const int* __restrict__ status, double* __restrict__ out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = double(*status);
-}
-
-__global__ void kc_eye(double* __restrict__ E, int k) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < k * k) E[i] = (i / k == i % k) ? 1.0 : 0.0;
-}
-
-__global__ void kc_fill(double* __restrict__ p, size_t n, double v) {
-  for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) p[i] = v;
-}
-
-// dst[c * rows + r] = src[r * cols + c]
-__global__ void kc_transpose(double* __restrict__ dst, const double* __restrict__ src, int rows, int cols) {
-  const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (idx >= (long long)rows * cols) return;
-  const int r = int(idx / cols), c = int(idx % cols);
-  dst[(long long)c * rows + r] = src[idx];
 }
 
 // a dead direction: unit diagonal in every block form (its row and column are exactly 0: w = 0), as kb_grow_ahat does
@@ -246,8 +223,6 @@ __global__ void kc_curve_out(const double* __restrict__ ERR2, const double* __re
   if (GAP) ERR[cnt + i] = sqrt(e2 + GAP[i]);
 }
 
-unsigned blocks_for(size_t n, int threads = 256) { return unsigned(std::max<size_t>(1, (n + threads - 1) / threads)); }
-
 template <int NC>
 void launch_curve(dim3 grid, hipStream_t st, const StencilGeom& g, const double* U, const double* DW, int NP, const double* PT,
                   int M, int N, int j0, long long ept, double* part) {
@@ -286,32 +261,13 @@ extern "C" int rom_error_curves(rom_fem* f, rom_buf* U, int64_t u_row0, int M, r
   int* d_dead = reinterpret_cast<int*>(dead.p());
   ROM_HIP(hipMemsetAsync(ctx->d_status, 0, sizeof(int), ctx->stream));
   ROM_HIP(hipMemsetAsync(dead.p(), 0, size_t(Nb) * sizeof(double), ctx->stream));
-  const unsigned vgrid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
   // 1. CGS2 in the A_1 inner product
   if (N) {
     ROM_PROF(ctx, "curves_basis", 12.0 * N * N * double(dim), 48.0 * N * double(dim));
     ROM_TRY(rom_launch_h10norm(f, c, nullptr, N, norm0, false));  // ||C_i||_A^2
     ROM_HIP(hipMemcpyAsync(W.p(), c, size_t(N) * dim * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    for (int i = 0; i < N; ++i) {
-      double* wi = W.p() + size_t(i) * dim;
-      if (i == 0) {
-        ROM_HIP(hipMemcpyAsync(nrm1.p(), norm0.p(), sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      } else {
-        ROM_TRY(rom_launch_rowdot(ctx, AW, i, dim, wi, t1.p() + size_t(i) * Nb));
-        ROM_TRY(rom_launch_gemm_nn(ctx, 1, dim, i, -1.0, t1.p() + size_t(i) * Nb, i, W, dim, 1.0, wi, dim));
-        ROM_TRY(rom_launch_h10norm(f, wi, nullptr, 1, nrm1.p() + i, false));
-      }
-      kc_decide<<<1, 1, 0, ctx->stream>>>(nrm1.p() + i, norm0, i, d_dead);
-      ROM_HIP(hipGetLastError());
-      if (i == 0) {
-        kb_renormalise<<<vgrid, 256, 0, ctx->stream>>>(wi, dim, nrm1.p(), d_dead, 0);
-        ROM_HIP(hipGetLastError());
-      } else {
-        kb_renormalise<<<vgrid, 256, 0, ctx->stream>>>(wi, dim, nrm1.p() + i, d_dead, i);
-        ROM_HIP(hipGetLastError());
-        ROM_TRY(romb_a1_reorth(f, W, AW, i, wi, t2.p() + size_t(i) * Nb, nrm2.p() + i, d_dead, i));
-      }
-      ROM_TRY(rom_launch_stencil_apply(f, nullptr, wi, 1, AW.p() + size_t(i) * dim));
+    for (int i = 0; i < N; ++i) {  // (row i of the N x N blocks t1, t2: kc_trow reads them)
+      ROM_TRY(romb_a1_append(f, W, AW, i, norm0, t1.p() + size_t(i) * Nb, t2.p() + size_t(i) * Nb, nrm1.p() + i, nrm2.p() + i, d_dead));
       kc_trow<<<blocks_for(N), 256, 0, ctx->stream>>>(T->p, N, i, t1.p() + size_t(i) * Nb, t2.p() + size_t(i) * Nb,
                                                        nrm1.p() + i, nrm2.p() + i, d_dead);
       ROM_HIP(hipGetLastError());
@@ -326,8 +282,7 @@ extern "C" int rom_error_curves(rom_fem* f, rom_buf* U, int64_t u_row0, int M, r
     ROM_TRY(PT.get(ctx, size_t(Nb) * M));
     if (N) {
       ROM_TRY(rom_launch_gemm_nt(ctx, N, M, dim, 1.0, AW, dim, u, dim, 0.0, PT, M, "gemm_nt"));
-      kc_transpose<<<blocks_for(size_t(N) * M), 256, 0, ctx->stream>>>(P->p, PT, N, M);
-      ROM_HIP(hipGetLastError());
+      ROM_TRY(romb_transpose(ctx, P->p, N, PT, M, N, M));
     }
     // 3. the residual curves: one pass over U per chunk of 32 basis vectors
     {
@@ -373,19 +328,10 @@ extern "C" int rom_error_curves(rom_fem* f, rom_buf* U, int64_t u_row0, int M, r
       if (N == 0) {
         ROM_HIP(hipMemsetAsync(GAP.p(), 0, size_t(M) * sizeof(double), ctx->stream));
       } else {
-        Tmp Ahat, bhat, onehot, Bt, ws;
+        Tmp Ahat, bhat, ws;
         ROM_TRY(Ahat.get(ctx, size_t(k) * N * N));
         ROM_TRY(bhat.get(ctx, N));
-        ROM_TRY(onehot.get(ctx, size_t(k) * k));
-        ROM_TRY(Bt.get(ctx, dim));
-        kc_eye<<<blocks_for(size_t(k) * k), 256, 0, ctx->stream>>>(onehot, k);
-        kc_fill<<<unsigned(std::min<int64_t>((dim + 255) / 256, 2048)), 256, 0, ctx->stream>>>(Bt, dim, 1.0 / (double(f->N) * f->N));
-        ROM_HIP(hipGetLastError());
-        for (int b = 0; b < k; ++b) {  // Ahat_b = W A_b W^T (reduced_tensor of rom_basis.hip on the rows of W)
-          ROM_TRY(rom_launch_stencil_apply(f, onehot.p() + size_t(b) * k, W, N, AW));
-          ROM_TRY(rom_launch_gemm_nt(ctx, N, N, dim, 1.0, AW, dim, W, dim, 0.0, Ahat.p() + size_t(b) * N * N, N, "gemm_nt"));
-        }
-        ROM_TRY(rom_launch_gemm_nt(ctx, N, 1, dim, 1.0, W, dim, Bt, dim, 0.0, bhat, 1, "gemm_nt"));  // W B_total
+        ROM_TRY(romb_reduced_tensor(f, W, N, AW, Ahat, bhat));  // Ahat_b = W A_b W^T, W B_total (AW is free: PT holds the coefficients)
         kc_fix_dead<<<blocks_for(size_t(k) * N), 256, 0, ctx->stream>>>(Ahat, k, N, d_dead);
         ROM_HIP(hipGetLastError());
         if (N <= GAL_LDS_MAX) {

@@ -208,11 +208,6 @@ __global__ void kf_scale_cols(int k, int n, const double* __restrict__ LT, const
   if (idx < (long long)k * n) ET[idx] = LT[idx] * d[idx % n];
 }
 
-__global__ void kf_fill_const(double* __restrict__ p, long long n, double v) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
 __global__ void kf_set_identity(double* __restrict__ A, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) A[size_t(i) * n + i] = 1.0;
@@ -264,7 +259,7 @@ __global__ __launch_bounds__(1024) void kf_new_direction(int j, int it, int k1, 
   const int tid = threadIdx.x;
   const int p = picks[it];
   const double e2 = err2[p];
-  const bool dead = !(e2 > 1e-26 * norm0[p]) || !(e2 > 0.0);
+  const bool dead = a1_dead(e2, norm0[p]);
   double* q = Q + size_t(j) * k1;
   double* w = W + size_t(j) * Kc;
   if (dead) {
@@ -504,10 +499,7 @@ int ensure_map(rom_fem* f, int parts) {
     const size_t rect = size_t(N + 1) * (N + 1);
     ROM_TRY(Bc.get(ctx, size_t(Kc) * rect));
     ROM_TRY(Zc.get(ctx, size_t(Kc) * rect));
-    std::vector<double> eye(size_t(kblk) * kblk, 0.0);
-    for (int b = 0; b < kblk; ++b) eye[size_t(b) * kblk + b] = 1.0;
-    ROM_HIP(hipMemcpyAsync(coef.p(), eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ROM_HIP(hipStreamSynchronize(ctx->stream));
+    ROM_TRY(romb_onehot(ctx, kblk, coef));
     for (int b = 0; b < kblk; ++b) {
       const int p = b / f->ncb, q = b % f->ncb;
       // inner vertices (0-based rows r, columns c) touched by the cells of block (p, q): r in [p N - 1, (p + 1) N - 1] clipped
@@ -527,11 +519,7 @@ int ensure_map(rom_fem* f, int parts) {
         ROM_HIP(hipGetLastError());
       }
     }
-    {
-      std::vector<double> bt_h(size_t(dim), 1.0 / (double(f->N) * f->N));  // B_total (:177-185: every inner entry h^2)
-      ROM_HIP(hipMemcpyAsync(Btot.p(), bt_h.data(), bt_h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      ROM_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    ROM_TRY(romb_load_vector(f, Btot));
     ROM_TRY(rom_launch_rowdot(ctx, Bt, Kc, dim, Btot, bt));
     ROM_HIP(hipStreamSynchronize(ctx->stream));
     mp->Sb = Sb;
@@ -777,8 +765,7 @@ int pod_factored(rom_fem* f, bool h10, const char* who, rom_buf* Yc, int64_t c_r
   }
   ROM_TRY(Yfull.get(ctx, size_t(nz) * f->nGp));
   ROM_TRY(ones.get(ctx, size_t(nz) * kblk));
-  kf_fill_const<<<unsigned((size_t(nz) * kblk + 255) / 256), 256, 0, ctx->stream>>>(ones, (long long)nz * kblk, 1.0);
-  ROM_HIP(hipGetLastError());
+  ROM_TRY(romb_fill(ctx, ones, size_t(nz) * kblk, 1.0));
   ROM_TRY(rom_fem_unpack_reduced_async(f, Wc.b, 0, nz, Yfull.b, 0));
   ROM_TRY(rom_expand_batch_async(f, ones.b, nz, Yfull.b, 0, V, v_row0));
   // clean-up of the factor's defect and completion, in the coordinates in which the inner product is Euclidean

@@ -47,6 +47,9 @@ __global__ void k_eval_points(int nr, int nc, long long dim, const double* __res
                               double* __restrict__ out);
 // the sine tables of rom_riesz_h10, built once per FE space into f->d_riesz: S_r (nr x nr), S_c (nc x nc), lam_r, lam_c
 int rom_riesz_tables(rom_fem* f);
+// where they lie in f->d_riesz (valid after rom_riesz_tables)
+struct SineTables { const double *Sr, *Sc, *lam_r, *lam_c; };
+SineTables rom_sine_tables(const rom_fem* f);
 // the 2-D sine transform of K dense rows (rom_spectral.hip): OUT[k] = Lambda^(post/2) o (S_r (Lambda^(pre/2) o X[k]) S_c) on raw
 // device rows, OUT != X; its flop count (both factors)
 int rom_launch_sine_transform(rom_fem* f, const double* X, int K, int pre, int post, double* OUT);

@@ -21,9 +21,6 @@
 #include "rom_basis_int.h"
 #include "rom_mma.h"
 
-// (rom_pod.hip) out[0] = bits of the largest finite |x|, out[1] = number of entries that are not finite
-__global__ void kp_block_amax(const double* __restrict__ X, size_t count, unsigned long long* __restrict__ out);
-
 namespace {
 
 constexpr int PT_FUSED_MAX = 96;   // largest dim of the fused kernel (V + two slabs in 160 KB of LDS)
@@ -345,12 +342,6 @@ __global__ void k_newton_schulz_matrix(const double* __restrict__ E, int n, doub
   T[idx] = (r == c ? 1.5 : 0.0) - 0.5 * E[idx];
 }
 
-__global__ void k_identity(double* __restrict__ V, int n) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * n) return;
-  V[idx] = (idx / n == idx % n) ? 1.0 : 0.0;
-}
-
 // Vn[i, :] = Vc[perm[i], :]: a pure copy, the rows keep their bits
 __global__ void k_permute_rows(const double* __restrict__ Vc, const int* __restrict__ perm, int n, double* __restrict__ Vn) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -482,8 +473,7 @@ extern "C" int rom_pca_tall(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int
   }
   double *Vc = Va, *Vn = Vb;
   const unsigned gdd = unsigned((dd + 255) / 256);
-  k_identity<<<gdd, 256, 0, ctx->stream>>>(Vc, dim);
-  ROM_HIP(hipGetLastError());
+  ROM_TRY(romb_onehot(ctx, int(dim), Vc));
 
   size_t fused_lds = 0;
   if (plan.fused) {

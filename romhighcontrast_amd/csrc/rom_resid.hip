@@ -13,8 +13,8 @@
 // The functionals are rank deficient by construction (after the first pick f = sum_q a_q A_q u_1 lies in their span): a
 // functional whose remainder is at roundoff of its norm (RS_DROP) adds no row to Q and keeps its column of R.
 //
-// Offline (rom_resid_append), per basis row: CGS2 in the A_1 inner product with the dead-row rule of rom_error_curves; the
-// reduced tensor W A_q W^T and W f grown by kb_grow_ahat as in rom_greedy; the k new functionals by the per-block stencil
+// Offline (rom_resid_append), per basis row: CGS2 in the A_1 inner product with the dead-row rule (romb_a1_append); the
+// reduced tensor W A_q W^T and W f grown by kb_grow_ahat; the k new functionals by the per-block stencil
 // apply; their transform; their orthonormalisation.  The decision whether a functional adds a row is taken on the host: one
 // synchronisation per functional (the rank sizes the next products).
 // Online (rom_resid_eval): the reduced solves (rom_launch_reduced_solve on the leading n x n blocks; a dead direction has a
@@ -50,20 +50,6 @@ struct rom_resid {
 
 namespace {
 
-__global__ void kr_decide(const double* __restrict__ nrm1, const double* __restrict__ norm0, int i, int* __restrict__ dead) {
-  const double e2 = *nrm1;
-  dead[i] = (!(e2 > 1e-26 * norm0[i]) || !(e2 > 0.0)) ? 1 : 0;
-}
-
-__global__ void kr_fill(double* __restrict__ p, size_t n, double v) {
-  for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) p[i] = v;
-}
-
-__global__ void kr_eye(double* __restrict__ E, int k) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < k * k) E[i] = (i / k == i % k) ? 1.0 : 0.0;
-}
-
 // q = g / sqrt(s2)
 __global__ void kr_unit_row(double* __restrict__ q, const double* __restrict__ g, long long dim, const double* __restrict__ s2) {
   const double a = 1.0 / sqrt(*s2);
@@ -76,11 +62,6 @@ __global__ void kr_rcol(double* __restrict__ R, int ldR, int j, int rank, const 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < rank) R[size_t(i) * ldR + j] = t1[i] + t2[i];
   else if (i == rank && live) R[size_t(i) * ldR + j] = sqrt(*s2);
-}
-
-__global__ void kr_ints_to_doubles(const int* __restrict__ src, double* __restrict__ dst, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = double(src[i]);
 }
 
 // dst[(b * n + i) * n + j] = src[(b * ld + i) * ld + j]
@@ -216,8 +197,6 @@ __global__ __launch_bounds__(1024) void kr_argmax(long long M, const double* __r
   }
 }
 
-unsigned blocks_for(size_t n, int threads = 256) { return unsigned(std::max<size_t>(1, (n + threads - 1) / threads)); }
-
 int alloc(rom_ctx* ctx, size_t n, rom_buf** out) { return rom_buf_alloc(ctx, std::max<size_t>(n, 1), out); }
 
 // orthonormalise the transformed functional g (dim doubles, overwritten) against Q and append column j of R
@@ -226,7 +205,6 @@ int add_functional(rom_resid* h, double* g, int j) {
   rom_ctx* ctx = f->ctx;
   const int64_t dim = f->dim;
   const int rank = h->rank;
-  const unsigned vgrid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
   double* s = h->s->p;
   ROM_TRY(rom_launch_l2norm(ctx, g, 1, dim, s, false));
   if (rank > 0) {
@@ -242,7 +220,7 @@ int add_functional(rom_resid* h, double* g, int j) {
   ++h->syncs;
   const bool live = host[1] > RS_DROP * host[0] && host[1] > 0.0 && rank < h->rank_cap;
   if (live) {
-    kr_unit_row<<<vgrid, 256, 0, ctx->stream>>>(h->Q->p + size_t(rank) * dim, g, dim, s + 1);
+    kr_unit_row<<<vector_grid(dim), 256, 0, ctx->stream>>>(h->Q->p + size_t(rank) * dim, g, dim, s + 1);
     ROM_HIP(hipGetLastError());
   }
   kr_rcol<<<blocks_for(size_t(rank) + 1), 256, 0, ctx->stream>>>(h->R->p, h->ldR, j, rank, h->t1->p, h->t2->p, s + 1, live ? 1 : 0);
@@ -288,9 +266,8 @@ int create_body(rom_resid* h) {
   ROM_HIP(hipMemsetAsync(h->dead->p, 0, size_t(nb) * sizeof(double), ctx->stream));
   ROM_HIP(hipMemsetAsync(h->t1->p, 0, size_t(std::max(h->rank_cap, nb)) * sizeof(double), ctx->stream));
   ROM_HIP(hipMemsetAsync(h->t2->p, 0, size_t(std::max(h->rank_cap, nb)) * sizeof(double), ctx->stream));
-  kr_eye<<<blocks_for(size_t(k) * k), 256, 0, ctx->stream>>>(h->onehot->p, k);
-  kr_fill<<<unsigned(std::min<int64_t>((dim + 255) / 256, 2048)), 256, 0, ctx->stream>>>(h->Bt->p, dim, 1.0 / (double(f->N) * f->N));
-  ROM_HIP(hipGetLastError());
+  ROM_TRY(romb_onehot(ctx, k, h->onehot->p));
+  ROM_TRY(romb_load_vector(f, h->Bt->p));
   // g_0 = f
   ROM_TRY(rom_launch_sine_transform(f, h->Bt->p, 1, 0, -1, h->GH->p));
   ROM_TRY(add_functional(h, h->GH->p, 0));
@@ -360,28 +337,15 @@ extern "C" int rom_resid_append(rom_resid* h, rom_buf* C, int64_t c_row0, int ro
   const int k = h->k;
   ROM_CHECK(rows == 0 || size_t(c_row0 + rows) * dim <= C->n, "rom_resid_append: rows out of range");
   int* d_dead = reinterpret_cast<int*>(h->dead->p);
-  const unsigned vgrid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
-  double *W = h->W->p, *AW = h->AW->p, *norm0 = h->norm0->p, *nrm1 = h->nrm1->p, *nrm2 = h->nrm2->p;
+  double *W = h->W->p, *AW = h->AW->p, *norm0 = h->norm0->p;
   for (int rr = 0; rr < rows; ++rr) {
     const int i = h->n;
     double* wi = W + size_t(i) * dim;
-    // 1. w_i: CGS2 in the A_1 inner product, the sequence of rom_error_curves
+    // 1. w_i: CGS2 in the A_1 inner product
     ROM_HIP(hipMemcpyAsync(wi, C->p + (c_row0 + rr) * dim, size_t(dim) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     ROM_TRY(rom_launch_h10norm(f, wi, nullptr, 1, norm0 + i, false));
-    if (i == 0) {
-      ROM_HIP(hipMemcpyAsync(nrm1, norm0, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-      ROM_TRY(rom_launch_rowdot(ctx, AW, i, dim, wi, h->t1->p));
-      ROM_TRY(rom_launch_gemm_nn(ctx, 1, dim, i, -1.0, h->t1->p, i, W, dim, 1.0, wi, dim));
-      ROM_TRY(rom_launch_h10norm(f, wi, nullptr, 1, nrm1 + i, false));
-    }
-    kr_decide<<<1, 1, 0, ctx->stream>>>(nrm1 + i, norm0, i, d_dead);
-    ROM_HIP(hipGetLastError());
-    kb_renormalise<<<vgrid, 256, 0, ctx->stream>>>(wi, dim, nrm1 + i, d_dead, i);
-    ROM_HIP(hipGetLastError());
-    if (i > 0) ROM_TRY(romb_a1_reorth(f, W, AW, i, wi, h->t2->p, nrm2 + i, d_dead, i));
-    ROM_TRY(rom_launch_stencil_apply(f, nullptr, wi, 1, AW + size_t(i) * dim));
-    // 2. the reduced tensor and load grow by one row (rom_greedy's sequence)
+    ROM_TRY(romb_a1_append(f, W, AW, i, norm0, h->t1->p, h->t2->p, h->nrm1->p + i, h->nrm2->p + i, d_dead));
+    // 2. the reduced tensor and load grow by one row
     ROM_TRY(rom_launch_stencil_apply_blocks(f, h->onehot->p, wi, h->ZB->p));                                      // A_q w_i, all q
     ROM_TRY(rom_launch_gemm_nt(ctx, i + 1, k, dim, 1.0, W, dim, h->ZB->p, dim, 0.0, h->col->p, k, "gemm_nt"));    // w_l . A_q w_i
     kb_grow_ahat<<<blocks_for(size_t(i + 1) * k), 256, 0, ctx->stream>>>(h->Ahat->p, k, std::max(h->n_cap, 1), i, h->col->p, d_dead, i);
@@ -390,7 +354,7 @@ extern "C" int rom_resid_append(rom_resid* h, rom_buf* C, int64_t c_row0, int ro
     // 3. the k new functionals in H^-1 coordinates, orthonormalised against what is there
     ROM_TRY(rom_launch_sine_transform(f, h->ZB->p, k, 0, -1, h->GH->p));
     for (int q = 0; q < k; ++q) ROM_TRY(add_functional(h, h->GH->p + size_t(q) * dim, 1 + i * k + q));
-    kr_ints_to_doubles<<<1, 1, 0, ctx->stream>>>(d_dead + i, h->s->p + 2, 1);
+    kb_ints_to_doubles<<<1, 1, 0, ctx->stream>>>(d_dead + i, h->s->p + 2, 1);
     ROM_HIP(hipGetLastError());
     double dead = 0.0;
     ROM_TRY(download(ctx, h->s->p + 2, &dead, 1));

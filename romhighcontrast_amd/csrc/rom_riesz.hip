@@ -89,21 +89,24 @@ __global__ __launch_bounds__(256) void kr_permute(int nr, int nc, int npts, cons
 
 }  // namespace
 
-// (shared with rom_sensors.hip, declared in rom_ops.h)
+SineTables rom_sine_tables(const rom_fem* f) {
+  const double* Sr = f->d_riesz;
+  const double* Sc = Sr + size_t(f->nr) * f->nr;
+  const double* lr = Sc + size_t(f->nc) * f->nc;
+  return {Sr, Sc, lr, lr + f->nr};
+}
+
 int rom_riesz_tables(rom_fem* f) {
   if (f->d_riesz) return ROM_OK;
   rom_ctx* ctx = f->ctx;
   const size_t n = size_t(f->nr) * f->nr + size_t(f->nc) * f->nc + f->nr + f->nc;
   ROM_HIP(hipMalloc(&f->d_riesz, n * sizeof(double)));
-  double* Sr = f->d_riesz;
-  double* Sc = Sr + size_t(f->nr) * f->nr;
-  double* lr = Sc + size_t(f->nc) * f->nc;
-  double* lc = lr + f->nr;
+  const SineTables st = rom_sine_tables(f);  // (this call owns the block: the one place that writes through the pointers)
   {
     ROM_PROF(ctx, "riesz_sine", 4.0 * double(n), 8.0 * double(n));
-    kr_sine<<<unsigned((size_t(f->nr) * f->nr + 255) / 256), 256, 0, ctx->stream>>>(Sr, lr, f->nr);
+    kr_sine<<<blocks_for(size_t(f->nr) * f->nr), 256, 0, ctx->stream>>>(const_cast<double*>(st.Sr), const_cast<double*>(st.lam_r), f->nr);
     ROM_HIP(hipGetLastError());
-    kr_sine<<<unsigned((size_t(f->nc) * f->nc + 255) / 256), 256, 0, ctx->stream>>>(Sc, lc, f->nc);
+    kr_sine<<<blocks_for(size_t(f->nc) * f->nc), 256, 0, ctx->stream>>>(const_cast<double*>(st.Sc), const_cast<double*>(st.lam_c), f->nc);
     ROM_HIP(hipGetLastError());
   }
   return ROM_OK;
@@ -122,29 +125,17 @@ extern "C" int rom_riesz_h10(rom_fem* f, int npts, const int* ix_host, const int
   if (npts == 0 || (!OMEGA && !gram_host)) return ROM_OK;
   rom_ctx* ctx = f->ctx;
   ROM_TRY(rom_riesz_tables(f));
-  const double* Sr = f->d_riesz;
-  const double* Sc = Sr + size_t(nr) * nr;
-  const double* lr = Sc + size_t(nc) * nc;
-  const double* lc = lr + nr;
-
-  // the points: [ix | iy] as ints, then [tx | ty]
-  const size_t n_idx = (2 * size_t(npts) * sizeof(int) + sizeof(double) - 1) / sizeof(double);
-  Tmp pts, Gs, What, Gd;
-  ROM_TRY(pts.get(ctx, n_idx + 2 * size_t(npts)));
-  int* d_i = reinterpret_cast<int*>(pts.p());
-  double* d_t = pts.p() + n_idx;
-  ROM_HIP(hipMemcpyAsync(d_i, ix_host, npts * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  ROM_HIP(hipMemcpyAsync(d_i + npts, iy_host, npts * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  ROM_HIP(hipMemcpyAsync(d_t, tx_host, npts * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ROM_HIP(hipMemcpyAsync(d_t + npts, ty_host, npts * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-
+  const SineTables st = rom_sine_tables(f);
+  DevPoints pts;
+  ROM_TRY(pts.upload(ctx, npts, ix_host, iy_host, tx_host, ty_host));
+  Tmp Gs, What, Gd;
   const size_t block = size_t(npts) * dim;
   ROM_TRY(Gs.get(ctx, block));
   if (OMEGA) ROM_TRY(What.get(ctx, block));
   {
     const dim3 grid(unsigned((dim + 255) / 256), unsigned(std::min(npts, 65535)));
     ROM_PROF(ctx, "riesz_spectral", 8.0 * double(block), 8.0 * (OMEGA ? 2.0 : 1.0) * double(block));
-    kr_spectral<<<grid, 256, 0, ctx->stream>>>(nr, nc, npts, d_i, d_i + npts, d_t, d_t + npts, Sr, Sc, lr, lc, Gs,
+    kr_spectral<<<grid, 256, 0, ctx->stream>>>(nr, nc, npts, pts.ix, pts.iy, pts.tx, pts.ty, st.Sr, st.Sc, st.lam_r, st.lam_c, Gs,
                                                OMEGA ? What.p() : nullptr);
     ROM_HIP(hipGetLastError());
   }
@@ -157,12 +148,12 @@ extern "C" int rom_riesz_h10(rom_fem* f, int npts, const int* ix_host, const int
     // Z = S_r What: [p][i][k] into the Gs block (the Gram product has read it: same stream)
     double* Z = Gs.p();
     const int64_t wide = int64_t(npts) * nc;
-    ROM_TRY(rom_launch_gemm_nn(ctx, nr, wide, nr, 1.0, Sr, nr, What, wide, 0.0, Z, wide, nullptr, "riesz_transform_r"));
+    ROM_TRY(rom_launch_gemm_nn(ctx, nr, wide, nr, 1.0, st.Sr, nr, What, wide, 0.0, Z, wide, nullptr, "riesz_transform_r"));
     // Z S_c on the nr*npts rows of length nc: [p][i][q] into the What block
     const int64_t rows = int64_t(nr) * npts;
     for (int64_t r0 = 0; r0 < rows; r0 += RZ_MAX_ROWS) {
       const int64_t take = std::min(RZ_MAX_ROWS, rows - r0);
-      ROM_TRY(rom_launch_gemm_nn(ctx, take, nc, nc, 1.0, Z + r0 * nc, nc, Sc, nc, 0.0, What.p() + r0 * nc, nc, nullptr,
+      ROM_TRY(rom_launch_gemm_nn(ctx, take, nc, nc, 1.0, Z + r0 * nc, nc, st.Sc, nc, 0.0, What.p() + r0 * nc, nc, nullptr,
                                  "riesz_transform_c"));
     }
     {

@@ -34,8 +34,6 @@ constexpr int SG_TPB = 256;        // candidates per workgroup of the per-step p
 constexpr int SG_SELECT = 1024;    // threads of the single-workgroup argmax over the partials
 constexpr int SG_MAX_N = 128, SG_MAX_N_WORST = SE_LDS_MAX, SG_MAX_M = 1024;
 
-unsigned blocks_for(size_t n, int threads = 256) { return unsigned(std::max<size_t>(1, (n + threads - 1) / threads)); }
-
 // ---- the vertex-pair Green tables -----------------------------------------------------------------------------------
 // Linv (nr x nc), P_r^0, P_r^1 (nr x nr, ld nr; the last row of P_r^1 is 0), P_c^0, P_c^1 (nc x nc, ld nc; the last
 // column of P_c^1 is 0), in one grid-stride launch
@@ -70,10 +68,7 @@ int green_tables(rom_fem* f) {
   rom_ctx* ctx = f->ctx;
   const int nr = f->nr, nc = f->nc;
   const int64_t dim = f->dim;
-  const double* Sr = f->d_riesz;
-  const double* Sc = Sr + size_t(nr) * nr;
-  const double* lr = Sc + size_t(nc) * nc;
-  const double* lc = lr + nr;
+  const SineTables st = rom_sine_tables(f);
   double* T = nullptr;
   ROM_HIP(hipMalloc(&T, 4 * size_t(dim) * sizeof(double)));
   // (the entries past the last row / column of T_01, T_10, T_11 are never read; they are zeroed so that no table holds
@@ -91,7 +86,7 @@ int green_tables(rom_fem* f) {
   {
     const double cnt = double(dim) + double(nr) * nr + double(nc) * nc;
     ROM_PROF(ctx, "sensor_pair_factors", cnt, 8.0 * (double(dim) + 2.0 * nr * nr + 2.0 * nc * nc));
-    ks_pair_factors<<<unsigned(std::min<double>((cnt + 255) / 256, 4096.0)), 256, 0, ctx->stream>>>(nr, nc, Sr, Sc, lr, lc, Linv,
+    ks_pair_factors<<<unsigned(std::min<double>((cnt + 255) / 256, 4096.0)), 256, 0, ctx->stream>>>(nr, nc, st.Sr, st.Sc, st.lam_r, st.lam_c, Linv,
                                                                                                    Pr0, Pr1, Pc0, Pc1);
     ROM_HIP(hipGetLastError());
   }
@@ -142,36 +137,8 @@ __global__ __launch_bounds__(256) void ks_norms(int nr, int nc, int npts, const 
   if (p < npts) out[p] = point_norm2(T, nr, nc, ix[p], iy[p], tx[p], ty[p]);
 }
 
-// the points on the device: [ix | iy] as ints, then [tx | ty]
-struct DevPoints {
-  Tmp buf;
-  int* ix = nullptr;
-  int* iy = nullptr;
-  double* tx = nullptr;
-  double* ty = nullptr;
-  int upload(rom_ctx* ctx, int npts, const int* ix_host, const int* iy_host, const double* tx_host, const double* ty_host) {
-    const size_t n_idx = (2 * size_t(npts) * sizeof(int) + sizeof(double) - 1) / sizeof(double);
-    ROM_TRY(buf.get(ctx, n_idx + 2 * size_t(npts)));
-    ix = reinterpret_cast<int*>(buf.p());
-    iy = ix + npts;
-    tx = buf.p() + n_idx;
-    ty = tx + npts;
-    ROM_HIP(hipMemcpyAsync(ix, ix_host, npts * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    ROM_HIP(hipMemcpyAsync(iy, iy_host, npts * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    ROM_HIP(hipMemcpyAsync(tx, tx_host, npts * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ROM_HIP(hipMemcpyAsync(ty, ty_host, npts * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    return ROM_OK;
-  }
-};
-
 // ---- the greedy -----------------------------------------------------------------------------------------------------
 // state (ints): [0] stopped, [1] stop reason, [2] picks made; scal (doubles): [0] best criterion of step 1
-
-// the A_1-orthonormal basis: the dead-row rule of rom_error_curves (rom_curves.hip: kc_decide)
-__global__ void ks_decide(const double* __restrict__ nrm1, const double* __restrict__ norm0, int i, int* __restrict__ dead) {
-  const double e2 = *nrm1;
-  dead[i] = (!(e2 > 1e-26 * norm0[i]) || !(e2 > 0.0)) ? 1 : 0;
-}
 
 // dead count -> info; A^T A of no sensor: 0, with 2 on the diagonal of a dead direction (every eigenvalue of A^T A is at
 // most 1 -- A holds coefficients of orthonormal rows in an orthonormal basis -- so the smallest eigenvector stays in the
@@ -452,14 +419,11 @@ extern "C" int rom_sensor_greedy(rom_fem* f, rom_buf* C, int64_t c_row0, int n, 
   const int64_t dim = f->dim;
   const bool worst = mode == 1;
   ROM_TRY(green_tables(f));
-  const double* Sr = f->d_riesz;
-  const double* Sc = Sr + size_t(nr) * nr;
-  const double* lr = Sc + size_t(nc) * nc;
-  const double* lc = lr + nr;
+  const SineTables st = rom_sine_tables(f);
   DevPoints pts;
   ROM_TRY(pts.upload(ctx, ncand, ix_host, iy_host, tx_host, ty_host));
 
-  // 1. W: CGS2 in the A_1 inner product with the dead-row rule, as rom_error_curves builds it
+  // 1. W: CGS2 in the A_1 inner product with the dead-row rule
   Tmp W, AW, norm0, t1, nrm1, nrm2, dead;
   ROM_TRY(W.get(ctx, size_t(n) * dim));
   ROM_TRY(AW.get(ctx, size_t(n) * dim));
@@ -470,28 +434,12 @@ extern "C" int rom_sensor_greedy(rom_fem* f, rom_buf* C, int64_t c_row0, int n, 
   ROM_TRY(dead.get(ctx, n));  // n ints in a block of n doubles
   int* d_dead = reinterpret_cast<int*>(dead.p());
   ROM_HIP(hipMemsetAsync(dead.p(), 0, size_t(n) * sizeof(double), ctx->stream));
-  const unsigned vgrid = unsigned(std::min<int64_t>((dim + 255) / 256, 512));
   const double* c = C->p + c_row0 * dim;
   {
     ROM_PROF(ctx, "sensor_basis", 12.0 * n * n * double(dim), 48.0 * n * double(dim));
     ROM_TRY(rom_launch_h10norm(f, c, nullptr, n, norm0, false));
     ROM_HIP(hipMemcpyAsync(W.p(), c, size_t(n) * dim * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    for (int i = 0; i < n; ++i) {
-      double* wi = W.p() + size_t(i) * dim;
-      if (i == 0) {
-        ROM_HIP(hipMemcpyAsync(nrm1.p(), norm0.p(), sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      } else {
-        ROM_TRY(rom_launch_rowdot(ctx, AW, i, dim, wi, t1));
-        ROM_TRY(rom_launch_gemm_nn(ctx, 1, dim, i, -1.0, t1, i, W, dim, 1.0, wi, dim));
-        ROM_TRY(rom_launch_h10norm(f, wi, nullptr, 1, nrm1.p() + i, false));
-      }
-      ks_decide<<<1, 1, 0, ctx->stream>>>(nrm1.p() + i, norm0, i, d_dead);
-      ROM_HIP(hipGetLastError());
-      kb_renormalise<<<vgrid, 256, 0, ctx->stream>>>(wi, dim, nrm1.p() + i, d_dead, i);
-      ROM_HIP(hipGetLastError());
-      if (i > 0) ROM_TRY(romb_a1_reorth(f, W, AW, i, wi, t1, nrm2.p() + i, d_dead, i));
-      ROM_TRY(rom_launch_stencil_apply(f, nullptr, wi, 1, AW.p() + size_t(i) * dim));
-    }
+    for (int i = 0; i < n; ++i) ROM_TRY(romb_a1_append(f, W, AW, i, norm0, t1, t1, nrm1.p() + i, nrm2.p() + i, d_dead));
   }
 
   // 2. the candidates: nu (masked as they are picked), the basis values (Res at k = 0)
@@ -572,12 +520,12 @@ extern "C" int rom_sensor_greedy(rom_fem* f, rom_buf* C, int64_t c_row0, int n, 
     // the Green row g = omega_{p_k} at the candidates: one representer (spectral kernel, S_r What, (S_r What) S_c), a gather
     {
       ROM_PROF(ctx, "sensor_spectral", 8.0 * double(dim), 8.0 * double(dim));
-      ks_spectral_pick<<<blocks_for(dim), 256, 0, ctx->stream>>>(nr, nc, d_pick, k, pts.ix, pts.iy, pts.tx, pts.ty, Sr, Sc, lr, lc,
-                                                                 d_state, What);
+      ks_spectral_pick<<<blocks_for(dim), 256, 0, ctx->stream>>>(nr, nc, d_pick, k, pts.ix, pts.iy, pts.tx, pts.ty, st.Sr, st.Sc, st.lam_r,
+                                                                 st.lam_c, d_state, What);
       ROM_HIP(hipGetLastError());
     }
-    ROM_TRY(rom_launch_gemm_nn(ctx, nr, nc, nr, 1.0, Sr, nr, What, nc, 0.0, Z, nc, nullptr, "sensor_green_r"));
-    ROM_TRY(rom_launch_gemm_nn(ctx, nr, nc, nc, 1.0, Z, nc, Sc, nc, 0.0, Om, nc, nullptr, "sensor_green_c"));
+    ROM_TRY(rom_launch_gemm_nn(ctx, nr, nc, nr, 1.0, st.Sr, nr, What, nc, 0.0, Z, nc, nullptr, "sensor_green_r"));
+    ROM_TRY(rom_launch_gemm_nn(ctx, nr, nc, nc, 1.0, Z, nc, st.Sc, nc, 0.0, Om, nc, nullptr, "sensor_green_c"));
     {
       ROM_PROF(ctx, "sensor_green_eval", 8.0 * ncand, 32.0 * ncand);
       k_eval_points<<<dim3(blocks_for(ncand), 1), 256, 0, ctx->stream>>>(nr, nc, dim, Om, 1, ncand, pts.ix, pts.iy, pts.tx, pts.ty,

@@ -135,14 +135,12 @@ __global__ __launch_bounds__(256) void k_lambda_scale(int nr, int nc, long long 
 int launch_left(rom_fem* f, const double* X, int K, int pre, int post, double* OUT) {
   rom_ctx* ctx = f->ctx;
   const int nr = f->nr, nc = f->nc;
-  const double* Sr = f->d_riesz;
-  const double* lr = Sr + size_t(nr) * nr + size_t(nc) * nc;
-  const double* lc = lr + nr;
+  const SineTables st = rom_sine_tables(f);
   for (int i0 = 0; i0 < K; i0 += SP_MAX_BATCH) {
     const int take = std::min(SP_MAX_BATCH, K - i0);
     const dim3 grid(unsigned((nc + 63) / 64), unsigned((nr + 63) / 64), unsigned(take));
     ROM_PROF(ctx, "sine_transform_r", 2.0 * take * double(nr) * nr * nc, 16.0 * take * double(f->dim));
-    k_sine_left<<<grid, 256, 0, ctx->stream>>>(nr, nc, Sr, lr, lc, X + size_t(i0) * f->dim, OUT + size_t(i0) * f->dim, pre, post);
+    k_sine_left<<<grid, 256, 0, ctx->stream>>>(nr, nc, st.Sr, st.lam_r, st.lam_c, X + size_t(i0) * f->dim, OUT + size_t(i0) * f->dim, pre, post);
     ROM_HIP(hipGetLastError());
   }
   return ROM_OK;
@@ -151,7 +149,7 @@ int launch_left(rom_fem* f, const double* X, int K, int pre, int post, double* O
 int launch_right(rom_fem* f, const double* X, int K, double* OUT) {
   rom_ctx* ctx = f->ctx;
   const int nr = f->nr, nc = f->nc;
-  const double* Sc = f->d_riesz + size_t(nr) * nr;
+  const double* Sc = rom_sine_tables(f).Sc;
   const int64_t rows = int64_t(K) * nr;
   for (int64_t q0 = 0; q0 < rows; q0 += SP_MAX_ROWS) {
     const int64_t take = std::min(SP_MAX_ROWS, rows - q0);
@@ -182,11 +180,11 @@ int rom_launch_sine_transform(rom_fem* f, const double* X, int K, int pre, int p
       ROM_TRY(launch_left(f, x, take, pre, 0, T));
       ROM_TRY(launch_right(f, T, take, out));
       if (post != 0) {
-        const double* lr = f->d_riesz + size_t(f->nr) * f->nr + size_t(f->nc) * f->nc;
+        const SineTables st = rom_sine_tables(f);
         const size_t total = size_t(take) * dim;
         ROM_PROF(ctx, "sine_transform_scale", 4.0 * double(total), 16.0 * double(total));
         k_lambda_scale<<<unsigned(std::min<size_t>((total + 255) / 256, size_t(16) * 1024)), 256, 0, ctx->stream>>>(
-            f->nr, f->nc, take, lr, lr + f->nr, out, post);
+            f->nr, f->nc, take, st.lam_r, st.lam_c, out, post);
         ROM_HIP(hipGetLastError());
       }
     }
