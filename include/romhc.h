@@ -403,6 +403,44 @@ int rom_resid_eval(rom_resid* h, rom_buf* a, int64_t a_row0, int64_t M, int n, r
 int rom_weak_greedy(rom_fem* fem, rom_buf* a, int64_t M, rom_buf* weights, int n_max, double rel_tol, rom_resid* h,
                     rom_buf* BASIS, int64_t basis_row0, int64_t* picks_out, double* crit_out, double* info_host);
 
+/* ---- polynomial maps between columns of a tall block (src/experiments/NonLinearROM.py:54-70,131-139) ------------------------
+ * The least-squares fit of q target columns as polynomials of total degree <= d in m input columns over M rows: what the
+ * reference's pipelines PolynomialFeatures(d) + LinearRegression compute (src/experiments/NonLinearROM.py:54-70,131-139), in
+ * the basis of the P = C(m + d, d) products prod_j L_{alpha_j}(t_j), |alpha| <= d, of Legendre polynomials of t_j = (x_j - c_j)
+ * / h_j (c_j, h_j: mid-range and half-range of input column j over the training rows; a constant column has t_j = 0).  The
+ * same function space as scikit-learn's monomials -- the same fitted function whenever the problem has full rank -- without
+ * their conditioning: the result does not depend on the scales of the input columns.  1 <= m <= 16, 1 <= d <= 8, P <= 96,
+ * 1 <= q <= 1024, M >= 1.
+ * Method: CholeskyQR in passes over the block, Gram matrices always from the data (as rom_pca_tall): G = Psi^T Psi and
+ * B = Psi^T Y of Psi = Phi T^T by slabs of 32 rows in one MFMA kernel per pass and group of 96 target columns; pass 1 (T = I)
+ * gives the rank-revealing whitening transform of the column-normalised G (rom_small_eig_host's mode 3); a term is DROPPED
+ * there when its squared pivot is <= rcond^2 times the largest (rcond <= 0: sqrt(P eps), the noise level of a Cholesky
+ * factorisation of a Gram matrix); pass 2 has G = I + delta and W = T^T G^-1 B; a further pass only while P |delta|_max > 1/3,
+ * at most 4 passes.  When rank < P the result is a least-squares minimiser with the dropped terms' coefficients ZERO, not
+ * scikit-learn's minimum-norm one.  No floating-point atomics: the same bits on a repeated call.  NaN / Inf among the training
+ * inputs or targets are an error.  One host synchronisation per pass, one per re-whitening and one at the end. */
+typedef struct rom_poly rom_poly;
+/* (src/experiments/NonLinearROM.py:54-70,131-139) host only, no context: P = C(m+d,d) and (powers_out != NULL) the P x m
+ * exponent rows in scikit-learn's order, PolynomialFeatures(d).powers_ */
+int rom_poly_terms(int m, int d, int* P_out, int* powers_out);
+/* (src/experiments/NonLinearROM.py:54-70,131-139: model.fit) X: M rows, m columns from element x_off with row stride ldx; Y
+ * likewise (q columns).  Neither is modified.  info_host (8 doubles or NULL): P, rank, passes, |delta|_max of the accepted
+ * pass, smallest kept / largest squared pivot of pass 1, executed flops, host synchronisations, stop reason (0 full rank,
+ * 1 terms dropped, 2 pass budget reached). */
+int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q,
+                 int64_t M, int d, double rcond, rom_poly** out, double* info_host);
+/* (src/experiments/NonLinearROM.py:54-70,131-139: model.predict and the error) OUT (may be NULL) <- prediction, or Yref -
+ * prediction when Yref != NULL; sumsq_host (q, may be NULL): column sums of squares of what OUT receives (fixed-order
+ * partials).  OUT == NULL requires sumsq_host != NULL.  OUT must not overlap X.  One host synchronisation. */
+int rom_poly_predict(rom_poly* h, rom_buf* X, size_t x_off, int64_t ldx, int64_t M, rom_buf* OUT, size_t o_off, int64_t ldo,
+                     rom_buf* Yref, size_t r_off, int64_t ldr, double* sumsq_host);
+/* (src/experiments/NonLinearROM.py:54-70,131-139) out8: m, d, P, q, rank, M_train, passes, host synchronisations so far */
+int rom_poly_query(rom_poly* h, int64_t* out8);
+/* (src/experiments/NonLinearROM.py:54-70,131-139) host copies: what = 0 c (m), 1 h (m), 2 W (q x P: coefficients of the
+ * Legendre products, LinearRegression.coef_ in that basis), 3 dropped flags of pass 1 (P).  count must be the size of the part. */
+int rom_poly_download(rom_poly* h, int what, double* host, size_t count);
+int rom_poly_destroy(rom_poly* h);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

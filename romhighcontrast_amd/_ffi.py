@@ -118,6 +118,14 @@ PROTOTYPES = {
     "rom_resid_basis": (C.c_int, [_vp, _vp, C.c_int64]),
     "rom_resid_eval": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64]),
     "rom_weak_greedy": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int, C.c_double, _vp, _vp, C.c_int64, _vp, _vp, _vp]),
+    "rom_poly_terms": (C.c_int, [C.c_int, C.c_int, _vp, _vp]),
+    "rom_poly_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
+                               C.c_double, C.POINTER(_vp), _vp]),
+    "rom_poly_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
+                                   _vp]),
+    "rom_poly_query": (C.c_int, [_vp, _vp]),
+    "rom_poly_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
+    "rom_poly_destroy": (C.c_int, [_vp]),
     "rom_comm_unique_id": (C.c_int, [C.c_char_p, C.c_size_t]),
     "rom_comm_init": (C.c_int, [_vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int]),
     "rom_comm_destroy": (C.c_int, [_vp]),
@@ -309,6 +317,11 @@ class Context:
                  worst_ratio=float(info[4]), stop_reason=("converged", "budget")[int(info[5])], host_syncs=int(info[6]))
         return sigma[:n], d
 
+    def poly_fit(self, X: "Buffer", x_off, ldx, m, Y: "Buffer", y_off, ldy, q, M, degree, rcond=0.0) -> "PolyMap":
+        """rom_poly_fit: the least-squares polynomial map of total degree <= ``degree`` from the m columns of X (from element
+        x_off, row stride ldx) to the q columns of Y over M rows.  Neither block is modified.  Returns the PolyMap."""
+        return PolyMap(self, X, x_off, ldx, m, Y, y_off, ldy, q, M, degree, rcond)
+
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):
         check(self.lib.rom_symmetric_orthonormalize(self.h, V.h, v_row0, n, dim))
 
@@ -353,6 +366,16 @@ class Context:
         v = _host(np.atleast_1d(vals)).copy()
         check(self.lib.rom_comm_allreduce_host(self.h, v.ctypes.data, v.size, 1 if op == "max" else 0))
         return v
+
+
+def poly_terms(m: int, degree: int) -> np.ndarray:
+    """rom_poly_terms: the (P, m) exponent rows of the feature space, PolynomialFeatures(degree).powers_ (host only)."""
+    lib = load_library()
+    P = C.c_int(0)
+    check(lib.rom_poly_terms(int(m), int(degree), C.byref(P), None))
+    powers = np.zeros((P.value, int(m)), dtype=np.int32)
+    check(lib.rom_poly_terms(int(m), int(degree), C.byref(P), powers.ctypes.data))
+    return powers
 
 
 def _pod_info(info) -> dict:
@@ -416,6 +439,60 @@ class Buffer:
     def free(self):
         if getattr(self, "h", None) is not None and self.h:
             self.ctx.lib.rom_buf_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PolyMap:
+    """Handle of a fitted polynomial map (rom_poly_*): owns the device coefficients, destroyed on collection."""
+
+    _PARTS = {"c": 0, "h": 1, "W": 2, "dropped": 3}
+
+    def __init__(self, ctx: Context, X: Buffer, x_off, ldx, m, Y: Buffer, y_off, ldy, q, M, degree, rcond=0.0):
+        self.ctx = ctx
+        self.h = None
+        h, info = _vp(), np.zeros(8)
+        check(ctx.lib.rom_poly_fit(ctx.h, X.h if X is not None else None, int(x_off), int(ldx), int(m),
+                                   Y.h if Y is not None else None, int(y_off), int(ldy), int(q), int(M), int(degree), float(rcond),
+                                   C.byref(h), info.ctypes.data))
+        self.h = h
+        self.m, self.q, self.degree = int(m), int(q), int(degree)
+        self.info = dict(P=int(info[0]), rank=int(info[1]), passes=int(info[2]), delta_max=float(info[3]),
+                         pivot_ratio=float(info[4]), executed_flops=float(info[5]), host_syncs=int(info[6]),
+                         stop_reason=("full_rank", "terms_dropped", "budget")[int(info[7])])
+
+    def query(self) -> dict:
+        out = np.zeros(8, dtype=np.int64)
+        check(self.ctx.lib.rom_poly_query(self.h, out.ctypes.data))
+        keys = ("m", "d", "P", "q", "rank", "M_train", "passes", "host_syncs")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def download(self, part: str) -> np.ndarray:
+        """Host copy of "c" (m,), "h" (m,), "W" (q, P) or the "dropped" flags (P,)."""
+        P = self.info["P"]
+        out = np.zeros({"c": (self.m,), "h": (self.m,), "W": (self.q, P), "dropped": (P,)}[part])
+        check(self.ctx.lib.rom_poly_download(self.h, self._PARTS[part], out.ctypes.data, out.size))
+        return out
+
+    def predict(self, X: Buffer, x_off, ldx, M, OUT: "Buffer | None" = None, o_off=0, ldo=None, Yref: "Buffer | None" = None, r_off=0,
+                ldr=None, sumsq=False):
+        """rom_poly_predict: OUT <- the prediction for the M rows of X, or Yref - prediction; with ``sumsq`` returns the q
+        column sums of squares of that (OUT may then be None: nothing of size M x q is written)."""
+        ss = np.zeros(self.q) if sumsq else None
+        check(self.ctx.lib.rom_poly_predict(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M),
+                                            OUT.h if OUT is not None else None, int(o_off), int(self.q if ldo is None else ldo),
+                                            Yref.h if Yref is not None else None, int(r_off), int(self.q if ldr is None else ldr),
+                                            ss.ctypes.data if sumsq else None))
+        return ss
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.rom_poly_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -93,6 +93,7 @@ struct rom_ctx {
   // read the difference
   unsigned long long host_syncs = 0;
   bool lds_optin_reduced_solve = false, lds_optin_small_eig = false, lds_optin_pivchol = false, lds_optin_pca_tall = false;
+  bool lds_optin_poly_pass = false, lds_optin_poly_predict = false;
 };
 
 struct rom_buf {

@@ -1,8 +1,10 @@
 """The device-independent parts of the reference's second experiment, src/experiments/NonLinearROM.py ("learn the higher
 PCA coordinates of a solution from its leading ones"): the parameter sweep, the full PCA of the tall snapshot block and
 the index bookkeeping of the regression experiments.  The sweep runs on the device (SolutionsManagerFEM) and the PCA is
-``pca_tall`` (rom_pca_tall: 25,000 x 81 is M >> dim, the shape rom_pod was not designed for).  The plots and the
-PerplexityLab LabPipeline driver of the reference are out of scope.
+``pca_tall`` (rom_pca_tall: 25,000 x 81 is M >> dim, the shape rom_pod was not designed for).  The polynomial regressions
+of the third stage have a device path as well (``PolynomialMap``, ``learn_eigenvalues_device``, ``nonlinear_reconstruction``:
+rom_poly_fit / rom_poly_predict); trees, forests and MLPs stay scikit-learn's.  The plots and the PerplexityLab LabPipeline
+driver of the reference are out of scope.
 """
 from __future__ import annotations
 
@@ -11,10 +13,10 @@ from collections import namedtuple
 import numpy as np
 
 from .lib.ReducedBasis import pca_tall
-from .lib.SolutionsManagers import SolutionsManagerFEM
+from .lib.SolutionsManagers import DeviceArray, SolutionsManagerFEM
 
 __all__ = ["ZERO", "Bounds", "MWhere", "draw_parameters", "vn_family_sampler", "do_pca", "get_known_unknown_indexes",
-           "learn_eigenvalues"]
+           "learn_eigenvalues", "PolynomialMap", "learn_eigenvalues_device", "nonlinear_reconstruction"]
 
 ZERO = 1e-15
 Bounds = namedtuple("Bounds", "lower upper")
@@ -79,3 +81,135 @@ def learn_eigenvalues(model):
 
     experiment.__name__ = " ".join(step[0] for step in model.steps)
     return experiment
+
+
+# ---- the regression stage on the device: rom_poly_fit / rom_poly_predict --------------------------------------------------
+
+
+def _contiguous_ranges(idx):
+    """[a, a+1, .., b-1, c, c+1, ...] -> [(a, b), (c, ...)]: the runs of consecutive column indices, in order."""
+    idx = [int(i) for i in idx]
+    runs = []
+    for i in idx:
+        if runs and runs[-1][1] == i:
+            runs[-1][1] = i + 1
+        else:
+            runs.append([i, i + 1])
+    return [tuple(r) for r in runs]
+
+
+class PolynomialMap:
+    """(:131-139) ``Pipeline([PolynomialFeatures(degree), LinearRegression()])`` as one device fit (rom_poly_fit): the
+    least-squares polynomial of total degree <= ``degree`` in a basis of scaled Legendre products, by a CholeskyQR whose
+    Gram matrices come from the data.  Same function space as the scikit-learn pipeline -- the same predictions whenever
+    the problem has full rank -- independent of the scales of the input columns.  ``fit`` / ``predict`` follow
+    scikit-learn's protocol on host arrays or DeviceArrays (``predict`` returns what it was given: a host array for a host
+    array); ``steps`` lets ``learn_eigenvalues(model)`` take it unchanged.  ``info_`` is the PolyMap's info dict."""
+
+    def __init__(self, degree, rcond=0.0, ctx=None):
+        self.degree, self.rcond, self._ctx = int(degree), float(rcond), ctx
+        # (the reference's names, :131-139: "LR", "Quadratic LR", "Degree 4 LR")
+        first = [] if self.degree == 1 else [("Quadratic" if self.degree == 2 else f"Degree {self.degree}", None)]
+        self.steps = first + [("LR device", self)]
+        self.map_ = None
+
+    def _context(self):
+        from . import _ffi
+        if self._ctx is None:
+            self._ctx = _ffi.get_context()
+        return self._ctx
+
+    def _device(self, A):
+        if isinstance(A, DeviceArray):
+            return A
+        arr = np.asarray(A, dtype=np.float64)
+        arr = arr.reshape(-1, 1) if arr.ndim == 1 else arr
+        arr = np.ascontiguousarray(arr)
+        return DeviceArray(self._context().upload(arr), arr.shape[0], arr.shape[1])
+
+    def fit(self, X, y):
+        Xd, Yd = self._device(X), self._device(y)
+        assert Xd.rows == Yd.rows, "PolynomialMap.fit: X and y have different numbers of rows"
+        return self.fit_columns(Xd, (0, Xd.dim), Yd, (0, Yd.dim), 0, Xd.rows)
+
+    def fit_columns(self, Xd, xcols, Yd, ycols, row0, rows):
+        """Fit on rows [row0, row0 + rows) of the column ranges xcols = (lo, hi) of Xd and ycols of Yd (DeviceArrays; they
+        may be the same block): nothing is copied."""
+        from . import _ffi
+        try:
+            self.map_ = self._context().poly_fit(Xd.buf, row0 * Xd.dim + xcols[0], Xd.dim, xcols[1] - xcols[0], Yd.buf,
+                                                 row0 * Yd.dim + ycols[0], Yd.dim, ycols[1] - ycols[0], rows, self.degree, self.rcond)
+        except _ffi.RomLibraryError as e:
+            if "NaN / Inf" in str(e):   # (scikit-learn's estimators raise ValueError on such input)
+                raise ValueError(str(e)) from None
+            raise
+        self.info_ = self.map_.info
+        return self
+
+    def predict(self, X):
+        assert self.map_ is not None, "PolynomialMap.predict before fit"
+        Xd = self._device(X)
+        out = self._context().alloc(max(Xd.rows * self.map_.q, 1))
+        self.map_.predict(Xd.buf, 0, Xd.dim, Xd.rows, OUT=out)
+        res = DeviceArray(out, Xd.rows, self.map_.q)
+        return res if isinstance(X, DeviceArray) else res.numpy()
+
+
+def learn_eigenvalues_device(degree, rcond=0.0, ctx=None):
+    """(:54-70) ``learn_eigenvalues`` with the device fit: the same experiment function, but ``pca_projections`` is the
+    DeviceArray of scores (``pca_tall(..., download=False).scores``) and nothing of size (rows, modes) comes to the host
+    except the (n_test, unknown) errors.  Fit on rows [n_test, n_test + n_train), predict rows [0, n_test).  A
+    non-contiguous unknown list (``learn_higher_modes_only=False``) is fitted as its contiguous ranges.  Returns
+    ``{"error": ..., "rmse": ...}``: ``rmse`` per unknown mode from the device's column sums of squares."""
+
+    def experiment(n_train, n_test, pca_projections, mwhere: MWhere, only_j, learn_higher_modes_only=True):
+        from . import _ffi
+        S = pca_projections
+        assert isinstance(S, DeviceArray), "learn_eigenvalues_device: the scores as a DeviceArray"
+        c = _ffi.get_context() if ctx is None else ctx
+        known, unknown = get_known_unknown_indexes(mwhere, np.empty((0, S.dim)), learn_higher_modes_only, only_j)
+        errors, rmse = [], []
+        for lo, hi in _contiguous_ranges(unknown):
+            model = PolynomialMap(degree, rcond, c).fit_columns(S, (int(known[0]), int(known[-1]) + 1), S, (lo, hi), n_test, n_train)
+            E = c.alloc(max(n_test * (hi - lo), 1))
+            ss = model.map_.predict(S.buf, int(known[0]), S.dim, n_test, OUT=E, Yref=S.buf, r_off=lo, ldr=S.dim, sumsq=True)
+            errors.append(E.download(n_test * (hi - lo), shape=(n_test, hi - lo)))
+            rmse.append(np.sqrt(ss / n_test))
+        if not errors:
+            return {"error": np.zeros((n_test, 0)), "rmse": np.zeros(0)}
+        return {"error": np.hstack(errors), "rmse": np.concatenate(rmse)}
+
+    experiment.__name__ = " ".join(step[0] for step in PolynomialMap(degree).steps)
+    return experiment
+
+
+def nonlinear_reconstruction(pca, poly, known_scores, known_start=0, unknown_start=None, download=True):
+    """The reduced model the fitted map defines: u = mean + known scores . their components + predicted scores . theirs.
+    ``pca``: a TallPCA; ``poly``: a fitted PolynomialMap (or PolyMap) from m known to q unknown score columns;
+    ``known_scores``: (K, m) host array or DeviceArray; the known columns are the components [known_start, known_start + m)
+    and the predicted ones [unknown_start, unknown_start + q) (default: right after the known ones).  Two rom_gemm_nn
+    products on the device."""
+    from . import _ffi
+    pm = poly.map_ if isinstance(poly, PolynomialMap) else poly
+    ctx = pm.ctx
+    m, q = pm.m, pm.q
+    unknown_start = known_start + m if unknown_start is None else int(unknown_start)
+    if isinstance(known_scores, DeviceArray):
+        Kd = known_scores
+    else:
+        arr = np.ascontiguousarray(np.asarray(known_scores, dtype=np.float64)).reshape(-1, m)
+        Kd = DeviceArray(ctx.upload(arr), arr.shape[0], m)
+    assert Kd.dim == m, "nonlinear_reconstruction: known_scores must have the map's m columns"
+    K = Kd.rows
+    comps = pca.components_
+    Vd = comps if isinstance(comps, DeviceArray) else DeviceArray(ctx.upload(np.asarray(comps, dtype=np.float64)), *np.shape(comps))
+    dim = Vd.dim
+    assert known_start + m <= Vd.rows and unknown_start + q <= Vd.rows, "nonlinear_reconstruction: components out of range"
+    mean = pca.mean_.numpy().ravel() if isinstance(pca.mean_, DeviceArray) else np.asarray(pca.mean_, dtype=np.float64).ravel()
+    pred = ctx.alloc(max(K * q, 1))
+    pm.predict(Kd.buf, 0, m, K, OUT=pred)
+    U = ctx.upload(np.tile(mean, (K, 1)))
+    ctx.gemm_nn(K, dim, m, Kd.buf, 0, m, Vd.buf, known_start * dim, dim, U, 0, dim, alpha=1.0, beta=1.0)
+    ctx.gemm_nn(K, dim, q, pred, 0, q, Vd.buf, unknown_start * dim, dim, U, 0, dim, alpha=1.0, beta=1.0)
+    out = DeviceArray(U, K, dim)
+    return out.numpy() if download else out
