@@ -162,10 +162,23 @@ __device__ inline void expand_tile(const FemDev& f, int Mc, double* __restrict__
   const int mA = by * 64 + srow;
   const double* pA = mA < Mc ? f.y + size_t(mA) * f.nGp + ee.zpos + sseg : nullptr;
   const double* pB = f.P + (size_t(ee.ptab) * f.n1p + bx * 64 + srow) * f.n1p + sseg;
+  // The rank is rounded up to whole chunks: the last chunk of the last edge group of the reduced part can reach past
+  // it (by `kover` < BK entries), into the nodal part -- an OUTPUT of this stage: another workgroup may be writing it, and
+  // whatever an earlier sweep or the caller left there (NaN after a failed sweep) must not count, not even against the zero
+  // table columns it meets.  (kover and ch are the same for the whole workgroup: a scalar branch, taken by one chunk of one edge.)
+  const int kover = ee.zpos < f.nGa ? max(ee.zpos + ee.nch * BK - f.nGa, 0) : 0;
   Acc acc;
   acc_zero(acc);
   gemm_loop(
-      ee.nch, [&](int ch, double* v) { load4_any(pA ? pA + ch * BK : nullptr, v); },
+      ee.nch,
+      [&](int ch, double* v) {
+        load4_any(pA ? pA + ch * BK : nullptr, v);
+        if (kover > 0 && ch == ee.nch - 1) {
+#pragma unroll
+          for (int x = 0; x < 4; ++x)
+            if (sseg + x >= BK - kover) v[x] = 0.0;
+        }
+      },
       [&](int ch, double* v) { load4_aligned(pB + ch * BK, v); }, acc, lds, wp);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
