@@ -54,6 +54,41 @@ __global__ void kb_ints_to_doubles(const int* __restrict__ src, double* __restri
   if (i < n) dst[i] = double(src[i]);
 }
 
+// ---- fixed-order sums of per-chunk partials (no floating-point atomics: the same bits on every call) -----------------
+// Part[chunk] is ppad x ldp: a lower triangle in its leading columns and a rectangle from column ppad on.
+// G[r][c] (P x P, with G != NULL) = sum over the chunks, in chunk order, of Part[chunk][max(r, c)][min(r, c)]: the reduction
+// and the mirror in one; B[r][c0 + c] (P x q) = the same sum of Part[chunk][r][ppad + c], c < qg
+__global__ void kb_partials_reduce(const double* __restrict__ Part, int chunks, int ppad, int ldp, int P, int qg,
+                                   double* __restrict__ G, double* __restrict__ B, int q, int c0) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ng = G ? P * P : 0;
+  if (idx >= ng + P * qg) return;
+  const size_t step = size_t(ppad) * ldp;
+  const double* p;
+  double* out;
+  if (idx < ng) {
+    const int r = idx / P, c = idx - r * P;
+    p = Part + size_t(max(r, c)) * ldp + min(r, c);
+    out = G + idx;
+  } else {
+    const int e = idx - ng, r = e / qg, c = e - r * qg;
+    p = Part + size_t(r) * ldp + ppad + c;
+    out = B + size_t(r) * q + c0 + c;
+  }
+  double s = 0.0;
+  for (int ch = 0; ch < chunks; ++ch) s += p[ch * step];
+  *out = s;
+}
+
+// out[j] = (sum over the chunks, in chunk order, of part[chunk][j]) / divisor, j < n (a plain sum: divisor = 1, exact)
+__global__ void kb_partials_colsum(const double* __restrict__ part, int chunks, int n, double divisor, double* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  double s = 0.0;
+  for (int ch = 0; ch < chunks; ++ch) s += part[size_t(ch) * n + j];
+  out[j] = s / divisor;
+}
+
 // counter-based generator (splitmix64 of seed and index): the same numbers whatever the launch shape
 __device__ inline unsigned long long mix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -649,11 +684,8 @@ int romb_pivchol_whiten(rom_ctx* ctx, int n, const double* A, int lda, double* l
   }
   const int ld = n | 1;
   const size_t lds = 2 * size_t(n) * ld * sizeof(double) + 4 * sizeof(double) + (4 + size_t(n)) * sizeof(int) + 16;
-  if (lds > 64 * 1024 && !ctx->lds_optin_pivchol) {
-    ROM_HIP(hipSetDevice(ctx->device));
-    ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kb_pivchol_whiten), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    ctx->lds_optin_pivchol = true;
-  }
+  if (lds > 64 * 1024)
+    ROM_TRY(rom_lds_optin(ctx->lds_optin_pivchol, reinterpret_cast<const void*>(kb_pivchol_whiten), 160 * 1024 - 256, ctx->device));
   {
     ROM_PROF(ctx, "pivchol_whiten", 1.0 * n * n * n, 16.0 * n * n);
     kb_pivchol_whiten<<<1, 256, lds, ctx->stream>>>(n, A, lda, lam, T, ldt, rel_tol);
@@ -869,15 +901,11 @@ int romb_small_eig(rom_ctx* ctx, int n, const double* A, int lda, double* lam, d
   size_t lds = vec + 16 + 2 * size_t(n) * ld * sizeof(double);   // (n <= SE_LDS_MAX here: matrix + eigenvector rows in LDS)
   double* ns_ws = nullptr;
   ROM_TRY(rom_ctx_scratch(ctx, 2 * size_t(n) * n, &ns_ws));   // Newton-Schulz fast path: next iterates
-  if (lds > 64 * 1024 && !ctx->lds_optin_small_eig) {
-    ROM_HIP(hipSetDevice(ctx->device));
-    ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kb_small_eig<512, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ctx->lds_optin_small_eig = true;
-  }
+  if (lds > 64 * 1024)
+    ROM_TRY(rom_lds_optin(ctx->lds_optin_small_eig, reinterpret_cast<const void*>(kb_small_eig<512, false>), 160 * 1024, ctx->device));
   {
-    static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;  // per-shape names in the profile records
     char nm[48];
-    detail ? snprintf(nm, sizeof nm, "small_eig_n%d_mode%d_%s", n, mode, gram_like ? "gram" : "sym") : snprintf(nm, sizeof nm, "small_eig");
+    rom_prof_name(nm, sizeof nm, "small_eig", "_n%d_mode%d_%s", n, mode, gram_like ? "gram" : "sym");
     ROM_PROF(ctx, nm, 30.0 * n * n * n, 16.0 * n * n);
     // n <= 32: ONE wave -- no barrier between the phases of a round and the item map divided out once: 5x the rounds per
     // microsecond of the 512-thread form on the same rotations (same results)

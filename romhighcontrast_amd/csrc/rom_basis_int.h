@@ -84,6 +84,11 @@ int romb_load_vector(rom_fem* f, double* out);
 // dst (cols x rows, ld ldd) = transpose of src (rows x cols, ld lds): small matrices only
 int romb_transpose(rom_ctx* ctx, double* dst, long long ldd, const double* src, long long lds, int rows, int cols);
 __global__ void kb_ints_to_doubles(const int* __restrict__ src, double* __restrict__ dst, int n);
+// fixed-order sums of per-chunk partials: G (mirrored lower triangle, or NULL) and the rectangle B of Part[chunk] (ppad x ldp);
+// out[j] = (column sum of part[chunk][j] over the chunks) / divisor
+__global__ void kb_partials_reduce(const double* __restrict__ Part, int chunks, int ppad, int ldp, int P, int qg,
+                                   double* __restrict__ G, double* __restrict__ B, int q, int c0);
+__global__ void kb_partials_colsum(const double* __restrict__ part, int chunks, int n, double divisor, double* __restrict__ out);
 // (rom_pod.hip) out[0] = bits of the largest |x| among the finite entries, out[1] = number of entries that are not finite
 __global__ void kp_block_amax(const double* __restrict__ X, size_t count, unsigned long long* __restrict__ out);
 

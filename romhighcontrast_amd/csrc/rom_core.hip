@@ -192,6 +192,39 @@ ProfScope::~ProfScope() {
   if (idx >= 0) hipEventRecord(ctx->prof_recs[idx].e1, ctx->prof_recs[idx].st);
 }
 
+bool rom_prof_detail() {
+  static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;
+  return detail;
+}
+
+void rom_prof_name(char* nm, size_t cap, const char* base, const char* suffix_fmt, ...) {
+  const int at = snprintf(nm, cap, "%s", base);
+  if (!rom_prof_detail() || at < 0 || size_t(at) >= cap) return;
+  va_list ap;
+  va_start(ap, suffix_fmt);
+  vsnprintf(nm + at, cap - size_t(at), suffix_fmt, ap);
+  va_end(ap);
+}
+
+// ---- launch plans and attributes shared by the kernels' hosts ------------------------------------
+int rom_lds_optin(bool& done, const void* kernel, int bytes, int device) {
+  if (done) return ROM_OK;
+  if (device >= 0) ROM_HIP(hipSetDevice(device));
+  ROM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done = true;
+  return ROM_OK;
+}
+
+SlabPlan rom_slab_plan(const rom_ctx* ctx, long long M, int n) {
+  SlabPlan p;
+  const long long n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+  const long long nslabs = (M + SLAB_ROWS - 1) / SLAB_ROWS;
+  p.pad = (n + 15) / 16 * 16;
+  p.per_chunk = (nslabs + n_cu - 1) / n_cu;
+  p.chunks = int((nslabs + p.per_chunk - 1) / p.per_chunk);
+  return p;
+}
+
 extern "C" int rom_profile_enable(rom_ctx* c, int on) {
   ROM_CHECK(c, "null context");
   c->profile = on != 0;

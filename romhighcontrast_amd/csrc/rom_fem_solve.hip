@@ -106,8 +106,7 @@ static int enqueue_solve(rom_fem* f, const FemDev& d, const double* am, int Mc, 
                          hipStream_t st, size_t lds_back, int stages) {
   rom_ctx* ctx = f->ctx;
   const int kblk = f->nrb * f->ncb;
-  static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;  // per-column kernel names
-  char nm[4][48];
+  char nm[4][48];  // (per-column kernel names under ROMHC_PROF_DETAIL)
   const bool fused1 = f->fused1 && !f->sw_no_fused;  // the whole reduced solve in one wave-per-system kernel
   if (f->nGp > 0 && fused1 && (stages & 1)) {
     ROM_PROF(ctx, "solve1", Mc * (262144 / 3.0 + 3 * 4096.0), Mc * 8.0 * 4096 * 3);
@@ -123,7 +122,7 @@ static int enqueue_solve(rom_fem* f, const FemDev& d, const double* am, int Mc, 
         int slot = f->diag_slot[j];
         double nk = f->kptr[slot + 1] - f->kptr[slot];
         const char* base[4] = {"diag_update", "diag_factor", "", "factor_panel"};
-        for (int q = 0; q < 4; ++q) detail ? snprintf(nm[q], 48, "%s_j%02d", base[q], j) : snprintf(nm[q], 48, "%s", base[q]);
+        for (int q = 0; q < 4; ++q) rom_prof_name(nm[q], 48, base[q], "_j%02d", j);
         {
           ROM_PROF(ctx, nm[0], Mc * nk * 2.0 * 262144, Mc * 8.0 * 4096 * (1 + 2 * nk));
           // (two systems per workgroup share one pass over the term tables: -20 % at 1024 systems, nothing at 4096)
@@ -151,10 +150,8 @@ static int enqueue_solve(rom_fem* f, const FemDev& d, const double* am, int Mc, 
       ROM_PROF(ctx, "coef", 0, 8.0 * Mc * f->ncoef);
       // the nGa reduced unknowns + 8 dot products per closed-form entry (those in HBM where they outgrow the LDS: d.gdots)
       const size_t lds_coef = d.gdots ? lds_back : lds_back + size_t(f->ncf) * 64;
-      if (lds_coef > 48 * 1024 && !f->lds_optin_coef) {  // (the attribute belongs to the kernel as loaded on this device)
-        ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_coef), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        f->lds_optin_coef = true;
-      }
+      if (lds_coef > 48 * 1024)  // (the attribute belongs to the kernel as loaded on this device)
+        ROM_TRY(rom_lds_optin(f->lds_optin_coef, reinterpret_cast<const void*>(k_coef), 156 * 1024));
       k_coef<<<Mc, 1024, lds_coef, st>>>(d, am);
     }
   }

@@ -192,10 +192,8 @@ static int launch_gemm_nt_thin(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, do
   ROM_TRY(rom_ctx_scratch(ctx, size_t(splits) * m * n, &part));
   const dim3 grid{unsigned(tiles), 1u, unsigned(splits)};
   {
-    static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;
     char nm[64];
-    detail ? snprintf(nm, sizeof nm, "%s_thin_%lldx%lldx%lld_s%lld", prof_name, (long long)m, (long long)n, (long long)k, splits)
-           : snprintf(nm, sizeof nm, "%s", prof_name);
+    rom_prof_name(nm, sizeof nm, prof_name, "_thin_%lldx%lldx%lld_s%lld", (long long)m, (long long)n, (long long)k, splits);
     ROM_PROF(ctx, nm, 2.0 * m * n * k, 8.0 * (double(m) * k + double(n) * k + double(splits) * m * n));
     switch ((m + 15) / 16) {
       case 1: k_gemm_nt_thin<1><<<grid, 256, 0, ctx->stream>>>(m, n, k, kper, A, lda, B, ldb, part); break;
@@ -258,10 +256,8 @@ int rom_launch_gemm_nt_ex(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double 
   dim3 grid(unsigned((n + 63) / 64), unsigned((m + 63) / 64), unsigned(splits));
   if (lower_only) grid = dim3(unsigned(tiles), 1, unsigned(splits));
   {
-    static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;  // per-shape names in the profile records
     char nm[64];
-    detail ? snprintf(nm, sizeof nm, "%s_%lldx%lldx%lld_s%d", prof_name, (long long)m, (long long)n, (long long)k, splits)
-           : snprintf(nm, sizeof nm, "%s", prof_name);
+    rom_prof_name(nm, sizeof nm, prof_name, "_%lldx%lldx%lld_s%d", (long long)m, (long long)n, (long long)k, splits);
     ROM_PROF(ctx, nm, (lower_only ? 1.0 : 2.0) * m * n * k + (lower_only ? 64.0 * n * k : 0.0),
              8.0 * (double(m) * k + double(n) * k + double(m) * n));
     if (aligned)
@@ -872,13 +868,11 @@ int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alp
                        const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* part_ws,
                        const char* prof_name) {
   if (m <= 0 || n <= 0) return ROM_OK;
-  static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;  // per-shape names in the profile records
   if (gemm_nn_thin(m, n, k, lda, ldb)) {
     // thin A against the rows of a snapshot-wide B; or a tall A with a short K (the lift: output bound), in row tiles of 64
     char nm[64];
-    prof_name ? snprintf(nm, sizeof nm, "%s", prof_name)
-    : detail  ? snprintf(nm, sizeof nm, "gemm_nn_thin_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k)
-              : snprintf(nm, sizeof nm, "gemm_nn");
+    if (prof_name) snprintf(nm, sizeof nm, "%s", prof_name);
+    else rom_prof_name(nm, sizeof nm, "gemm_nn", "_thin_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k);
     ROM_PROF(ctx, nm, 2.0 * m * n * k, 8.0 * (double(m) * k + double(n) * k + double(m) * n));
     const dim3 grid{unsigned((n + 127) / 128), unsigned((m + 63) / 64)};
     switch (m > 64 ? 4 : (m + 15) / 16) {
@@ -901,9 +895,8 @@ int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alp
   }
   {
     char nm[64];
-    prof_name ? snprintf(nm, sizeof nm, "%s", prof_name)
-    : detail  ? snprintf(nm, sizeof nm, "gemm_nn_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k)
-              : snprintf(nm, sizeof nm, "gemm_nn");
+    if (prof_name) snprintf(nm, sizeof nm, "%s", prof_name);
+    else rom_prof_name(nm, sizeof nm, "gemm_nn", "_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k);
     ROM_PROF(ctx, nm, 2.0 * m * n * k, 8.0 * (double(m) * k + double(n) * k + double(m) * n));
     k_gemm_nn<<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, kper, part);
   }
@@ -1321,14 +1314,8 @@ int rom_launch_reduced_solve(rom_ctx* ctx, int n, int ldA, int kb, int M, const 
   const size_t mat = size_t(n) * (n + 1) * sizeof(double), vecs = 2 * size_t(n) * sizeof(double);
   const bool in_lds = mat + vecs <= size_t(REDUCED_LDS_MAX);
   const size_t lds = in_lds ? mat + vecs : vecs;
-  if (lds > size_t(REDUCED_LDS_DEFAULT)) {
-    if (!ctx->lds_optin_reduced_solve) {  // once per device: the attribute belongs to the kernel as loaded on THIS device
-      ROM_HIP(hipSetDevice(ctx->device));
-      ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_reduced_solve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  REDUCED_LDS_MAX));
-      ctx->lds_optin_reduced_solve = true;
-    }
-  }
+  if (lds > size_t(REDUCED_LDS_DEFAULT))  // once per device: the attribute belongs to the kernel as loaded on THIS device
+    ROM_TRY(rom_lds_optin(ctx->lds_optin_reduced_solve, reinterpret_cast<const void*>(k_reduced_solve), REDUCED_LDS_MAX, ctx->device));
   // matrices beyond the LDS: slabs of the scratch block, as many systems per launch as 1 GiB of it holds
   const int per_launch = in_lds ? M : int(std::max<size_t>(1, std::min<size_t>(size_t(M), (size_t(1) << 30) / mat)));
   double* gws = nullptr;

@@ -10,33 +10,25 @@
 // |a_pq| <= tol sqrt(a_pp a_qq) delivers its small eigenvalues to high relative accuracy: no sqrt(eps) floor as in the
 // one-pass covariance route.  G always comes from the data (never as V C V^T): that is what carries the accuracy.
 //
-// Kernels: k_pca_tall_fused (dim <= 96: V and 32-row slabs of X and Y in LDS; rotation and Y^T Y on MFMA in one pass over
-// the block, scores written from the same slab), k_syrk_tn (any dim: G = Y^T Y of a row-major block, the TN product the
-// NT / NN engines of rom_mma.h do not have), both with per-chunk partial sums that k_syrk_reduce adds in a fixed order (no
-// floating-point atomics: the same bits on every call).
+// Kernels: k_pca_tall_fused (dim <= 96: the slab engine of rom_slab.h, rotation and Y^T Y in one pass over the block, scores
+// written from the same slab), k_syrk_tn (any dim: G = Y^T Y of a row-major block, the TN product the NT / NN engines of
+// rom_mma.h do not have), both with per-chunk partial sums that kb_partials_reduce adds in a fixed order (no floating-point
+// atomics: the same bits on every call).
 #include <cmath>
 #include <cstring>
 #include <numeric>
 
 #include "rom_basis_int.h"
-#include "rom_mma.h"
+#include "rom_slab.h"
 
 namespace {
 
 constexpr int PT_FUSED_MAX = 96;   // largest dim of the fused kernel (V + two slabs in 160 KB of LDS)
-constexpr int PT_ROWS = 32;        // rows of a slab
-constexpr int PT_THREADS = 512;    // 8 waves: one workgroup per CU (LDS), two waves per SIMD
-constexpr int PT_XREG = PT_ROWS * PT_FUSED_MAX / PT_THREADS;   // doubles of a slab per thread
+constexpr int PT_XREG = SLAB_ROWS * PT_FUSED_MAX / SLAB_THREADS;   // doubles of a slab per thread
 constexpr int PT_PASS_CAP = 6;
 constexpr double PT_EPS = 1.1102230246251565e-16;   // 2^-53
 constexpr double PT_C = 64.0;
 constexpr double PT_NOISE_FLOOR = 1e-13;
-
-// LDS row strides (doubles).  An NT operand read (lane -> row l & 15, k = l >> 4) wants rows 4 banks apart: stride = 2 mod 4
-// doubles.  A TN operand read (lane -> column l & 15, row k = l >> 4: 16 consecutive doubles of four rows) wants
-// consecutive rows half the banks apart: stride = 16 mod 32 doubles.
-__host__ __device__ inline int pt_ld_nt(int dpad) { return dpad + 2; }
-__host__ __device__ inline int pt_ld_tn(int dpad) { return (dpad & 31) == 0 ? dpad + 16 : dpad; }
 
 // ---- column means with fixed-order partials -------------------------------------------------------------------------
 // part[chunk][j] = sum of column j over the rows of the chunk; 256 threads = (256 / cw) row lanes x cw columns
@@ -61,79 +53,64 @@ __global__ __launch_bounds__(256) void k_colsum_partial(const double* __restrict
   }
 }
 
-__global__ void k_colmean_finish(const double* __restrict__ part, int chunks, int dim, int M, double* __restrict__ mean) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= dim) return;
-  double s = 0.0;
-  for (int q = 0; q < chunks; ++q) s += part[size_t(q) * dim + j];
-  mean[j] = s / double(M);
-}
-
 __global__ void k_subtract_mean(double* __restrict__ X, size_t count, int dim, const double* __restrict__ mean) {
   for (size_t e = blockIdx.x * size_t(blockDim.x) + threadIdx.x; e < count; e += size_t(gridDim.x) * blockDim.x)
     X[e] -= mean[e % size_t(dim)];
 }
 
 // ---- fused pass, dim <= 96 ------------------------------------------------------------------------------------------
-// Workgroup `b` owns the slabs [b * slabs_per_chunk, (b + 1) * slabs_per_chunk) of 32 rows.  Per slab: Xs <- rows of X
-// (prefetched in registers under the previous slab's MFMAs), Ys = Xs Vs^T (NT product, 16x16 tiles over the 8 waves),
-// acc += Ys^T Ys (TN product: the lower 16x16 tiles, at most three per wave, held in registers over all slabs).  With S
-// the slab of scores goes to S[(row, col < n_s)] as it is formed.  P[b] (dpad x dpad, lower tiles) receives the partial.
-__global__ __launch_bounds__(PT_THREADS) void k_pca_tall_fused(const double* __restrict__ X, int M, int dim, int dpad,
-                                                              const double* __restrict__ V, int slabs_per_chunk,
-                                                              double* __restrict__ P, double* __restrict__ S, int n_s) {
+// Workgroup `b` owns slabs_per_chunk slabs of 32 rows.  Per slab: Xs <- rows of X (prefetched in registers under the
+// previous slab's MFMAs), Ys = Xs Vs^T (NT), acc += Ys^T Ys (TN: the lower 16x16 tiles, at most three per wave).  With S the
+// slab of scores goes to S[(row, col < n_s)] as it is formed.  P[b] (dpad x dpad, lower tiles) receives the partial.
+__global__ __launch_bounds__(SLAB_THREADS) void k_pca_tall_fused(const double* __restrict__ X, int M, int dim, int dpad,
+                                                                const double* __restrict__ V, int slabs_per_chunk,
+                                                                double* __restrict__ P, double* __restrict__ S, int n_s) {
   extern __shared__ double pt_lds[];
-  const int LX = pt_ld_nt(dpad), LY = pt_ld_tn(dpad);
+  const int LX = slab_ld_nt(dpad), LY = slab_ld_tn(dpad);
   double* Vs = pt_lds;                 // dpad x LX
   double* Xs = Vs + dpad * LX;         // 32 x LX
-  double* Ys = Xs + PT_ROWS * LX;      // 32 x LY
+  double* Ys = Xs + SLAB_ROWS * LX;    // 32 x LY
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int i = lane & 15, k = lane >> 4;
   const int nct = dpad >> 4;
 
-  for (int e = t; e < dpad * LX; e += PT_THREADS) {
+  for (int e = t; e < dpad * LX; e += SLAB_THREADS) {
     const int j = e / LX, c = e - j * LX;
     Vs[e] = (j < dim && c < dim) ? V[size_t(j) * dim + c] : 0.0;
   }
-  for (int e = t; e < PT_ROWS * LX; e += PT_THREADS) Xs[e] = 0.0;   // (the padding columns stay zero: the slabs only write c < dim)
+  for (int e = t; e < SLAB_ROWS * LX; e += SLAB_THREADS) Xs[e] = 0.0;   // (the padding columns stay zero: the slabs only write c < dim)
 
   // this thread's entries of a slab: e = t + 512 q of the 32 * dim contiguous doubles
-  const int slab_doubles = PT_ROWS * dim;
+  const int slab_doubles = SLAB_ROWS * dim;
   int xoff[PT_XREG];
 #pragma unroll
   for (int q = 0; q < PT_XREG; ++q) {
-    const int e = t + PT_THREADS * q;
+    const int e = t + SLAB_THREADS * q;
     const int r = e / dim;
     xoff[q] = e < slab_doubles ? r * LX + (e - r * dim) : -1;
   }
   const size_t total = size_t(M) * dim;
-  const long long slab0 = (long long)blockIdx.x * slabs_per_chunk;
-  const long long nslabs = ((long long)M + PT_ROWS - 1) / PT_ROWS;
-  const long long slab1 = min(nslabs, slab0 + slabs_per_chunk);
+  long long slab0, slab1;
+  slab_chunk_range(M, slabs_per_chunk, &slab0, &slab1);
   double xr[PT_XREG];
   auto load_slab = [&](long long s) {
     const size_t base = size_t(s) * slab_doubles;
 #pragma unroll
     for (int q = 0; q < PT_XREG; ++q) {
-      const size_t g = base + t + PT_THREADS * q;
+      const size_t g = base + t + SLAB_THREADS * q;
       xr[q] = (xoff[q] >= 0 && g < total) ? X[g] : 0.0;
     }
   };
 
-  // tiles of this wave: rotation -- row tile w & 1, column tiles (w >> 1) + 4 jj; Gram -- lower tiles w + 8 q
-  const int rt = w & 1;
-  int gti[3], gtj[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int tt = w + 8 * q;
-    int ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= tt) ++ti;
-    gti[q] = ti < nct ? ti : -1;
-    gtj[q] = tt - ti * (ti + 1) / 2;
-  }
+  const int rt = w & 1, ct0 = w >> 1;
+  int gti[3], gtj[3];   // Gram: lower tiles w + 8 q
   d4_t acc[3];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) acc[q] = d4_t{0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < 3; ++q) {
+    lower_tile(w + 8 * q, &gti[q], &gtj[q]);
+    if (gti[q] >= nct) gti[q] = -1;
+    acc[q] = d4_t{0.0, 0.0, 0.0, 0.0};
+  }
 
   if (slab0 < slab1) load_slab(slab0);
   __syncthreads();
@@ -143,23 +120,10 @@ __global__ __launch_bounds__(PT_THREADS) void k_pca_tall_fused(const double* __r
       if (xoff[q] >= 0) Xs[xoff[q]] = xr[q];
     __syncthreads();
     if (s + 1 < slab1) load_slab(s + 1);
-    // Ys = Xs Vs^T
     {
-      d4_t y[2] = {d4_t{0.0, 0.0, 0.0, 0.0}, d4_t{0.0, 0.0, 0.0, 0.0}};
-      const int ct0 = w >> 1, ct1 = ct0 + 4;
-      const double* pa = Xs + (rt * 16 + i) * LX + k;
-      const double* pb0 = Vs + (ct0 * 16 + i) * LX + k;
-      const double* pb1 = Vs + (ct1 * 16 + i) * LX + k;
-      if (ct1 < nct) {
-        for (int kk = 0; kk < dpad; kk += 4) {
-          const double a = pa[kk];
-          y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb0[kk], y[0], 0, 0, 0);
-          y[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb1[kk], y[1], 0, 0, 0);
-        }
-      } else if (ct0 < nct) {
-        for (int kk = 0; kk < dpad; kk += 4) y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kk], pb0[kk], y[0], 0, 0, 0);
-      }
-      const long long grow0 = s * PT_ROWS + rt * 16 + k;
+      d4_t y[2];
+      slab_nt(Xs, LX, Vs, LX, dpad, nct, y);   // Ys = Xs Vs^T
+      const long long grow0 = s * SLAB_ROWS + rt * 16 + k;
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         const int ct = ct0 + 4 * jj;
@@ -174,26 +138,15 @@ __global__ __launch_bounds__(PT_THREADS) void k_pca_tall_fused(const double* __r
       }
     }
     __syncthreads();
-    // acc += Ys^T Ys (lower tiles)
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      if (gti[q] >= 0) {
-        const double* pa = Ys + k * LY + gti[q] * 16 + i;
-        const double* pb = Ys + k * LY + gtj[q] * 16 + i;
-#pragma unroll
-        for (int r = 0; r < PT_ROWS; r += 4) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[r * LY], pb[r * LY], acc[q], 0, 0, 0);
-      }
-    }
+    for (int q = 0; q < 3; ++q)
+      if (gti[q] >= 0) slab_tn_acc(Ys, LY, gti[q] * 16, gtj[q] * 16, acc[q]);
     // (the next iteration writes Xs, last read before the barrier above, and then passes a barrier before Ys is rewritten)
   }
   double* Pb = P + size_t(blockIdx.x) * dpad * dpad;
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    if (gti[q] >= 0) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) Pb[size_t(gti[q] * 16 + k + 4 * g) * dpad + gtj[q] * 16 + i] = acc[q][g];
-    }
-  }
+  for (int q = 0; q < 3; ++q)
+    if (gti[q] >= 0) slab_tn_store(Pb, dpad, gti[q] * 16, gtj[q] * 16, acc[q]);
 }
 
 // ---- G = Y^T Y of a row-major block (TN) ----------------------------------------------------------------------------
@@ -201,14 +154,13 @@ __global__ __launch_bounds__(PT_THREADS) void k_pca_tall_fused(const double* __r
 // layout is the MFMA's own: the A operand of lane (i = l & 15, k = l >> 4) is Y[r0 + k][c0 + i] -- 16 consecutive doubles
 // of a row.  Slabs of 32 rows x 64 columns per operand in LDS (stride 80: consecutive rows half the banks apart), the next
 // slab prefetched in registers.  P[chunk] (dpad x dpad, dpad = dim rounded up to 64): the lower quadrants of the block.
-constexpr int ST_LD = 80;
+constexpr int ST_ROWS = 32, ST_LD = 80;
 __global__ __launch_bounds__(256) void k_syrk_tn(const double* __restrict__ Y, int M, int dim, long long ld, int rows_per_chunk,
                                                  int dpad, double* __restrict__ P) {
-  __shared__ double As[PT_ROWS * ST_LD];
-  __shared__ double Bs[PT_ROWS * ST_LD];
-  int bi = 0;
-  while ((bi + 1) * (bi + 2) / 2 <= int(blockIdx.x)) ++bi;
-  const int bj = int(blockIdx.x) - bi * (bi + 1) / 2;
+  __shared__ double As[ST_ROWS * ST_LD];
+  __shared__ double Bs[ST_ROWS * ST_LD];
+  int bi, bj;
+  lower_tile(int(blockIdx.x), &bi, &bj);
   const bool diag = bi == bj;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w >> 1, wc = w & 1;
   const int i = lane & 15, k = lane >> 4;
@@ -231,19 +183,19 @@ __global__ __launch_bounds__(256) void k_syrk_tn(const double* __restrict__ Y, i
   const bool active = !(diag && wr < wc);
   const double* sB = diag ? As : Bs;
   if (r_begin < r_end) load(r_begin);
-  for (long long r0 = r_begin; r0 < r_end; r0 += PT_ROWS) {
+  for (long long r0 = r_begin; r0 < r_end; r0 += ST_ROWS) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       As[(rq + 4 * q) * ST_LD + col] = va[q];
       if (!diag) Bs[(rq + 4 * q) * ST_LD + col] = vb[q];
     }
     __syncthreads();
-    if (r0 + PT_ROWS < r_end) load(r0 + PT_ROWS);
+    if (r0 + ST_ROWS < r_end) load(r0 + ST_ROWS);
     if (active) {
       const double* pa = As + k * ST_LD + wr * 32 + i;
       const double* pb = sB + k * ST_LD + wc * 32 + i;
 #pragma unroll
-      for (int r = 0; r < PT_ROWS; r += 4) {
+      for (int r = 0; r < ST_ROWS; r += 4) {
         const double a0 = pa[r * ST_LD], a1 = pa[r * ST_LD + 16];
         const double b0 = pb[r * ST_LD], b1 = pb[r * ST_LD + 16];
         acc.c[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc.c[0][0], 0, 0, 0);
@@ -263,19 +215,6 @@ __global__ __launch_bounds__(256) void k_syrk_tn(const double* __restrict__ Y, i
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         Pb[size_t(bi * 64 + wr * 32 + ii * 16 + k + 4 * g) * dpad + bj * 64 + wc * 32 + jj * 16 + i] = acc.c[ii][jj][g];
-}
-
-// G[i][j] = sum over the chunks, in chunk order, of P[chunk][max(i, j)][min(i, j)]: the reduction and the mirror in one
-__global__ void k_syrk_reduce(const double* __restrict__ P, int chunks, int dpad, int dim, double* __restrict__ G) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= dim * dim) return;
-  const int r = idx / dim, c = idx - r * dim;
-  const int hi = max(r, c), lo = min(r, c);
-  const double* p = P + size_t(hi) * dpad + lo;
-  const size_t step = size_t(dpad) * dpad;
-  double s = 0.0;
-  for (int q = 0; q < chunks; ++q) s += p[q * step];
-  G[idx] = s;
 }
 
 // stat[0] = max over i != j of |g_ij| / (64 eps max(d) max(d_i, d_j)), stat[1] = max(d), stat[2] = entries of G that are
@@ -378,22 +317,23 @@ struct TallPlan {
 
 TallPlan make_plan(const rom_ctx* ctx, int M, int dim) {
   TallPlan p;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
   p.fused = dim <= PT_FUSED_MAX;
-  const int nslabs = (M + PT_ROWS - 1) / PT_ROWS;
   if (p.fused) {
-    p.dpad = (dim + 15) / 16 * 16;
+    const SlabPlan sp = rom_slab_plan(ctx, M, dim);
+    p.dpad = sp.pad;
     p.nblk = 1;
-    p.per_chunk = (nslabs + n_cu - 1) / n_cu;
-    p.chunks = (nslabs + p.per_chunk - 1) / p.per_chunk;
+    p.per_chunk = int(sp.per_chunk);
+    p.chunks = sp.chunks;
   } else {
+    const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+    const int nslabs = (M + ST_ROWS - 1) / ST_ROWS;
     p.dpad = (dim + 63) / 64 * 64;
     const int nb = p.dpad / 64;
     p.nblk = nb * (nb + 1) / 2;
     int want = std::max(1, (4 * n_cu + p.nblk - 1) / p.nblk);   // four workgroups (40 KB of LDS each) per CU
     want = std::min(want, nslabs);
     const int slabs = (nslabs + want - 1) / want;
-    p.per_chunk = slabs * PT_ROWS;
+    p.per_chunk = slabs * ST_ROWS;
     p.chunks = (nslabs + slabs - 1) / slabs;
   }
   return p;
@@ -422,7 +362,6 @@ extern "C" int rom_pca_tall(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int
   double* s_out = (S && n > 0) ? S->p + s_row0 * n : nullptr;
   const size_t dd = size_t(dim) * dim;
   const TallPlan plan = make_plan(ctx, M, dim);
-  static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;   // per-shape names in the profile records
   double executed = 0.0;
   int syncs = 0;
   const unsigned long long helper_syncs0 = ctx->host_syncs;
@@ -444,7 +383,7 @@ extern "C" int rom_pca_tall(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int
       {
         ROM_PROF(ctx, "pca_tall_center", 2.0 * M * dim, 24.0 * M * dim);
         k_colsum_partial<<<chunks, 256, 0, ctx->stream>>>(x, M, dim, per, cw, part);
-        k_colmean_finish<<<(dim + 255) / 256, 256, 0, ctx->stream>>>(part, chunks, dim, M, d_mean);
+        kb_partials_colsum<<<(dim + 255) / 256, 256, 0, ctx->stream>>>(part, chunks, dim, double(M), d_mean);
         k_subtract_mean<<<unsigned(std::min<size_t>((size_t(M) * dim + 255) / 256, 8192)), 256, 0, ctx->stream>>>(x, size_t(M) * dim, dim,
                                                                                                              d_mean);
       }
@@ -477,35 +416,32 @@ extern "C" int rom_pca_tall(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int
 
   size_t fused_lds = 0;
   if (plan.fused) {
-    fused_lds = (size_t(plan.dpad) * pt_ld_nt(plan.dpad) + size_t(PT_ROWS) * pt_ld_nt(plan.dpad) + size_t(PT_ROWS) * pt_ld_tn(plan.dpad)) *
-                sizeof(double);
-    if (fused_lds > 64 * 1024 && !ctx->lds_optin_pca_tall) {
-      ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pca_tall_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      ctx->lds_optin_pca_tall = true;
-    }
+    fused_lds = (size_t(plan.dpad + SLAB_ROWS) * slab_ld_nt(plan.dpad) + size_t(SLAB_ROWS) * slab_ld_tn(plan.dpad)) * sizeof(double);
+    if (fused_lds > 64 * 1024)
+      ROM_TRY(rom_lds_optin(ctx->lds_optin_pca_tall, reinterpret_cast<const void*>(k_pca_tall_fused), 160 * 1024));
   }
 
   // one pass over the block: G = (Xc Vc^T)^T (Xc Vc^T), the scores into S when `write_s`
   auto pass = [&](bool rotate, bool write_s) -> int {
     if (plan.fused) {
       char nm[48];
-      detail ? snprintf(nm, sizeof nm, "pca_tall_fused_d%d", dim) : snprintf(nm, sizeof nm, "pca_tall_fused");
+      rom_prof_name(nm, sizeof nm, "pca_tall_fused", "_d%d", dim);
       const double fl = 3.0 * M * double(plan.dpad) * plan.dpad;
       ROM_PROF(ctx, nm, fl, 8.0 * M * dim + (write_s ? 8.0 * M * n : 0.0));
-      k_pca_tall_fused<<<plan.chunks, PT_THREADS, fused_lds, ctx->stream>>>(x, M, dim, plan.dpad, Vc, plan.per_chunk, P,
+      k_pca_tall_fused<<<plan.chunks, SLAB_THREADS, fused_lds, ctx->stream>>>(x, M, dim, plan.dpad, Vc, plan.per_chunk, P,
                                                                             write_s ? s_out : nullptr, n);
       executed += fl;
     } else {
       const double* src = x;
       if (rotate) {
         char nm[48];
-        detail ? snprintf(nm, sizeof nm, "pca_tall_rotate_d%d", dim) : snprintf(nm, sizeof nm, "pca_tall_rotate");
+        rom_prof_name(nm, sizeof nm, "pca_tall_rotate", "_d%d", dim);
         ROM_TRY(rom_launch_gemm_nt(ctx, M, dim, dim, 1.0, x, dim, Vc, dim, 0.0, y_buf, dim, nm));
         executed += 2.0 * M * double(dim) * dim;
         src = y_buf;
       }
       char nm[48];
-      detail ? snprintf(nm, sizeof nm, "syrk_tn_d%d", dim) : snprintf(nm, sizeof nm, "syrk_tn");
+      rom_prof_name(nm, sizeof nm, "syrk_tn", "_d%d", dim);
       const double fl = double(M) * plan.dpad * (plan.dpad + 64.0);
       ROM_PROF(ctx, nm, fl, 8.0 * M * dim);
       k_syrk_tn<<<dim3(plan.nblk, plan.chunks), 256, 0, ctx->stream>>>(src, M, dim, dim, plan.per_chunk, plan.dpad, P);
@@ -514,7 +450,7 @@ extern "C" int rom_pca_tall(rom_ctx* ctx, rom_buf* X, int64_t x_row0, int M, int
     ROM_HIP(hipGetLastError());
     {
       ROM_PROF(ctx, "syrk_tn_reduce", double(plan.chunks) * dd, 8.0 * plan.chunks * dd);
-      k_syrk_reduce<<<gdd, 256, 0, ctx->stream>>>(P, plan.chunks, plan.dpad, dim, G);
+      kb_partials_reduce<<<gdd, 256, 0, ctx->stream>>>(P, plan.chunks, plan.dpad, plan.dpad, dim, 0, G, nullptr, 0, 0);
       k_pca_tall_check<<<1, 1024, 0, ctx->stream>>>(G, dim, stat);
     }
     ROM_HIP(hipGetLastError());

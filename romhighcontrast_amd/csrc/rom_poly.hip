@@ -14,25 +14,23 @@
 //   pass 2+: G_k = I + delta on the leading rank x rank block.  W = T_k^T G_k^-1 B_k carries the remaining non-orthogonality
 //            exactly; the solve costs a factor cond(G_k) <= (1 + |delta|_2) / (1 - |delta|_2) on eps.  Another pass (with T
 //            <- whitening of G_k times T) only while P |delta|_max > PL_DELTA_OK; at most PL_PASS_CAP passes.
-// Kernels: k_poly_pass (features generated in LDS from an exponent table, NT product with T and TN product Psi^T [Psi | Y] on
-// v_mfma_f64_16x16x4_f64, accumulators in registers over the slabs of a workgroup's chunk, one partial per workgroup),
-// k_poly_reduce (the partials added in chunk order), k_poly_predict (the same slab times W^T, written as it is formed, with
-// optional Yref - prediction and per-column sums of squares).  No floating-point atomics: the same bits on every call.
+// Kernels: k_poly_pass (features generated in LDS from an exponent table; NT product with T and TN product Psi^T [Psi | Y] by the
+// slab engine of rom_slab.h, one partial per workgroup that kb_partials_reduce adds in chunk order), k_poly_predict (the same
+// slab times W^T, written as it is formed, with optional Yref - prediction and per-column sums of squares).  No floating-point
+// atomics: the same bits on every call.
 #include <cmath>
 #include <cstring>
 
 #include "rom_basis_int.h"
-#include "rom_mma.h"
+#include "rom_slab.h"
 
 namespace {
 
-constexpr int PL_MAX = 96;       // largest P (T + the slabs in 160 KB of LDS, as PT_FUSED_MAX of rom_pca_tall)
+constexpr int PL_MAX = 96;       // largest P (T + the slabs in 160 KB of LDS)
 constexpr int PL_QG = 96;        // target columns of one launch
 constexpr int PL_QMAX = 1024;
 constexpr int PL_MMAX = 16, PL_DMAX = 8;
-constexpr int PL_ROWS = 32;      // rows of a slab
-constexpr int PL_THREADS = 512;  // 8 waves: one workgroup per CU (LDS), two waves per SIMD
-constexpr int PL_YREG = PL_ROWS * PL_QG / PL_THREADS;   // target values of a slab per thread
+constexpr int PL_YREG = SLAB_ROWS * PL_QG / SLAB_THREADS;   // target values of a slab per thread
 constexpr int PL_TILES = 8;      // 16 x 16 tiles of Psi^T [Psi | Y] per wave: 21 lower Gram tiles + 36 of B <= 64
 constexpr int PL_PASS_CAP = 4;
 constexpr int PL_NOFAC = 255;
@@ -44,11 +42,7 @@ constexpr double PL_DELTA_OK = 1.0 / 3.0;
 // device block of a map: c (16) | h (16) | bad count (1, then padding to 40) | factor table (PL_MAX x PL_DMAX bytes) | W (q x P)
 constexpr size_t PL_OFF_BAD = 32, PL_OFF_TAB = 40, PL_OFF_W = PL_OFF_TAB + PL_MAX * PL_DMAX / sizeof(double);
 
-// LDS row strides (doubles), as in rom_pca_tall.hip: an NT operand read (lane -> row l & 15, k = l >> 4) wants rows 4 banks
-// apart: stride = 2 mod 4; a TN operand read (lane -> column l & 15, row k = l >> 4) wants consecutive rows half the banks
-// apart: stride = 16 mod 32.  The Legendre table has an odd stride (a lane per row).
-__host__ __device__ inline int pl_ld_nt(int n) { return n + 2; }
-__host__ __device__ inline int pl_ld_tn(int n) { return (n & 31) == 0 ? n + 16 : n; }
+// LDS row stride of the Legendre table: odd (a lane per row)
 __host__ __device__ inline int pl_ld_leg(int m, int d) { return (m * d) | 1; }
 
 // ---- mid-range and half-range of the input columns (fixed-order partials) -------------------------------------------------
@@ -150,35 +144,34 @@ __device__ inline void pl_features(double* __restrict__ dst, int ld, const doubl
 }
 
 // ---- one pass of the fit --------------------------------------------------------------------------------------------------
-// Workgroup b owns the slabs [b * slabs_per_chunk, (b + 1) * slabs_per_chunk) of 32 rows.  Per slab: the Legendre values of the
-// m inputs (prefetched in registers under the previous slab's MFMAs, as the targets), the 32 x P feature slab, Psi = Phi T^T
-// (NT product; T == NULL: Psi = Phi, the features go straight to the TN slab), acc += Psi^T [Psi | Y] (TN product: the lower
-// Gram tiles when `gram`, and the ppad x qpad tiles of B; at most PL_TILES per wave, held in registers over all slabs).
-// Part[b] (ppad x (ppad + qpad)) receives the partial.
-__global__ __launch_bounds__(PL_THREADS) void k_poly_pass(const double* __restrict__ X, long long ldx, int m, int d,
-                                                         const double* __restrict__ ch, const unsigned char* __restrict__ tab_g,
-                                                         int P, int ppad, const double* __restrict__ T,
-                                                         const double* __restrict__ Y, long long ldy, int qg, int qpad, long long M,
-                                                         long long slabs_per_chunk, int gram, double* __restrict__ Part) {
+// Workgroup b owns slabs_per_chunk slabs of 32 rows.  Per slab: the Legendre values of the m inputs (prefetched in registers
+// under the previous slab's MFMAs, as the targets), the 32 x P feature slab, Psi = Phi T^T (NT product; T == NULL: Psi = Phi,
+// the features go straight to the TN slab), acc += Psi^T [Psi | Y] (TN product: the lower Gram tiles when `gram`, and the
+// ppad x qpad tiles of B; at most PL_TILES per wave).  Part[b] (ppad x (ppad + qpad)) receives the partial.
+__global__ __launch_bounds__(SLAB_THREADS) void k_poly_pass(const double* __restrict__ X, long long ldx, int m, int d,
+                                                           const double* __restrict__ ch, const unsigned char* __restrict__ tab_g,
+                                                           int P, int ppad, const double* __restrict__ T,
+                                                           const double* __restrict__ Y, long long ldy, int qg, int qpad, long long M,
+                                                           long long slabs_per_chunk, int gram, double* __restrict__ Part) {
   extern __shared__ double pl_lds[];
   __shared__ unsigned char tab[PL_MAX * PL_DMAX];
-  const int LX = pl_ld_nt(ppad), LY = pl_ld_tn(ppad + qpad), LL = pl_ld_leg(m, d);
+  const int LX = slab_ld_nt(ppad), LY = slab_ld_tn(ppad + qpad), LL = pl_ld_leg(m, d);
   double* Ts = pl_lds;                 // ppad x LX
   double* Fs = Ts + ppad * LX;         // 32 x LX: the features (NT operand)
-  double* Ys = Fs + PL_ROWS * LX;      // 32 x LY: [Psi | Y] (TN operand)
-  double* Leg = Ys + PL_ROWS * LY;     // 32 x LL
+  double* Ys = Fs + SLAB_ROWS * LX;    // 32 x LY: [Psi | Y] (TN operand)
+  double* Leg = Ys + SLAB_ROWS * LY;   // 32 x LL
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int i = lane & 15, k = lane >> 4;
   const int nct = ppad >> 4, nqt = qpad >> 4;
   const bool identity = T == nullptr;
 
-  for (int e = t; e < PL_MAX * PL_DMAX; e += PL_THREADS) tab[e] = tab_g[e];
-  for (int e = t; e < ppad * LX; e += PL_THREADS) {
+  for (int e = t; e < PL_MAX * PL_DMAX; e += SLAB_THREADS) tab[e] = tab_g[e];
+  for (int e = t; e < ppad * LX; e += SLAB_THREADS) {
     const int j = e / LX, c = e - j * LX;
     Ts[e] = (!identity && j < P && c < P) ? T[size_t(j) * P + c] : 0.0;
   }
-  for (int e = t; e < PL_ROWS * LX; e += PL_THREADS) Fs[e] = 0.0;   // (the padding columns stay zero: the slabs write p < P)
-  for (int e = t; e < PL_ROWS * LY; e += PL_THREADS) Ys[e] = 0.0;
+  for (int e = t; e < SLAB_ROWS * LX; e += SLAB_THREADS) Fs[e] = 0.0;   // (the padding columns stay zero: the slabs write p < P)
+  for (int e = t; e < SLAB_ROWS * LY; e += SLAB_THREADS) Ys[e] = 0.0;
 
   // this thread's input value of a slab: row t >> 4, column t & 15; its targets: e = t + 512 u of the 32 x qg values
   const int xj = t & 15, xrow = t >> 4;
@@ -186,75 +179,59 @@ __global__ __launch_bounds__(PL_THREADS) void k_poly_pass(const double* __restri
   int yrow[PL_YREG], ycol[PL_YREG];
 #pragma unroll
   for (int u = 0; u < PL_YREG; ++u) {
-    const int e = t + PL_THREADS * u;
+    const int e = t + SLAB_THREADS * u;
     const int r = e / qg;
-    yrow[u] = e < PL_ROWS * qg ? r : -1;
+    yrow[u] = e < SLAB_ROWS * qg ? r : -1;
     ycol[u] = e - r * qg;
   }
-  const long long nslabs = (M + PL_ROWS - 1) / PL_ROWS;
-  const long long slab0 = (long long)blockIdx.x * slabs_per_chunk;
-  const long long slab1 = min(nslabs, slab0 + slabs_per_chunk);
+  long long slab0, slab1;
+  slab_chunk_range(M, slabs_per_chunk, &slab0, &slab1);
   double xr = 0.0, yr[PL_YREG];
   auto load_slab = [&](long long s) {
-    const long long row0 = s * PL_ROWS;
+    const long long row0 = s * SLAB_ROWS;
     xr = (xj < m && row0 + xrow < M) ? X[(row0 + xrow) * ldx + xj] : 0.0;
 #pragma unroll
     for (int u = 0; u < PL_YREG; ++u)
       yr[u] = (yrow[u] >= 0 && row0 + yrow[u] < M) ? Y[(row0 + yrow[u]) * ldy + ycol[u]] : 0.0;
   };
 
-  // tiles of this wave: NT -- row tile w & 1, column tiles (w >> 1) + 4 jj; TN -- tile w + 8 u of the list [lower Gram
-  // tiles | B tiles], as column offsets (ca, cb) into the TN slab
-  const int rt = w & 1;
+  const int rt = w & 1, ct0 = w >> 1;
+  // TN tiles of this wave: w + 8 u of the list [lower Gram tiles | B tiles], as column offsets (ca, cb) into the TN slab
   const int ngram = gram ? nct * (nct + 1) / 2 : 0, ntile = ngram + nct * nqt;
   int tca[PL_TILES], tcb[PL_TILES];
+  d4_t acc[PL_TILES];
 #pragma unroll
   for (int u = 0; u < PL_TILES; ++u) {
     const int tt = w + 8 * u;
     tca[u] = -1;
     tcb[u] = 0;
     if (tt < ngram) {
-      int ti = 0;
-      while ((ti + 1) * (ti + 2) / 2 <= tt) ++ti;
+      int ti, tj;
+      lower_tile(tt, &ti, &tj);
       tca[u] = ti * 16;
-      tcb[u] = (tt - ti * (ti + 1) / 2) * 16;
+      tcb[u] = tj * 16;
     } else if (tt < ntile) {
       const int tb = tt - ngram, bi = tb / nqt;
       tca[u] = bi * 16;
       tcb[u] = ppad + (tb - bi * nqt) * 16;
     }
+    acc[u] = d4_t{0.0, 0.0, 0.0, 0.0};
   }
-  d4_t acc[PL_TILES];
-#pragma unroll
-  for (int u = 0; u < PL_TILES; ++u) acc[u] = d4_t{0.0, 0.0, 0.0, 0.0};
 
   if (slab0 < slab1) load_slab(slab0);
   __syncthreads();
   for (long long s = slab0; s < slab1; ++s) {
     pl_legendre_rows(Leg, LL, m, d, xr, xc, xh);
     __syncthreads();   // (every wave is past the TN product of the previous slab: the TN slab is free)
-    pl_features(identity ? Ys : Fs, identity ? LY : LX, Leg, LL, tab, P, d, M - s * PL_ROWS);
+    pl_features(identity ? Ys : Fs, identity ? LY : LX, Leg, LL, tab, P, d, M - s * SLAB_ROWS);
 #pragma unroll
     for (int u = 0; u < PL_YREG; ++u)
       if (yrow[u] >= 0) Ys[yrow[u] * LY + ppad + ycol[u]] = yr[u];
     if (s + 1 < slab1) load_slab(s + 1);
     __syncthreads();
     if (!identity) {
-      // Psi = Phi T^T
-      d4_t y[2] = {d4_t{0.0, 0.0, 0.0, 0.0}, d4_t{0.0, 0.0, 0.0, 0.0}};
-      const int ct0 = w >> 1, ct1 = ct0 + 4;
-      const double* pa = Fs + (rt * 16 + i) * LX + k;
-      const double* pb0 = Ts + (ct0 * 16 + i) * LX + k;
-      const double* pb1 = Ts + (ct1 * 16 + i) * LX + k;
-      if (ct1 < nct) {
-        for (int kk = 0; kk < ppad; kk += 4) {
-          const double a = pa[kk];
-          y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb0[kk], y[0], 0, 0, 0);
-          y[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb1[kk], y[1], 0, 0, 0);
-        }
-      } else if (ct0 < nct) {
-        for (int kk = 0; kk < ppad; kk += 4) y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kk], pb0[kk], y[0], 0, 0, 0);
-      }
+      d4_t y[2];
+      slab_nt(Fs, LX, Ts, LX, ppad, nct, y);   // Psi = Phi T^T
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         const int ct = ct0 + 4 * jj;
@@ -265,50 +242,15 @@ __global__ __launch_bounds__(PL_THREADS) void k_poly_pass(const double* __restri
       }
       __syncthreads();
     }
-    // acc += Psi^T [Psi | Y]
 #pragma unroll
-    for (int u = 0; u < PL_TILES; ++u) {
-      if (tca[u] >= 0) {
-        const double* pa = Ys + k * LY + tca[u] + i;
-        const double* pb = Ys + k * LY + tcb[u] + i;
-#pragma unroll
-        for (int r = 0; r < PL_ROWS; r += 4) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[r * LY], pb[r * LY], acc[u], 0, 0, 0);
-      }
-    }
+    for (int u = 0; u < PL_TILES; ++u)
+      if (tca[u] >= 0) slab_tn_acc(Ys, LY, tca[u], tcb[u], acc[u]);   // acc += Psi^T [Psi | Y]
   }
   const int ldp = ppad + qpad;
   double* Pb = Part + size_t(blockIdx.x) * ppad * ldp;
 #pragma unroll
-  for (int u = 0; u < PL_TILES; ++u) {
-    if (tca[u] >= 0) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) Pb[size_t(tca[u] + k + 4 * g) * ldp + tcb[u] + i] = acc[u][g];
-    }
-  }
-}
-
-// G[r][c] (P x P, with G != NULL) = sum over the chunks, in chunk order, of Part[chunk][max(r, c)][min(r, c)]; B[r][c0 + c]
-// (P x q) = the same sum of Part[chunk][r][ppad + c], c < qg
-__global__ void k_poly_reduce(const double* __restrict__ Part, int chunks, int ppad, int ldp, int P, int qg, double* __restrict__ G,
-                              double* __restrict__ B, int q, int c0) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ng = G ? P * P : 0;
-  if (idx >= ng + P * qg) return;
-  const size_t step = size_t(ppad) * ldp;
-  const double* p;
-  double* out;
-  if (idx < ng) {
-    const int r = idx / P, c = idx - r * P;
-    p = Part + size_t(max(r, c)) * ldp + min(r, c);
-    out = G + idx;
-  } else {
-    const int e = idx - ng, r = e / qg, c = e - r * qg;
-    p = Part + size_t(r) * ldp + ppad + c;
-    out = B + size_t(r) * q + c0 + c;
-  }
-  double s = 0.0;
-  for (int ch = 0; ch < chunks; ++ch) s += p[ch * step];
-  *out = s;
+  for (int u = 0; u < PL_TILES; ++u)
+    if (tca[u] >= 0) slab_tn_store(Pb, ldp, tca[u], tcb[u], acc[u]);
 }
 
 // Gh = D G D with D = diag(g_ii)^-1/2 (0 for a column that is zero), Dv = the diagonal of D
@@ -327,36 +269,35 @@ __global__ void k_poly_normalise(const double* __restrict__ G, int P, double* __
 // as it is formed: OUT <- the prediction, or Yref - prediction.  SS[chunk][c] (with SS != NULL) = the chunk's sum of squares
 // of what OUT receives in column c: per lane over its rows and slabs, then over the four k lanes and the two row tiles, always
 // in the same order.
-__global__ __launch_bounds__(PL_THREADS) void k_poly_predict(const double* __restrict__ X, long long ldx, int m, int d,
-                                                            const double* __restrict__ ch, const unsigned char* __restrict__ tab_g,
-                                                            int P, int ppad, const double* __restrict__ W, int q, long long M,
-                                                            long long slabs_per_chunk, double* __restrict__ OUT, long long ldo,
-                                                            const double* __restrict__ Yref, long long ldr, double* __restrict__ SS) {
+__global__ __launch_bounds__(SLAB_THREADS) void k_poly_predict(const double* __restrict__ X, long long ldx, int m, int d,
+                                                              const double* __restrict__ ch, const unsigned char* __restrict__ tab_g,
+                                                              int P, int ppad, const double* __restrict__ W, int q, long long M,
+                                                              long long slabs_per_chunk, double* __restrict__ OUT, long long ldo,
+                                                              const double* __restrict__ Yref, long long ldr, double* __restrict__ SS) {
   extern __shared__ double pl_lds[];
   __shared__ unsigned char tab[PL_MAX * PL_DMAX];
   __shared__ double red[2 * PL_QG];
   const int c0 = blockIdx.y * PL_QG, qg = min(PL_QG, q - c0), qpad = (qg + 15) / 16 * 16;
-  const int LX = pl_ld_nt(ppad), LL = pl_ld_leg(m, d);
+  const int LX = slab_ld_nt(ppad), LL = pl_ld_leg(m, d);
   double* Ws = pl_lds;                 // qpad x LX
   double* Fs = Ws + qpad * LX;         // 32 x LX
-  double* Leg = Fs + PL_ROWS * LX;     // 32 x LL
+  double* Leg = Fs + SLAB_ROWS * LX;   // 32 x LL
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int i = lane & 15, k = lane >> 4;
   const int nqt = qpad >> 4;
 
-  for (int e = t; e < PL_MAX * PL_DMAX; e += PL_THREADS) tab[e] = tab_g[e];
-  for (int e = t; e < qpad * LX; e += PL_THREADS) {
+  for (int e = t; e < PL_MAX * PL_DMAX; e += SLAB_THREADS) tab[e] = tab_g[e];
+  for (int e = t; e < qpad * LX; e += SLAB_THREADS) {
     const int j = e / LX, c = e - j * LX;
     Ws[e] = (j < qg && c < P) ? W[size_t(c0 + j) * P + c] : 0.0;
   }
-  for (int e = t; e < PL_ROWS * LX; e += PL_THREADS) Fs[e] = 0.0;
+  for (int e = t; e < SLAB_ROWS * LX; e += SLAB_THREADS) Fs[e] = 0.0;
   const int xj = t & 15, xrow = t >> 4;
   const double xc = xj < m ? ch[xj] : 0.0, xh = xj < m ? ch[16 + xj] : 0.0;
-  const long long nslabs = (M + PL_ROWS - 1) / PL_ROWS;
-  const long long slab0 = (long long)blockIdx.x * slabs_per_chunk;
-  const long long slab1 = min(nslabs, slab0 + slabs_per_chunk);
+  long long slab0, slab1;
+  slab_chunk_range(M, slabs_per_chunk, &slab0, &slab1);
   auto load_x = [&](long long s) {
-    const long long row = s * PL_ROWS + xrow;
+    const long long row = s * SLAB_ROWS + xrow;
     return (xj < m && row < M) ? X[row * ldx + xj] : 0.0;
   };
   const int rt = w & 1, ct0 = w >> 1;
@@ -366,24 +307,12 @@ __global__ __launch_bounds__(PL_THREADS) void k_poly_predict(const double* __res
   for (long long s = slab0; s < slab1; ++s) {
     pl_legendre_rows(Leg, LL, m, d, xr, xc, xh);
     __syncthreads();
-    pl_features(Fs, LX, Leg, LL, tab, P, d, M - s * PL_ROWS);
+    pl_features(Fs, LX, Leg, LL, tab, P, d, M - s * SLAB_ROWS);
     if (s + 1 < slab1) xr = load_x(s + 1);
     __syncthreads();
-    d4_t y[2] = {d4_t{0.0, 0.0, 0.0, 0.0}, d4_t{0.0, 0.0, 0.0, 0.0}};
-    const int ct1 = ct0 + 4;
-    const double* pa = Fs + (rt * 16 + i) * LX + k;
-    const double* pb0 = Ws + (ct0 * 16 + i) * LX + k;
-    const double* pb1 = Ws + (ct1 * 16 + i) * LX + k;
-    if (ct1 < nqt) {
-      for (int kk = 0; kk < ppad; kk += 4) {
-        const double a = pa[kk];
-        y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb0[kk], y[0], 0, 0, 0);
-        y[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb1[kk], y[1], 0, 0, 0);
-      }
-    } else if (ct0 < nqt) {
-      for (int kk = 0; kk < ppad; kk += 4) y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kk], pb0[kk], y[0], 0, 0, 0);
-    }
-    const long long grow0 = s * PL_ROWS + rt * 16 + k;
+    d4_t y[2];
+    slab_nt(Fs, LX, Ws, LX, ppad, nqt, y);   // the slab times W_g^T
+    const long long grow0 = s * SLAB_ROWS + rt * 16 + k;
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       const int col = (ct0 + 4 * jj) * 16 + i;
@@ -413,14 +342,6 @@ __global__ __launch_bounds__(PL_THREADS) void k_poly_predict(const double* __res
   if (t < qg) SS[size_t(blockIdx.x) * q + c0 + t] = red[t] + red[PL_QG + t];
 }
 
-__global__ void k_poly_sumsq_finish(const double* __restrict__ SS, int chunks, int q, double* __restrict__ out) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= q) return;
-  double s = 0.0;
-  for (int ch = 0; ch < chunks; ++ch) s += SS[size_t(ch) * q + c];
-  out[c] = s;
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------
 // the exponent rows of PolynomialFeatures(d).powers_: graded, combinations_with_replacement(range(m), k) in lexicographic order
 long long poly_count(int m, int d) {
@@ -447,27 +368,12 @@ void poly_powers(int m, int d, std::vector<int>& powers) {
   }
 }
 
-struct PolyPlan {
-  int ppad, chunks;
-  long long per_chunk;   // slabs of a chunk
-};
-
-PolyPlan poly_plan(const rom_ctx* ctx, long long M, int P) {
-  PolyPlan p;
-  const long long n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-  const long long nslabs = (M + PL_ROWS - 1) / PL_ROWS;
-  p.ppad = (P + 15) / 16 * 16;
-  p.per_chunk = (nslabs + n_cu - 1) / n_cu;
-  p.chunks = int((nslabs + p.per_chunk - 1) / p.per_chunk);
-  return p;
-}
-
 size_t pass_lds(int ppad, int qpad, int m, int d) {
-  return (size_t(ppad + PL_ROWS) * pl_ld_nt(ppad) + size_t(PL_ROWS) * pl_ld_tn(ppad + qpad) + size_t(PL_ROWS) * pl_ld_leg(m, d)) *
+  return (size_t(ppad + SLAB_ROWS) * slab_ld_nt(ppad) + size_t(SLAB_ROWS) * slab_ld_tn(ppad + qpad) + size_t(SLAB_ROWS) * pl_ld_leg(m, d)) *
          sizeof(double);
 }
 size_t predict_lds(int ppad, int qpad, int m, int d) {
-  return (size_t(qpad + PL_ROWS) * pl_ld_nt(ppad) + size_t(PL_ROWS) * pl_ld_leg(m, d)) * sizeof(double);
+  return (size_t(qpad + SLAB_ROWS) * slab_ld_nt(ppad) + size_t(SLAB_ROWS) * pl_ld_leg(m, d)) * sizeof(double);
 }
 
 bool ranges_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
@@ -542,13 +448,12 @@ extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx,
   const int P = int(Pl);
   const double* x = X->p + x_off;
   const double* y = Y->p + y_off;
-  static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;   // per-shape names in the profile records
   // A Cholesky factorisation of a Gram matrix sees the SQUARE of the condition number: a squared pivot of the column-
   // normalised G_1 at or below about P eps of the largest is rounding noise of the P-term sums behind it, so the default
   // drops a term there: rcond^2 = P eps, rcond = sqrt(P eps) (1e-7 at P = 96).
   const double rc = rcond > 0.0 ? rcond : std::sqrt(double(P) * PL_EPS);
-  const PolyPlan plan = poly_plan(ctx, M, P);
-  const int ppad = plan.ppad, ngroups = (q + PL_QG - 1) / PL_QG;
+  const SlabPlan plan = rom_slab_plan(ctx, M, P);
+  const int ppad = plan.pad, ngroups = (q + PL_QG - 1) / PL_QG;
   const unsigned long long helper_syncs0 = ctx->host_syncs;
   int syncs = 0;
   double executed = 0.0;
@@ -600,10 +505,8 @@ extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx,
   double* d_G = GB;
   double* d_B = GB.p() + pp;
 
-  if (pass_lds(ppad, PL_QG, m, d) > 64 * 1024 && !ctx->lds_optin_poly_pass) {
-    ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_poly_pass), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-    ctx->lds_optin_poly_pass = true;
-  }
+  if (pass_lds(ppad, PL_QG, m, d) > 64 * 1024)
+    ROM_TRY(rom_lds_optin(ctx->lds_optin_poly_pass, reinterpret_cast<const void*>(k_poly_pass), 159 * 1024));
 
   // one pass: every target group through the kernel (the Gram tiles with the first), G and B reduced in chunk order
   auto pass = [&](const double* T) -> int {
@@ -613,17 +516,17 @@ extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx,
       const double fl = double(M) * ((T ? 2.0 * ppad * ppad : 0.0) + 512.0 * ntile);
       {
         char nm[48];
-        detail ? snprintf(nm, sizeof nm, "poly_pass_P%d_q%d", P, qg) : snprintf(nm, sizeof nm, "poly_pass");
+        rom_prof_name(nm, sizeof nm, "poly_pass", "_P%d_q%d", P, qg);
         ROM_PROF(ctx, nm, fl, 8.0 * M * (m + qg));
-        k_poly_pass<<<plan.chunks, PL_THREADS, pass_lds(ppad, qpad, m, d), ctx->stream>>>(x, ldx, m, d, dev, d_tab, P, ppad, T, y + c0, ldy,
+        k_poly_pass<<<plan.chunks, SLAB_THREADS, pass_lds(ppad, qpad, m, d), ctx->stream>>>(x, ldx, m, d, dev, d_tab, P, ppad, T, y + c0, ldy,
                                                                                        qg, qpad, M, plan.per_chunk, g == 0, Part);
       }
       ROM_HIP(hipGetLastError());
       executed += fl;
       {
         ROM_PROF(ctx, "poly_reduce", double(plan.chunks) * (pp + P * qg), 8.0 * plan.chunks * (pp + P * qg));
-        k_poly_reduce<<<blocks_for((g == 0 ? pp : 0) + size_t(P) * qg), 256, 0, ctx->stream>>>(Part, plan.chunks, ppad, ppad + qpad, P, qg,
-                                                                                               g == 0 ? d_G : nullptr, d_B, q, c0);
+        kb_partials_reduce<<<blocks_for((g == 0 ? pp : 0) + size_t(P) * qg), 256, 0, ctx->stream>>>(Part, plan.chunks, ppad, ppad + qpad, P,
+                                                                                                    qg, g == 0 ? d_G : nullptr, d_B, q, c0);
       }
       ROM_HIP(hipGetLastError());
     }
@@ -780,15 +683,11 @@ extern "C" int rom_poly_predict(rom_poly* h, rom_buf* X, size_t x_off, int64_t l
               r_off, (long long)ldr);
   }
   ROM_HIP(hipSetDevice(ctx->device));
-  static const bool detail = getenv("ROMHC_PROF_DETAIL") != nullptr;
-  const PolyPlan plan = poly_plan(ctx, M, P);
-  const int ppad = plan.ppad, ngroups = (q + PL_QG - 1) / PL_QG;
+  const SlabPlan plan = rom_slab_plan(ctx, M, P);
+  const int ppad = plan.pad, ngroups = (q + PL_QG - 1) / PL_QG;
   const int qpad_max = (std::min(q, PL_QG) + 15) / 16 * 16;
   const size_t lds = predict_lds(ppad, qpad_max, m, d);
-  if (lds > 64 * 1024 && !ctx->lds_optin_poly_predict) {
-    ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_poly_predict), hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024));
-    ctx->lds_optin_poly_predict = true;
-  }
+  if (lds > 64 * 1024) ROM_TRY(rom_lds_optin(ctx->lds_optin_poly_predict, reinterpret_cast<const void*>(k_poly_predict), 112 * 1024));
   Tmp SS, sums;
   if (sumsq_host) {
     ROM_TRY(SS.get(ctx, size_t(plan.chunks) * q));
@@ -797,15 +696,15 @@ extern "C" int rom_poly_predict(rom_poly* h, rom_buf* X, size_t x_off, int64_t l
   const double* dev = h->dev->p;
   {
     char nm[48];
-    detail ? snprintf(nm, sizeof nm, "poly_predict_P%d_q%d", P, q) : snprintf(nm, sizeof nm, "poly_predict");
+    rom_prof_name(nm, sizeof nm, "poly_predict", "_P%d_q%d", P, q);
     ROM_PROF(ctx, nm, 2.0 * M * ppad * double(ngroups > 1 ? ngroups * PL_QG : qpad_max), 8.0 * M * (m + q * (Yref ? 2.0 : 1.0)));
-    k_poly_predict<<<dim3(plan.chunks, ngroups), PL_THREADS, lds, ctx->stream>>>(
+    k_poly_predict<<<dim3(plan.chunks, ngroups), SLAB_THREADS, lds, ctx->stream>>>(
         X->p + x_off, ldx, m, d, dev, reinterpret_cast<const unsigned char*>(dev + PL_OFF_TAB), P, ppad, dev + PL_OFF_W, q, M, plan.per_chunk,
         OUT ? OUT->p + o_off : nullptr, ldo, Yref ? Yref->p + r_off : nullptr, ldr, sumsq_host ? SS.p() : nullptr);
   }
   ROM_HIP(hipGetLastError());
   if (sumsq_host) {
-    k_poly_sumsq_finish<<<blocks_for(q), 256, 0, ctx->stream>>>(SS, plan.chunks, q, sums);
+    kb_partials_colsum<<<blocks_for(q), 256, 0, ctx->stream>>>(SS, plan.chunks, q, 1.0, sums);
     ROM_HIP(hipGetLastError());
     ROM_HIP(hipMemcpyAsync(sumsq_host, sums.p(), size_t(q) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   }

@@ -104,6 +104,24 @@ struct rom_buf {
 
 int rom_ctx_scratch(rom_ctx* ctx, size_t n_doubles, double** out);
 
+// A kernel that needs more than the default dynamic LDS opts in once per device: `done` is the flag of that kernel in the
+// context (or FE space).  With device >= 0 that device is made current first.
+int rom_lds_optin(bool& done, const void* kernel, int bytes, int device = -1);
+
+// A tall block (M rows, n <= 96 columns) walked in slabs of SLAB_ROWS rows by one workgroup per CU (rom_slab.h): n padded to
+// 16, the slabs dealt to `chunks` workgroups, per_chunk consecutive slabs each.
+constexpr int SLAB_ROWS = 32;
+struct SlabPlan {
+  int pad, chunks;
+  long long per_chunk;
+};
+SlabPlan rom_slab_plan(const rom_ctx* ctx, long long M, int n);
+
+// ROMHC_PROF_DETAIL (read once): per-shape names in the profile records
+bool rom_prof_detail();
+// nm = base, or under ROMHC_PROF_DETAIL base followed by the formatted suffix
+void rom_prof_name(char* nm, size_t cap, const char* base, const char* suffix_fmt, ...) __attribute__((format(printf, 4, 5)));
+
 // profiling bracket around one kernel launch
 struct ProfScope {
   rom_ctx* ctx;

@@ -51,9 +51,10 @@ def _geo(r, lo):
     return 10.0 ** -np.linspace(0, lo, r)
 
 
-def _case(cid, M, D, dim, values, n=None, mean=False, x_row0=3, v_row0=2, s_row0=1):
+def _case(cid, M, D, dim, values, n=None, mean=False, x_row0=3, v_row0=2, s_row0=1, pad=0):
+    """pad: zero rows past the M rows of the exact block (uncentred cases only): the device call sees M + pad rows."""
     return dict(id=cid, M=M, D=D, dim=dim, values=np.asarray(values, dtype=np.float64), n=dim if n is None else n, mean=mean,
-                x_row0=x_row0, v_row0=v_row0, s_row0=s_row0)
+                x_row0=x_row0, v_row0=v_row0, s_row0=s_row0, pad=pad)
 
 
 CASES = [
@@ -64,13 +65,21 @@ CASES = [
     _case("wide_64x256", 64, 256, 256, _geo(40, 8)),
     _case("t96_cluster", 4096, 64, 96, np.concatenate([_geo(10, 1), np.full(20, 1e-3)]), mean=True),
     _case("t81_n10", 16384, 64, 81, _geo(40, 10), n=10, mean=True),
+    # the smallest shapes at which the slab engine (csrc/rom_slab.h) can go wrong: 16-column tiles, 32-row slabs, chunks of slabs
+    _case("d1", 4, 1, 1, _geo(1, 0)),                               # one tile, one mode
+    _case("d15_33rows", 32, 8, 15, _geo(6, 3), pad=1),              # a partial tile; a second slab of one row
+    _case("d16", 16, 16, 16, _geo(12, 4)),                          # exactly one tile; half a slab
+    _case("d17_31rows", 16, 16, 17, _geo(10, 4), pad=15),           # two column tiles, the second one column wide; 31 rows
+    _case("d65", 64, 64, 65, _geo(40, 6)),                          # five column tiles: a second NT tile for one wave pair only
+    _case("d80_8193", 8192, 32, 80, _geo(30, 6), pad=1),            # two slabs per chunk on 256 CUs; the last chunk: one row
+    _case("d96_1025", 1024, 64, 96, _geo(50, 6), pad=1),            # the fused limit with a one-row last slab
 ]
 
 
 def _truth(case):
     mant, e = _mant(case["values"], case["M"])
     mi = (np.random.default_rng(5).integers(-mant[0], mant[0], size=case["dim"]) // 4) if case["mean"] else None
-    return rf.ExactSVD(case["M"], case["D"], case["dim"], mant, e, seed=1, mean_int=mi)
+    return rf.ExactSVD(case["M"], case["D"], case["dim"], mant, e, seed=1, mean_int=mi, pad=case["pad"])
 
 
 def _sentinel_block(X, before, after=2):
@@ -79,7 +88,7 @@ def _sentinel_block(X, before, after=2):
 
 def run_tall(ctx, case, t):
     """One device call with NaN rows around X, V and S.  Returns sigma, info and the four buffers."""
-    M, dim, n = t.M, t.dim, case["n"]
+    M, dim, n = t.rows, t.dim, case["n"]
     x0, v0, s0 = case["x_row0"], case["v_row0"], case["s_row0"]
     Xb = ctx.upload(_sentinel_block(t.X, x0))
     Vb = ctx.alloc((v0 + n + 2) * dim).fill(np.nan)
@@ -94,7 +103,7 @@ def _same_bits(a, b):
 
 
 def check_truth(case, t, sig, info, V, S):
-    cid, n, M, dim = case["id"], case["n"], t.M, t.dim
+    cid, n, M, dim = case["id"], case["n"], t.M, t.dim    # (M: the rows that carry the block -- zero rows add nothing to a sum)
     s, r = t.s, t.r
     s1 = s[0]
     assert s.min() > 100 * 1e-13 * s1        # (every true value clearly above the noise floor: resolved = r)
@@ -106,7 +115,7 @@ def check_truth(case, t, sig, info, V, S):
     sbound = C * EPS * s1 + M * EPS * s[:k]
     observed(f"pca_tall {cid}: |sigma - s| / (C eps s_1 + M eps s_i)", np.abs(sig[:k] - s[:k]) / sbound, 1.0)
     s_all = np.concatenate([s, np.zeros(1 if r < dim else 0)])
-    U = t.F1[:M] * np.sqrt(t.D)          # column i = s_i u_i (X = F1 F2, V = F2 / sqrt(D))
+    U = t.F1 * np.sqrt(t.D)              # column i = s_i u_i (X = F1 F2, V = F2 / sqrt(D)); t.rows rows
     ratios, sc_ratios = [], []
     i = 0
     while i < k:
@@ -127,7 +136,7 @@ def check_truth(case, t, sig, info, V, S):
             ratios.append(np.linalg.norm(resid, axis=1).max() / abound)
             if hi <= k:
                 ratios.append(np.abs(Vd.T @ Vd - Vt.T @ Vt).max() / abound)
-            ref = t.F1[:M] @ (t.F2 @ Vd.T)
+            ref = t.F1 @ (t.F2 @ Vd.T)
             fro = np.sqrt(np.sum(s ** 2))
             sc_ratios.append(np.linalg.norm(S[:, lo:lo + len(Vd)] - ref, axis=0).max() / (2 * dim * EPS * fro + sbound[lo]))
         i = hi
@@ -200,7 +209,7 @@ def test_small_eig_gram_like_is_relatively_accurate_on_graded_matrices(ctx, n, g
 @pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
 def test_exact_block(ctx, case, monkeypatch):
     t = _truth(case)
-    M, dim, n = t.M, t.dim, case["n"]
+    M, dim, n = t.rows, t.dim, case["n"]
     x0, v0, s0 = case["x_row0"], case["v_row0"], case["s_row0"]
     sig, info, Xb, Vb, Sb, mb = run_tall(ctx, case, t)
     Vall = Vb.download(shape=(v0 + n + 2, dim))

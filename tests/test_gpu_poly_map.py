@@ -6,7 +6,8 @@ test_gpu_pca_tall.py), Phi^ the column-normalised Legendre design matrix formed 
 dot product of length M in any summation order.  numpy.linalg.lstsq on the same Phi is printed next to every device figure.
 
 Cases: the smallest shapes that reach each path of the kernels -- P padded to 16 with M no multiple of 32; P = 70 over several
-workgroup chunks with a 5-row tail; P = 91 with two target groups and q no multiple of 16; one input at degree 8; fewer rows
+workgroup chunks with a 5-row tail; P = 91 with two target groups and q no multiple of 16; one input at degree 8; P = 15, 16
+and 17 around one 16-column tile with one-row last slabs; fewer rows
 than terms (rank < P); two inputs that agree to 2^-25 (kappa = 7e7: the re-whitening and a third pass).  X and Y are column ranges of ONE wider block whose other entries, and the sentinel rows around it, are
 NaN: the NaNs and both inputs must come back bit for bit.  Real scores: the (2, 2) / N = 5 problem of the reference's
 experiment, 3000 samples."""
@@ -30,7 +31,14 @@ CASES = [("p10_m300",       3, 2, 300, 5),
          ("p70_m4101",      4, 4, 4101, 5),
          ("p91_q100",       12, 2, 2048, 100),
          ("p9_deg8",        1, 8, 257, 1),
+         # tile and slab edges of the slab engine (csrc/rom_slab.h): P = 16 is one tile, with a full target group and two slabs
+         # per chunk of which the last holds one row; P = 17 pads to 32, with a second target group of one column and a one-row
+         # second slab; P = 15 with q = 17: q_pad = 32 with 15 padded columns
+         ("p16_q96_m8193",  15, 1, 8193, 96),
+         ("p17_q97_m33",    16, 1, 33, 97),
+         ("p15_q17_m1025",  2, 4, 1025, 17),
          ("p84_m31_rank",   6, 3, 31, 3)]
+FULL_RANK = CASES[:-1]
 
 
 @pytest.fixture(scope="module")
@@ -108,7 +116,7 @@ def _ratio(pred, truth, Ytrain, kappa, M):
     return err / np.maximum(pt.rms(Ytrain), 1e-300) / (C * EPS * kappa + M * EPS)
 
 
-@pytest.mark.parametrize("cid,m,d,M,q", CASES[:4], ids=[c[0] for c in CASES[:4]])
+@pytest.mark.parametrize("cid,m,d,M,q", FULL_RANK, ids=[c[0] for c in FULL_RANK])
 def test_synthetic_full_rank(ctx, cid, m, d, M, q, monkeypatch):
     X, Y0, Y1, pw, c, h = _synthetic(m, d, M, q, seed=m * 100 + d)
     for tag, Y in (("exact", Y0), ("noisy", Y1)):
@@ -141,7 +149,7 @@ def test_synthetic_full_rank(ctx, cid, m, d, M, q, monkeypatch):
 
 
 def test_fewer_rows_than_terms(ctx):
-    cid, m, d, M, q = CASES[4]
+    cid, m, d, M, q = CASES[-1]
     X, Y0, Y1, pw, c, h = _synthetic(m, d, M, q, seed=63)
     Phi = pt.features(X[:M], c, h, pw)
     kappa = pt.kappa_normalised(Phi, rank=M)     # (31 rows: the ratio of the largest to the 31st singular value)
