@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "rom_mma.h"
 #include "rom_ops.h"
@@ -28,6 +29,15 @@ __device__ inline void load4_row(const double* __restrict__ row, long long k, lo
   for (int x = 0; x < 4; ++x) v[x] = (k + x < kend) ? row[k + x] : 0.0;
 }
 
+// tile (ty, tx), tx <= ty, number t = ty (ty + 1) / 2 + tx of the lower triangle: a 1-D grid over the tiles on/below the
+// diagonal, so that consecutive block ids (dealt round-robin to the 8 XCDs) all carry work (square-root seed, corrected)
+__device__ __forceinline__ void lower_tile_of(long long t, long long& ty, long long& tx) {
+  ty = (long long)((sqrt(8.0 * double(t) + 1.0) - 1.0) * 0.5);
+  while (ty * (ty + 1) / 2 > t) --ty;
+  while ((ty + 1) * (ty + 2) / 2 <= t) ++ty;
+  tx = t - ty * (ty + 1) / 2;
+}
+
 // grid (ceil(n/64), ceil(m/64), splits).  Each z-slice handles K range [z*kper, min(K,(z+1)*kper)).
 // splits == 1: writes alpha*acc + beta*C directly; else writes the raw partial tile to `part`
 // ([z][m][n], ld n) for the deterministic reduction kernel below.
@@ -38,16 +48,9 @@ __global__ __launch_bounds__(256) void k_gemm_nt(long long m, long long n, long 
                                                  double* __restrict__ C, long long ldc, double* __restrict__ part,
                                                  int lower_only) {
   __shared__ __align__(16) double stage[STAGE_TOTAL];
-  // Gram (lower_only): 1-D grid over the tiles on/below the diagonal, so that consecutive block ids
-  // (dealt round-robin to the 8 XCDs) all carry work; the strict upper triangle comes from the mirror pass
+  // Gram (lower_only): the tiles on/below the diagonal; the strict upper triangle comes from the mirror pass
   long long ty = blockIdx.y, tx = blockIdx.x;
-  if (lower_only) {
-    const long long t = blockIdx.x;
-    ty = (long long)((sqrt(8.0 * double(t) + 1.0) - 1.0) * 0.5);
-    while (ty * (ty + 1) / 2 > t) --ty;
-    while ((ty + 1) * (ty + 2) / 2 <= t) ++ty;
-    tx = t - ty * (ty + 1) / 2;
-  }
+  if (lower_only) lower_tile_of(blockIdx.x, ty, tx);
   const WavePos wp;
   const long long r0 = ty * 64LL, c0 = tx * 64LL;
   const long long kbeg = blockIdx.z * kper, kend = std::min<long long>(K, kbeg + kper);
@@ -112,17 +115,33 @@ __global__ void k_mirror_lower(long long n, double* __restrict__ C, long long ld
   if (c > r) C[r * ldc + c] = C[c * ldc + r];
 }
 
-// (lower_only == 2: the partials are those of the TRANSPOSED product, C[c, r] receives element (r, c))
+// ============================================================================================
+// split-K: the plan and the deterministic reduction  C = alpha sum_z part[z] + beta C
+// ============================================================================================
+// what every reducer does with entry idx = r n + c once the partials are in: nothing for an entry of a 64-tile above the
+// diagonal (lower_only == 1: those partials were never written); sum() -- called by all lanes that get here -- and, in
+// the lanes that are `writer`, C = alpha s + beta C (lower_only == 2: the partials are those of the TRANSPOSED product,
+// C[c, r] receives element (r, c))
+template <class Sum>
+__device__ __forceinline__ void splitk_epilogue(long long idx, long long n, double alpha, double beta, double* C,
+                                                long long ldc, int lower_only, bool writer, Sum sum) {
+  if (lower_only == 1 && (idx % n) / 64 > (idx / n) / 64) return;
+  const double s = sum();
+  if (!writer) return;
+  const long long r = idx / n, c = idx % n;
+  double* p = lower_only == 2 ? C + c * ldc + r : C + r * ldc + c;
+  *p = beta == 0.0 ? alpha * s : alpha * s + beta * *p;
+}
+
 __global__ void k_splitk_reduce(long long m, long long n, int splits, double alpha, const double* __restrict__ part,
                                 double beta, double* __restrict__ C, long long ldc, int lower_only) {
   long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (idx >= m * n) return;
-  if (lower_only == 1 && (idx % n) / 64 > (idx / n) / 64) return;
-  double s = 0.0;
-  for (int z = 0; z < splits; ++z) s += part[z * m * n + idx];
-  long long r = idx / n, c = idx % n;
-  double* p = lower_only == 2 ? C + c * ldc + r : C + r * ldc + c;
-  *p = beta == 0.0 ? alpha * s : alpha * s + beta * *p;
+  splitk_epilogue(idx, n, alpha, beta, C, ldc, lower_only, true, [&] {
+    double s = 0.0;
+    for (int z = 0; z < splits; ++z) s += part[z * m * n + idx];
+    return s;
+  });
 }
 
 // the same reduction for outputs of a few thousand to tens of thousands of entries with dozens of splits (the b x M
@@ -142,11 +161,8 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_quad(long long m, long lo
   red[g][e] = s;
   __syncthreads();
   if (g != 0 || !in) return;
-  if (lower_only == 1 && (idx % n) / 64 > (idx / n) / 64) return;
-  s = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-  const long long r = idx / n, c = idx % n;
-  double* p = lower_only == 2 ? C + c * ldc + r : C + r * ldc + c;
-  *p = beta == 0.0 ? alpha * s : alpha * s + beta * *p;
+  splitk_epilogue(idx, n, alpha, beta, C, ldc, lower_only, true,
+                  [&] { return ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]; });
 }
 
 // the same reduction with one WAVE per output element (the splits are spread over its lanes): thin outputs with hundreds
@@ -156,17 +172,336 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_wave(long long m, long lo
                                                             double* __restrict__ C, long long ldc, int lower_only) {
   const long long idx = blockIdx.x * 4LL + (threadIdx.x >> 6);
   if (idx >= m * n) return;
-  if (lower_only == 1 && (idx % n) / 64 > (idx / n) / 64) return;
   const int lane = threadIdx.x & 63;
-  // fixed order: lane l sums splits l, l + 64, ...; then the lanes are folded pairwise -- deterministic
-  double s = 0.0;
-  for (int z = lane; z < splits; z += 64) s += part[z * m * n + idx];
+  splitk_epilogue(idx, n, alpha, beta, C, ldc, lower_only, lane == 0, [&] {
+    // fixed order: lane l sums splits l, l + 64, ...; then the lanes are folded pairwise -- deterministic
+    double s = 0.0;
+    for (int z = lane; z < splits; z += 64) s += part[z * m * n + idx];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-  if (lane == 0) {
-    const long long r = idx / n, c = idx % n;
-    double* p = lower_only == 2 ? C + c * ldc + r : C + r * ldc + c;
-    *p = beta == 0.0 ? alpha * s : alpha * s + beta * *p;
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    return s;
+  });
+}
+
+// the reducer of a product with `splits` partial tiles: quad, wave or the entry-per-thread form.  plain_only: the caller's
+// sums keep the order of the entry-per-thread form whatever the shape (the quad and wave forms add in another order)
+static int launch_splitk_reduce(rom_ctx* ctx, long long m, long long n, int splits, double alpha, const double* part,
+                                double beta, double* C, long long ldc, int lower_only, bool plain_only = false) {
+  {
+    ROM_PROF(ctx, "splitk_reduce", double(splits) * m * n, 8.0 * double(splits + 1) * m * n);
+    if (!plain_only && splits >= 8 && m * n >= 4096 && m * n <= (1 << 20))
+      k_splitk_reduce_quad<<<unsigned((m * n + 63) / 64), 256, 0, ctx->stream>>>(m, n, splits, alpha, part, beta, C, ldc, lower_only);
+    else if (!plain_only && splits >= 16 && m * n <= 65536)
+      k_splitk_reduce_wave<<<unsigned((m * n + 3) / 4), 256, 0, ctx->stream>>>(m, n, splits, alpha, part, beta, C, ldc, lower_only);
+    else
+      k_splitk_reduce<<<unsigned((m * n + 255) / 256), 256, 0, ctx->stream>>>(m, n, splits, alpha, part, beta, C, ldc, lower_only);
+  }
+  ROM_HIP(hipGetLastError());
+  return ROM_OK;
+}
+
+// K in `want` slices: the slice length *kper (a multiple of the chunk BK) and the number of slices that are not empty
+// (k == 0, which only the general NT route lets through: one empty slice of BK)
+static long long splitk_plan(long long k, long long want, long long* kper) {
+  *kper = ((k + want - 1) / want + BK - 1) / BK * BK;
+  if (*kper <= 0) *kper = BK;
+  return std::max<long long>(1, (k + *kper - 1) / *kper);
+}
+
+// ============================================================================================
+// The LDS-DMA pipeline of k_gram128 and the two thin kernels below.
+// ============================================================================================
+// The K chunks (16 wide) of an operand with K-contiguous rows go from global memory straight into LDS with
+// global_load_lds_dwordx4 (no staging registers, no ds_write): one instruction moves 8 rows x 128 bytes, lane -> row
+// lane >> 3, 16-byte unit lane & 7.  The DMA writes rows back to back (no padding possible), so a row's eight units are
+// stored at position u ^ ((row >> 1) & 7), which makes the MFMA fragment reads conflict free.  Rows behind the matrix
+// are clamped to its last row (their products are not stored).  Two slots, chunk ch + 1 in flight under the MFMAs of
+// chunk ch.  The tail of K (at most 15 columns of the last split) goes through registers, zero padded to one chunk.
+
+// one DMA instruction: 16 bytes per lane from base (uniform) + voff (lane) to LDS at lds (uniform) + 16 lane
+__device__ __forceinline__ void dma16(unsigned lds, const char* base, unsigned voff) {
+  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(__builtin_amdgcn_readfirstlane(lds)),
+               "v"(voff), "s"(base)
+               : "memory", "m0");
+}
+
+// byte offset inside its 128-byte row of the element a lane with k-quarter kq reads at k = 4 kki + kq of a tile row with
+// (row & 15) == fr: logical unit 2 kki + (kq >> 1), stored at that ^ ((row >> 1) & 7) = that ^ (fr >> 1)
+__device__ __forceinline__ unsigned frag_unit(int kki, int kq, int fr) {
+  return unsigned((((2 * kki) ^ (kq >> 1) ^ (fr >> 1)) << 4) + (kq & 1) * 8);
+}
+// N fragments `stride` bytes apart
+template <int N>
+__device__ __forceinline__ void lds_frags(const char* p, int stride, double (&f)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) f[i] = *reinterpret_cast<const double*>(p + i * stride);
+}
+
+// lane offset (bytes, behind a uniform base at row 0) of the DMA that brings in tile row rl = 8 x + (lane >> 3): `row`
+// is rl clamped to the operand, the stored unit lane & 7 holds the logical unit (lane & 7) ^ ((rl >> 1) & 7).  (With
+// rl = 32 w + 8 q + (lane >> 3) that swizzle is (4 (q & 1) + (lane >> 4)) & 7, the form k_gram128 was first written in.)
+__device__ __forceinline__ unsigned dma_row_offset(int rl, long long row, long long ld, int lane) {
+  return unsigned(row * ld * 8) + unsigned(((lane & 7) ^ ((rl >> 1) & 7)) * 16);  // (rows * ld * 8 < 2^32: checked on the host)
+}
+// a wave's Q instructions for tile rows row0 .. row0 + 8 Q - 1; `last`: the last row of the operand, relative to the tile
+template <int Q>
+__device__ __forceinline__ void dma_row_offsets(unsigned (&vo)[Q], int row0, int lane, long long last, long long ld) {
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int rl = row0 + 8 * q + (lane >> 3);
+    vo[q] = dma_row_offset(rl, std::min<long long>(rl, last), ld, lane);
+  }
+}
+// the Q instructions: 8 Q tile rows to LDS from `lds_row0` on
+template <int Q>
+__device__ __forceinline__ void dma_rows(unsigned lds_row0, const char* base, const unsigned (&vo)[Q]) {
+#pragma unroll
+  for (int q = 0; q < Q; ++q) dma16(lds_row0 + q * 1024, base, vo[q]);
+}
+
+template <int MI, int NJ>
+__device__ __forceinline__ void acc_zero(d4_t (&acc)[MI][NJ]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
+}
+
+// the main loop over nfull chunks: issue(slot) starts the DMA of the next chunk into a slot (and steps its own pointers),
+// frags(slot, kki, af, bf) reads the fragments of k-step kki; the fragments of k-step j + 1 are read before the MFMAs
+// of step j
+template <int MI, int NJ, class Issue, class Frags>
+__device__ __forceinline__ void dma_mainloop(int nfull, d4_t (&acc)[MI][NJ], Issue issue, Frags frags) {
+  if (nfull <= 0) return;
+  issue(0);
+  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  double af[2][MI], bf[2][NJ];
+  frags(0, 0, af[0], bf[0]);
+  for (int ch = 0; ch < nfull; ++ch) {
+    const int slot = ch & 1;
+    if (ch + 1 < nfull) issue(slot ^ 1);  // (everybody left that slot at the barrier behind chunk ch - 1)
+#pragma unroll
+    for (int kki = 0; kki < 4; ++kki) {
+      const int pb = kki & 1;
+      if (kki < 3) frags(slot, kki + 1, af[pb ^ 1], bf[pb ^ 1]);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[pb][i], bf[pb][j], acc[i][j], 0, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // chunk ch + 1 is in LDS for everybody
+    if (ch + 1 < nfull) frags(slot ^ 1, 0, af[0], bf[0]);
+  }
+}
+
+// ---- the last columns of K (< 16), zero padded to one chunk, through registers ----
+// ROWS rows of X from row r0 (those below `rows`) at columns k0 .. kend - 1 into st[ROWS][LDK]: lane -> k (t & 15),
+// thread t handles rows (t >> 4) + 16 x
+template <int ROWS>
+__device__ __forceinline__ void tail_stage_rows(double* st, const double* X, long long ld, long long r0,
+                                                long long rows, long long k0, long long kend) {
+  const int sk = threadIdx.x & 15, sr0 = threadIdx.x >> 4;
+  const long long k = k0 + sk;
+#pragma unroll
+  for (int x = 0; x < ROWS / 16; ++x) {
+    const long long r = r0 + sr0 + 16 * x;
+    st[(sr0 + 16 * x) * LDK + sk] = (r < rows && k < kend) ? X[r * ld + k] : 0.0;
+  }
+}
+// the 4 k-steps of a staged chunk: A fragments 16 rows of LDK apart, B element (kk, j) at pb[kk * bk + j * bj]
+template <int MI, int NJ>
+__device__ __forceinline__ void tail_mma(const double* pa, const double* pb, int bk, int bj, d4_t (&acc)[MI][NJ]) {
+#pragma unroll
+  for (int kk = 0; kk < BK; kk += 4) {
+    double af[MI], bf[NJ];
+#pragma unroll
+    for (int i = 0; i < MI; ++i) af[i] = pa[i * 16 * LDK + kk];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bf[j] = pb[kk * bk + j * bj];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
+  }
+}
+// the tail of an NT product: st = [A RA x LDK | B 128 x LDK] doubles (over the slots: the main loop is done); the wave's
+// fragments begin at rows arow / brow of the two parts
+template <int RA, int MI, int NJ>
+__device__ __forceinline__ void nt_tail(double* st, const double* A, long long lda, long long ra0, long long ma,
+                                        const double* B, long long ldb, long long rb0, long long nb,
+                                        long long k0, long long kend, int arow, int brow, int kq, d4_t (&acc)[MI][NJ]) {
+  tail_stage_rows<RA>(st, A, lda, ra0, ma, k0, kend);
+  tail_stage_rows<128>(st + RA * LDK, B, ldb, rb0, nb, k0, kend);
+  __syncthreads();
+  tail_mma(st + arow * LDK + kq, st + RA * LDK + brow * LDK + kq, 1, 16 * LDK, acc);
+}
+
+// raw partial tile of K slice blockIdx.z: part[z][m][n]; the wave's accumulators begin at (r0, c0)
+template <int MI, int NJ>
+__device__ __forceinline__ void store_partial(double* part, long long m, long long n, long long r0,
+                                              long long c0, int lane, const d4_t (&acc)[MI][NJ]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const long long r = r0 + i * 16 + (lane >> 4) + 4 * g;
+      if (r >= m) continue;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const long long c = c0 + j * 16 + (lane & 15);
+        if (c < n) part[(blockIdx.z * m + r) * n + c] = acc[i][j][g];
+      }
+    }
+}
+
+// ============================================================================================
+// THIN contractions against a snapshot block (round 3): one operand has at most 64 rows (sketches, modes, basis
+// vectors), the other is the (M, dim) block -- HBM bound: the block should stream through ONCE at the rate of a copy.
+// The 64 x 64 register-staged engine above reaches 2.4-3.0 TB/s on these shapes; the two kernels below take their
+// operand chunks by LDS-DMA like k_gram128 (no staging registers, 128-row / 128-column workgroup tiles: twice the bytes
+// in flight per instruction issued) and give a wave only the 16-row blocks of the thin operand that carry data
+// (MI = ceil(m / 16): the fp64 MFMA rate would bound a 64-row padded product at ~4.3 TB/s).
+// ============================================================================================
+// ---- NT: part[z][m][n] = A[m, Kz] B[n, Kz]^T, m <= 64, K snapshot-long (split over z) --------------------------------
+// Workgroup: all rows of A x 128 rows of B; wave w: A rows 16 w .. 16 w + 15 and B rows 32 w .. 32 w + 31 of the DMA,
+// accumulators [MI][2].  Slot = {A: 64 rows x 128 B | B: 128 rows x 128 B}.
+constexpr int TN_A = 64 * 128;              // bytes
+constexpr int TN_SLOT = TN_A + 128 * 128;   // 24,576 B; two slots: three workgroups per CU
+// (No __launch_bounds__(256) on purpose: this kernel has always been compiled for the default bound of 1024 threads -- a
+// forward declaration without the attribute used to sit above its launcher and won.  Under that bound the accumulators
+// stay in VGPRs (46 .. 106 of them); with 256 the allocator moves them to AGPRs, as in k_gemm_nn_thin, whose main loop
+// pays v_accvgpr copies for it.  Changing it is a kernel change to be measured, not part of sharing the pipeline.)
+template <int MI>
+__global__ void k_gemm_nt_thin(long long m, long long n, long long K, long long kper, const double* __restrict__ A, long long lda,
+                               const double* __restrict__ B, long long ldb, double* __restrict__ part) {
+  __shared__ __align__(16) char lds[2 * TN_SLOT];
+  const unsigned lds0 = unsigned(size_t((__attribute__((address_space(3))) char*)lds));
+  const long long c0 = blockIdx.x * 128LL;
+  const long long kbeg = blockIdx.z * kper, kend = std::min<long long>(K, kbeg + kper);
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fr = lane & 15, kq = lane >> 4;
+  d4_t acc[MI][2];
+  acc_zero(acc);
+  const int nfull = int((kend - kbeg) / BK), rem = int((kend - kbeg) % BK);
+  unsigned fa[4], fb[4], voA[2], voB[4];
+#pragma unroll
+  for (int kki = 0; kki < 4; ++kki) {
+    const unsigned uo = frag_unit(kki, kq, fr);
+    fa[kki] = unsigned(fr * 128) + uo;
+    fb[kki] = unsigned(TN_A + (w * 32 + fr) * 128) + uo;
+  }
+  dma_row_offsets(voA, 16 * w, lane, m - 1, lda);
+  dma_row_offsets(voB, 32 * w, lane, n - 1 - c0, ldb);
+  const char* sA = reinterpret_cast<const char*>(A + kbeg);
+  const char* sB = reinterpret_cast<const char*>(B + c0 * ldb + kbeg);
+  dma_mainloop(
+      nfull, acc,
+      [&](int slot) {
+        const unsigned sl = lds0 + unsigned(slot) * TN_SLOT;
+        dma_rows(sl + unsigned(16 * w) * 128u, sA, voA);
+        dma_rows(sl + TN_A + unsigned(32 * w) * 128u, sB, voB);
+        sA += BK * 8;
+        sB += BK * 8;
+      },
+      [&](int slot, int kki, double (&af)[MI], double (&bf)[2]) {
+        lds_frags(lds + slot * TN_SLOT + fa[kki], 2048, af);
+        lds_frags(lds + slot * TN_SLOT + fb[kki], 2048, bf);
+      });
+  if (rem > 0)
+    nt_tail<64>(reinterpret_cast<double*>(lds), A, lda, 0, m, B, ldb, c0, n, kbeg + (long long)nfull * BK, kend, fr,
+                w * 32 + fr, kq, acc);
+  store_partial(part, m, n, 0, c0 + w * 32, lane, acc);
+}
+
+// ---- NN: C[m, n0 .. n0 + 128) = alpha A[m, K] B[K, n] + beta C, m <= 64, n snapshot-long (>= 128).  The last tile is
+// shifted left to end at column n (no column of B beyond n is touched) and stores only the columns no other tile owns ----
+// Slot = {A: 64 rows x 16 k (the layout above) | B: 16 k-rows x 128 columns, a k-row = ONE DMA instruction (1 KB), rows
+// 1152 B apart so that the four k-rows a fragment read touches fall into different bank halves}.  Wave w: columns
+// 32 w .. 32 w + 31, accumulators [MI][2].  The last k-rows (K % 16) go through registers, zero padded.
+constexpr int TNN_BROW = 1024 + 128;               // bytes between the k-rows of the B part
+constexpr int TNN_SLOT = TN_A + 16 * TNN_BROW;     // 26,624 B; two slots: three workgroups per CU
+template <int MI>
+__global__ __launch_bounds__(256) void k_gemm_nn_thin(long long m, long long n, long long K, double alpha,
+                                                      const double* __restrict__ A, long long lda, const double* __restrict__ B,
+                                                      long long ldb, double beta, double* __restrict__ C, long long ldc) {
+  __shared__ __align__(16) char lds[2 * TNN_SLOT];
+  const unsigned lds0 = unsigned(size_t((__attribute__((address_space(3))) char*)lds));
+  const long long c_own = blockIdx.x * 128LL;                  // first column this workgroup stores
+  const long long c0 = std::min<long long>(c_own, n - 128);    // first column of its tile
+  // (grid.y > 1: A has more than 64 rows and a short K -- the lift  coefficients x basis : row tile blockIdx.y)
+  const long long r0 = blockIdx.y * 64LL;
+  A += r0 * lda;
+  C += r0 * ldc;
+  m = std::min<long long>(64, m - r0);
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fr = lane & 15, kq = lane >> 4;
+  d4_t acc[MI][2];
+  acc_zero(acc);
+  const int nfull = int(K / BK), rem = int(K % BK);
+  unsigned fa[4], fb[4], voA[2];
+#pragma unroll
+  for (int kki = 0; kki < 4; ++kki) {
+    fa[kki] = unsigned(fr * 128) + frag_unit(kki, kq, fr);
+    fb[kki] = unsigned(TN_A + (4 * kki + kq) * TNN_BROW + (w * 32 + fr) * 8);
+  }
+  dma_row_offsets(voA, 16 * w, lane, m - 1, lda);
+  const unsigned voB = unsigned(lane) * 16u;  // lane -> columns 2 lane, 2 lane + 1 of the tile
+  const char* sA = reinterpret_cast<const char*>(A);
+  const char* sB = reinterpret_cast<const char*>(B + c0);
+  const size_t brow = size_t(ldb) * 8;
+  dma_mainloop(
+      nfull, acc,
+      [&](int slot) {  // (B: wave w brings in k-rows 4 w .. 4 w + 3)
+        const unsigned sl = lds0 + unsigned(slot) * TNN_SLOT;
+        dma_rows(sl + unsigned(16 * w) * 128u, sA, voA);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dma16(sl + TN_A + unsigned(4 * w + q) * unsigned(TNN_BROW), sB + size_t(4 * w + q) * brow, voB);
+        sA += BK * 8;
+        sB += BK * brow;
+      },
+      [&](int slot, int kki, double (&af)[MI], double (&bf)[2]) {
+        lds_frags(lds + slot * TNN_SLOT + fa[kki], 2048, af);
+        lds_frags(lds + slot * TNN_SLOT + fb[kki], 128, bf);
+      });
+  if (rem > 0) {
+    // [A 64 x LDK doubles | B 16 x 144 doubles]: the last k-rows, zero padded to one chunk
+    double* st = reinterpret_cast<double*>(lds);
+    double* stb = st + 64 * LDK;
+    const long long k0 = (long long)nfull * BK;
+    tail_stage_rows<64>(st, A, lda, 0, m, k0, K);
+    const int cc = threadIdx.x & 127, kr0 = threadIdx.x >> 7;
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {
+      const int kr = kr0 + 2 * x;
+      stb[kr * 144 + cc] = kr < rem ? B[(k0 + kr) * ldb + c0 + cc] : 0.0;
+    }
+    __syncthreads();
+    tail_mma(st + fr * LDK + kq, stb + kq * 144 + w * 32 + fr, 144, 16, acc);
+  }
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const long long r = i * 16 + (lane >> 4) + 4 * g;
+      if (r >= m) continue;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const long long c = c0 + w * 32 + j * 16 + (lane & 15);
+        if (c < c_own) continue;
+        double* p = C + r * ldc + c;
+        *p = beta == 0.0 ? alpha * acc[i][j][g] : alpha * acc[i][j][g] + beta * *p;
+      }
+    }
+}
+
+// launch(std::integral_constant<int, MI>): MI = the 16-row blocks of a thin operand of `rows` rows (4 from 49 rows on)
+template <class Launch>
+static void dispatch_mi(int64_t rows, Launch launch) {
+  switch ((rows + 15) / 16) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    default: launch(std::integral_constant<int, 4>{}); break;
   }
 }
 
@@ -175,9 +510,6 @@ static bool no_thin_gemm() {
   static const bool off = getenv("ROMHC_NO_THIN_GEMM") != nullptr;
   return off;
 }
-template <int MI>
-__global__ void k_gemm_nt_thin(long long m, long long n, long long K, long long kper, const double* __restrict__ A, long long lda,
-                               const double* __restrict__ B, long long ldb, double* __restrict__ part);  // (defined below)
 // thin A (m <= 64) against a long K: k_gemm_nt_thin over 128-row tiles of B x split-K, then the deterministic reduction
 // transposed != 0: (A, m, lda) is the THIN operand of C^T = A B^T, i.e. the caller's product is C (n x m) = B A^T
 static int launch_gemm_nt_thin(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
@@ -185,9 +517,8 @@ static int launch_gemm_nt_thin(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, do
                                int transposed = 0) {
   const long long tiles = (n + 127) / 128;
   // one full round of the 768 resident workgroups (3 per CU), at least 512 columns of K per workgroup
-  long long splits = std::max<long long>(1, std::min<long long>((768 + tiles - 1) / tiles, k / 512));
-  long long kper = ((k + splits - 1) / splits + BK - 1) / BK * BK;
-  splits = (k + kper - 1) / kper;
+  long long kper = 0;
+  const long long splits = splitk_plan(k, std::max<long long>(1, std::min<long long>((768 + tiles - 1) / tiles, k / 512)), &kper);
   double* part = nullptr;
   ROM_TRY(rom_ctx_scratch(ctx, size_t(splits) * m * n, &part));
   const dim3 grid{unsigned(tiles), 1u, unsigned(splits)};
@@ -195,28 +526,12 @@ static int launch_gemm_nt_thin(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, do
     char nm[64];
     rom_prof_name(nm, sizeof nm, prof_name, "_thin_%lldx%lldx%lld_s%lld", (long long)m, (long long)n, (long long)k, splits);
     ROM_PROF(ctx, nm, 2.0 * m * n * k, 8.0 * (double(m) * k + double(n) * k + double(splits) * m * n));
-    switch ((m + 15) / 16) {
-      case 1: k_gemm_nt_thin<1><<<grid, 256, 0, ctx->stream>>>(m, n, k, kper, A, lda, B, ldb, part); break;
-      case 2: k_gemm_nt_thin<2><<<grid, 256, 0, ctx->stream>>>(m, n, k, kper, A, lda, B, ldb, part); break;
-      case 3: k_gemm_nt_thin<3><<<grid, 256, 0, ctx->stream>>>(m, n, k, kper, A, lda, B, ldb, part); break;
-      default: k_gemm_nt_thin<4><<<grid, 256, 0, ctx->stream>>>(m, n, k, kper, A, lda, B, ldb, part); break;
-    }
+    dispatch_mi(m, [&](auto mi) {
+      k_gemm_nt_thin<decltype(mi)::value><<<grid, 256, 0, ctx->stream>>>(m, n, k, kper, A, lda, B, ldb, part);
+    });
   }
   ROM_HIP(hipGetLastError());
-  {
-    ROM_PROF(ctx, "splitk_reduce", double(splits) * m * n, 8.0 * double(splits + 1) * m * n);
-    if (splits >= 8 && m * n >= 4096 && m * n <= (1 << 20))
-      k_splitk_reduce_quad<<<unsigned((m * n + 63) / 64), 256, 0, ctx->stream>>>(m, n, int(splits), alpha, part, beta, C, ldc,
-                                                                                transposed ? 2 : 0);
-    else if (splits >= 16 && m * n <= 65536)
-      k_splitk_reduce_wave<<<unsigned((m * n + 3) / 4), 256, 0, ctx->stream>>>(m, n, int(splits), alpha, part, beta, C, ldc,
-                                                                               transposed ? 2 : 0);
-    else
-      k_splitk_reduce<<<unsigned((m * n + 255) / 256), 256, 0, ctx->stream>>>(m, n, int(splits), alpha, part, beta, C, ldc,
-                                                                              transposed ? 2 : 0);
-  }
-  ROM_HIP(hipGetLastError());
-  return ROM_OK;
+  return launch_splitk_reduce(ctx, m, n, int(splits), alpha, part, beta, C, ldc, transposed ? 2 : 0);
 }
 
 int rom_launch_gemm_nt(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
@@ -238,17 +553,14 @@ int rom_launch_gemm_nt_ex(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double 
     return launch_gemm_nt_thin(ctx, n, m, k, alpha, B, ldb, A, lda, beta, C, ldc, prof_name, 1);
   const long long nt = (m + 63) / 64;
   const long long tiles = lower_only ? nt * (nt + 1) / 2 : nt * ((n + 63) / 64);  // tiles that do work
-  int splits = 1;
+  long long want = 1;
   if (k >= 1024 && tiles < 512) {
     // (a handful of output tiles: the launch is one latency chain per workgroup -- 128 columns of K each instead of 512)
     const long long kmin = tiles <= 4 ? 128 : 512;
-    splits = int(std::min<long long>((768 + tiles - 1) / tiles, (k + kmin - 1) / kmin));
-    splits = std::max(splits, 1);
+    want = std::max<long long>(1, std::min<long long>((768 + tiles - 1) / tiles, (k + kmin - 1) / kmin));
   }
-  long long kper = ((k + splits - 1) / splits + BK - 1) / BK * BK;
-  if (kper <= 0) kper = BK;
-  splits = int((k + kper - 1) / kper);
-  if (splits < 1) splits = 1;
+  long long kper = 0;
+  const int splits = int(splitk_plan(k, want, &kper));
   double* part = nullptr;
   if (splits > 1) ROM_TRY(rom_ctx_scratch(ctx, size_t(splits) * m * n, &part));
   const bool aligned = (lda % 2 == 0) && (ldb % 2 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0) &&
@@ -266,17 +578,7 @@ int rom_launch_gemm_nt_ex(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double 
       k_gemm_nt<false><<<grid, 256, 0, ctx->stream>>>(m, n, k, kper, alpha, A, lda, B, ldb, beta, C, ldc, part, lower_only);
   }
   ROM_HIP(hipGetLastError());
-  if (splits > 1) {
-    ROM_PROF(ctx, "splitk_reduce", double(splits) * m * n, 8.0 * double(splits + 1) * m * n);
-    if (splits >= 8 && m * n >= 4096 && m * n <= (1 << 20))
-      k_splitk_reduce_quad<<<unsigned((m * n + 63) / 64), 256, 0, ctx->stream>>>(m, n, splits, alpha, part, beta, C, ldc, lower_only);
-    else if (splits >= 16 && m * n <= 65536)
-      k_splitk_reduce_wave<<<unsigned((m * n + 3) / 4), 256, 0, ctx->stream>>>(m, n, splits, alpha, part, beta, C, ldc, lower_only);
-    else
-      k_splitk_reduce<<<unsigned((m * n + 255) / 256), 256, 0, ctx->stream>>>(m, n, splits, alpha, part, beta, C, ldc,
-                                                                             lower_only);
-    ROM_HIP(hipGetLastError());
-  }
+  if (splits > 1) ROM_TRY(launch_splitk_reduce(ctx, m, n, splits, alpha, part, beta, C, ldc, lower_only));
   if (lower_only) {
     ROM_PROF(ctx, "mirror_lower", 0, 8.0 * n * n);
     k_mirror_lower<<<unsigned((n * n + 255) / 256), 256, 0, ctx->stream>>>(n, C, ldc);
@@ -304,142 +606,56 @@ extern "C" int rom_gemm_nt(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double
 // snapshot Gram needs once the block no longer fits in the Infinity Cache (C5: 34 GB).
 // 1-D grid over the lower tiles (XCD-balanced) x split-K; partial tiles go to `part`, reduced + mirrored after.
 // ============================================================================================
-// Main loop (round 2): the K chunks (16 wide) of both operands go from global memory straight into LDS with
-// global_load_lds_dwordx4 (no staging registers, no ds_write; 8 instructions per wave and chunk: 8 rows x 128 bytes
-// each), two 32 KB slots, chunk ch + 1 in flight under the 64 MFMAs per wave of chunk ch; a row's eight 16-byte units
-// are stored at position u ^ ((row >> 1) & 7) (the DMA writes rows back to back: no padding possible), which makes the
-// MFMA fragment reads conflict free; the fragments of k-step j + 1 are read before the MFMAs of step j.  Rows behind
-// the matrix are clamped to its last row (their products are not stored).  The tail of K (at most 15 columns of the
-// last split) goes through registers as before.
+// Main loop (round 2): the LDS-DMA pipeline above, 8 instructions per wave and chunk (rows 32 w .. 32 w + 31 of both
+// operands), two 32 KB slots, chunk ch + 1 in flight under the 64 MFMAs per wave of chunk ch.
 constexpr int G128_SLOT = 2 * 128 * 128;  // bytes: 128 rows of A, 128 rows of B, 16 doubles each
 
 __global__ __launch_bounds__(256, 2) void k_gram128(long long m, long long K, long long kper, const double* __restrict__ A,
                                                     long long lda, double* __restrict__ part) {
   __shared__ __align__(16) char lds[2 * G128_SLOT];  // 65,536 B: two workgroups per CU
   const unsigned lds0 = unsigned(size_t((__attribute__((address_space(3))) char*)lds));
-  const long long t = blockIdx.x;
-  long long ty = (long long)((sqrt(8.0 * double(t) + 1.0) - 1.0) * 0.5);
-  while (ty * (ty + 1) / 2 > t) --ty;
-  while ((ty + 1) * (ty + 2) / 2 <= t) ++ty;
-  const long long tx = t - ty * (ty + 1) / 2;
+  long long ty, tx;
+  lower_tile_of(blockIdx.x, ty, tx);
   const long long r0 = ty * 128, c0 = tx * 128;
   const long long kbeg = blockIdx.z * kper, kend = std::min<long long>(K, kbeg + kper);
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wr = w >> 1, wc = w & 1;
   const int fr = lane & 15, kq = lane >> 4;
   d4_t acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
+  acc_zero(acc);
   const int nfull = int((kend - kbeg) / BK), rem = int((kend - kbeg) % BK);
-
-  // ---- fragment addressing: lane (fr, kq) reads row fr (+ 16 i) at k = 4 kki + kq: unit (2 kki + (kq >> 1)) ^ (fr >> 1)
-  unsigned fa[4], fb[4];
+  unsigned fa[4], fb[4], voA[4], voB[4];
 #pragma unroll
-  for (int kki = 0; kki < 4; ++kki) {
-    const unsigned uo = unsigned((((2 * kki) ^ (kq >> 1) ^ (fr >> 1)) << 4) + (kq & 1) * 8);
+  for (int kki = 0; kki < 4; ++kki) {  // lane (fr, kq) reads rows fr + 16 i of its wave's quadrant
+    const unsigned uo = frag_unit(kki, kq, fr);
     fa[kki] = unsigned((wr * 64 + fr) * 128) + uo;
     fb[kki] = unsigned(16384 + (wc * 64 + fr) * 128) + uo;
   }
-#define G_FRAGS(SLOT_, KKI_, AF_, BF_)                                                                  \
-  do {                                                                                                  \
-    const char* pa_ = lds + (SLOT_) * G128_SLOT + fa[KKI_];                                             \
-    const char* pb_ = lds + (SLOT_) * G128_SLOT + fb[KKI_];                                             \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                  \
-      AF_[i_] = *reinterpret_cast<const double*>(pa_ + i_ * 2048);                                      \
-      BF_[i_] = *reinterpret_cast<const double*>(pb_ + i_ * 2048);                                      \
-    }                                                                                                   \
-  } while (0)
-  // ---- DMA addressing: a wave fetches rows 32 w .. 32 w + 31 of both operands, 8 rows per instruction (q = 0..3):
-  // lane -> row 32 w + 8 q + (lane >> 3), stored unit lane & 7 = logical unit (lane & 7) ^ ((4 (q & 1) + (lane >> 4)) & 7)
-  unsigned voA[4], voB[4];  // lane offsets (bytes) behind the scalar bases A + (r0 | c0) * lda + k
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int rl = 32 * w + 8 * q + (lane >> 3);
-    const unsigned u16 = unsigned((((lane & 7) ^ ((4 * (q & 1) + (lane >> 4)) & 7))) * 16);
-    const long long ra = std::min<long long>(rl, m - 1 - r0), rb = std::min<long long>(rl, m - 1 - c0);
-    voA[q] = unsigned(ra * lda * 8) + u16;  // (127 * lda * 8 < 2^32: checked on the host)
-    voB[q] = unsigned(rb * lda * 8) + u16;
-  }
+  dma_row_offsets(voA, 32 * w, lane, m - 1 - r0, lda);  // (127 * lda * 8 < 2^32: checked on the host)
+  dma_row_offsets(voB, 32 * w, lane, m - 1 - c0, lda);
   const char* sA = reinterpret_cast<const char*>(A + r0 * lda + kbeg);
   const char* sB = reinterpret_cast<const char*>(A + c0 * lda + kbeg);
-#define G_DMA(LDS_, BASE_, VOFF_)                                                                                   \
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(__builtin_amdgcn_readfirstlane(LDS_)),    \
-               "v"(VOFF_), "s"(BASE_)                                                                               \
-               : "memory", "m0")
-#define G_ISSUE(SLOT_)                                                                                              \
-  do {                                                                                                              \
-    const unsigned sl_ = lds0 + unsigned(SLOT_) * G128_SLOT + unsigned(w) * 4096;                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) G_DMA(sl_ + q_ * 1024, sA, voA[q_]);                           \
-    _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) G_DMA(sl_ + 16384 + q_ * 1024, sB, voB[q_]);                   \
-    sA += BK * 8;                                                                                                   \
-    sB += BK * 8;                                                                                                   \
-  } while (0)
-  if (nfull > 0) {
-    G_ISSUE(0);
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    double af[2][4], bf[2][4];
-    G_FRAGS(0, 0, af[0], bf[0]);
-    for (int ch = 0; ch < nfull; ++ch) {
-      const int slot = ch & 1;
-      if (ch + 1 < nfull) G_ISSUE(slot ^ 1);  // (everybody left that slot at the barrier behind chunk ch - 1)
+  dma_mainloop(
+      nfull, acc,
+      [&](int slot) {
+        const unsigned sl = lds0 + unsigned(slot) * G128_SLOT + unsigned(w) * 4096;
+        dma_rows(sl, sA, voA);
+        dma_rows(sl + 16384, sB, voB);
+        sA += BK * 8;
+        sB += BK * 8;
+      },
+      [&](int slot, int kki, double (&af)[4], double (&bf)[4]) {
+        const char* pa = lds + slot * G128_SLOT + fa[kki];
+        const char* pb = lds + slot * G128_SLOT + fb[kki];
 #pragma unroll
-      for (int kki = 0; kki < 4; ++kki) {
-        const int pb = kki & 1;
-        if (kki < 3) G_FRAGS(slot, kki + 1, af[pb ^ 1], bf[pb ^ 1]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[pb][i], bf[pb][j], acc[i][j], 0, 0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // chunk ch + 1 is in LDS for everybody
-      if (ch + 1 < nfull) G_FRAGS(slot ^ 1, 0, af[0], bf[0]);
-    }
-  }
-#undef G_ISSUE
-#undef G_DMA
-#undef G_FRAGS
-  if (rem > 0) {
-    // the last columns of K, zero padded to one chunk: lane -> k (t & 15), thread t handles rows (t >> 4) + 16 x
-    double* st = reinterpret_cast<double*>(lds);  // [A 128 x LDK | B 128 x LDK] doubles = 36,864 B
-    const int sk = threadIdx.x & 15, sr0 = threadIdx.x >> 4;
-    const long long k = kbeg + (long long)nfull * BK + sk;
-#pragma unroll
-    for (int x = 0; x < 8; ++x) {
-      const long long ra = r0 + sr0 + 16 * x, rb = c0 + sr0 + 16 * x;
-      st[(sr0 + 16 * x) * LDK + sk] = (ra < m && k < kend) ? A[ra * lda + k] : 0.0;
-      st[128 * LDK + (sr0 + 16 * x) * LDK + sk] = (rb < m && k < kend) ? A[rb * lda + k] : 0.0;
-    }
-    __syncthreads();
-    const double* pa = st + (wr * 64 + fr) * LDK + kq;
-    const double* pb = st + 128 * LDK + (wc * 64 + fr) * LDK + kq;
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      double af[4], bf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[i] = pa[i * 16 * LDK + kk];
-        bf[i] = pb[i * 16 * LDK + kk];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  // raw partial tile: part[z][m][m]
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const long long r = r0 + wr * 64 + i * 16 + (lane >> 4) + 4 * g;
-      if (r >= m) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const long long c = c0 + wc * 64 + j * 16 + (lane & 15);
-        if (c < m) part[(blockIdx.z * m + r) * m + c] = acc[i][j][g];
-      }
-    }
+        for (int i = 0; i < 4; ++i) {  // (A and B by turns: the first MFMA waits for two reads, not three)
+          af[i] = *reinterpret_cast<const double*>(pa + i * 2048);
+          bf[i] = *reinterpret_cast<const double*>(pb + i * 2048);
+        }
+      });
+  if (rem > 0)
+    nt_tail<128>(reinterpret_cast<double*>(lds), A, lda, r0, m, A, lda, c0, m, kbeg + (long long)nfull * BK, kend,
+                 wr * 64 + fr, wc * 64 + fr, kq, acc);  // 36,864 B
+  store_partial(part, m, m, r0 + wr * 64, c0 + wc * 64, lane, acc);
 }
 
 // C = sum_z part[z] on the lower 128-tiles, mirrored into the strict upper triangle
@@ -460,15 +676,15 @@ static int launch_gram128(rom_ctx* ctx, int64_t m, int64_t k, const double* A, i
   const long long nt = (m + 127) / 128, tiles = nt * (nt + 1) / 2;
   // split K so that the grid fills whole rounds of the 512 resident workgroups (2 per CU) with little tail
   const long long smax = std::max<long long>(1, std::min<long long>(64, (k + 2047) / 2048));
-  int splits = 1;
+  long long want = 1;
   double best = 1e30;
   for (long long sp = 1; sp <= smax; ++sp) {
     const double rounds = std::ceil(double(tiles * sp) / 512.0);
     const double cost = rounds / double(sp) + 0.002 * sp;  // time ~ rounds * (K / sp); mild penalty on partial traffic
-    if (cost < best) { best = cost; splits = int(sp); }
+    if (cost < best) { best = cost; want = sp; }
   }
-  long long kper = ((k + splits - 1) / splits + BK - 1) / BK * BK;
-  splits = int((k + kper - 1) / kper);
+  long long kper = 0;
+  const int splits = int(splitk_plan(k, want, &kper));
   double* part = nullptr;
   ROM_TRY(rom_ctx_scratch(ctx, size_t(splits) * m * m, &part));
   {
@@ -500,283 +716,6 @@ extern "C" int rom_gram(rom_ctx* ctx, int64_t m, int64_t k, rom_buf* A, size_t a
   ROM_CHECK(c_off + size_t(m - 1) * ldc + m <= C->n, "rom_gram: C out of range");
   return rom_launch_gram(ctx, m, k, A->p + a_off, lda, C->p + c_off, ldc);
 }
-
-// ============================================================================================
-// THIN contractions against a snapshot block (round 3): one operand has at most 64 rows (sketches, modes, basis
-// vectors), the other is the (M, dim) block -- HBM bound: the block should stream through ONCE at the rate of a copy.
-// The 64 x 64 register-staged engine above reaches 2.4-3.0 TB/s on these shapes; the two kernels below take their
-// operand chunks by LDS-DMA like k_gram128 (no staging registers, 128-row / 128-column workgroup tiles: twice the bytes
-// in flight per instruction issued) and give a wave only the 16-row blocks of the thin operand that carry data
-// (MI = ceil(m / 16): the fp64 MFMA rate would bound a 64-row padded product at ~4.3 TB/s).
-// ============================================================================================
-#define T_DMA(LDS_, BASE_, VOFF_)                                                                                   \
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(__builtin_amdgcn_readfirstlane(LDS_)),    \
-               "v"(VOFF_), "s"(BASE_)                                                                               \
-               : "memory", "m0")
-
-// ---- NT: part[z][m][n] = A[m, Kz] B[n, Kz]^T, m <= 64, K snapshot-long (split over z) --------------------------------
-// Workgroup: all rows of A x 128 rows of B; wave w: B rows 32 w .. 32 w + 31, accumulators [MI][2].  Slot = {A: 64 rows x
-// 128 B | B: 128 rows x 128 B}, a row's eight 16-byte units at position u ^ ((row >> 1) & 7) (k_gram128's layout); two
-// slots, chunk ch + 1 in flight under the MFMAs of chunk ch.  Rows behind the operands are clamped (not stored).
-constexpr int TN_A = 64 * 128;              // bytes
-constexpr int TN_SLOT = TN_A + 128 * 128;   // 24,576 B; two slots: three workgroups per CU
-template <int MI>
-__global__ __launch_bounds__(256) void k_gemm_nt_thin(long long m, long long n, long long K, long long kper,
-                                                      const double* __restrict__ A, long long lda,
-                                                      const double* __restrict__ B, long long ldb, double* __restrict__ part) {
-  __shared__ __align__(16) char lds[2 * TN_SLOT];
-  const unsigned lds0 = unsigned(size_t((__attribute__((address_space(3))) char*)lds));
-  const long long c0 = blockIdx.x * 128LL;
-  const long long kbeg = blockIdx.z * kper, kend = std::min<long long>(K, kbeg + kper);
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int fr = lane & 15, kq = lane >> 4;
-  d4_t acc[MI][2];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
-  const int nfull = int((kend - kbeg) / BK), rem = int((kend - kbeg) % BK);
-  unsigned fa[4], fb[4];
-#pragma unroll
-  for (int kki = 0; kki < 4; ++kki) {
-    const unsigned uo = unsigned((((2 * kki) ^ (kq >> 1) ^ (fr >> 1)) << 4) + (kq & 1) * 8);
-    fa[kki] = unsigned(fr * 128) + uo;
-    fb[kki] = unsigned(TN_A + (w * 32 + fr) * 128) + uo;
-  }
-#define TN_FRAGS(SLOT_, KKI_, AF_, BF_)                                                                    \
-  do {                                                                                                     \
-    const char* pa_ = lds + (SLOT_) * TN_SLOT + fa[KKI_];                                                  \
-    const char* pb_ = lds + (SLOT_) * TN_SLOT + fb[KKI_];                                                  \
-    _Pragma("unroll") for (int i_ = 0; i_ < MI; ++i_) AF_[i_] = *reinterpret_cast<const double*>(pa_ + i_ * 2048); \
-    _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_) BF_[j_] = *reinterpret_cast<const double*>(pb_ + j_ * 2048);  \
-  } while (0)
-  // DMA: 8 rows per instruction; wave w fetches A rows 16 w + 8 q (q < 2) and B rows 32 w + 8 q (q < 4)
-  unsigned voA[2], voB[4];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int rl = 16 * w + 8 * q + (lane >> 3);
-    const long long ra = std::min<long long>(rl, m - 1);
-    voA[q] = unsigned(ra * lda * 8) + unsigned(((lane & 7) ^ ((rl >> 1) & 7)) * 16);
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int rl = 32 * w + 8 * q + (lane >> 3);
-    const long long rb = std::min<long long>(rl, n - 1 - c0);
-    voB[q] = unsigned(rb * ldb * 8) + unsigned(((lane & 7) ^ ((rl >> 1) & 7)) * 16);
-  }
-  const char* sA = reinterpret_cast<const char*>(A + kbeg);
-  const char* sB = reinterpret_cast<const char*>(B + c0 * ldb + kbeg);
-#define TN_ISSUE(SLOT_)                                                                                      \
-  do {                                                                                                       \
-    const unsigned sl_ = lds0 + unsigned(SLOT_) * TN_SLOT;                                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) T_DMA(sl_ + unsigned(16 * w + 8 * q_) * 128u, sA, voA[q_]);        \
-    _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) T_DMA(sl_ + TN_A + unsigned(32 * w + 8 * q_) * 128u, sB, voB[q_]); \
-    sA += BK * 8;                                                                                            \
-    sB += BK * 8;                                                                                            \
-  } while (0)
-  if (nfull > 0) {
-    TN_ISSUE(0);
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    double af[2][MI], bf[2][2];
-    TN_FRAGS(0, 0, af[0], bf[0]);
-    for (int ch = 0; ch < nfull; ++ch) {
-      const int slot = ch & 1;
-      if (ch + 1 < nfull) TN_ISSUE(slot ^ 1);  // (everybody left that slot at the barrier behind chunk ch - 1)
-#pragma unroll
-      for (int kki = 0; kki < 4; ++kki) {
-        const int pb = kki & 1;
-        if (kki < 3) TN_FRAGS(slot, kki + 1, af[pb ^ 1], bf[pb ^ 1]);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[pb][i], bf[pb][j], acc[i][j], 0, 0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // chunk ch + 1 is in LDS for everybody
-      if (ch + 1 < nfull) TN_FRAGS(slot ^ 1, 0, af[0], bf[0]);
-    }
-  }
-#undef TN_ISSUE
-#undef TN_FRAGS
-  if (rem > 0) {
-    // the last columns of K (< 16), zero padded to one chunk, through registers: [A 64 x LDK | B 128 x LDK] doubles
-    double* st = reinterpret_cast<double*>(lds);
-    const int sk = threadIdx.x & 15, sr0 = threadIdx.x >> 4;
-    const long long k = kbeg + (long long)nfull * BK + sk;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const long long ra = sr0 + 16 * x;
-      st[ra * LDK + sk] = (ra < m && k < kend) ? A[ra * lda + k] : 0.0;
-    }
-#pragma unroll
-    for (int x = 0; x < 8; ++x) {
-      const long long rb = c0 + sr0 + 16 * x;
-      st[64 * LDK + (sr0 + 16 * x) * LDK + sk] = (rb < n && k < kend) ? B[rb * ldb + k] : 0.0;
-    }
-    __syncthreads();
-    const double* pa = st + fr * LDK + kq;
-    const double* pb = st + 64 * LDK + (w * 32 + fr) * LDK + kq;
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      double af[MI], bf[2];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[i] = pa[i * 16 * LDK + kk];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bf[j] = pb[j * 16 * LDK + kk];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const long long r = i * 16 + (lane >> 4) + 4 * g;
-      if (r >= m) continue;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const long long c = c0 + w * 32 + j * 16 + (lane & 15);
-        if (c < n) part[(blockIdx.z * m + r) * n + c] = acc[i][j][g];
-      }
-    }
-}
-
-// ---- NN: C[m, n0 .. n0 + 128) = alpha A[m, K] B[K, n] + beta C, m <= 64, n snapshot-long (>= 128).  The last tile is
-// shifted left to end at column n (no column of B beyond n is touched) and stores only the columns no other tile owns ----
-// Slot = {A: 64 rows x 16 k (the layout above) | B: 16 k-rows x 128 columns, a k-row = ONE DMA instruction (1 KB), rows
-// 1152 B apart so that the four k-rows a fragment read touches fall into different bank halves}.  Wave w: columns
-// 32 w .. 32 w + 31, accumulators [MI][2].  The last k-rows (K % 16) go through registers, zero padded.
-constexpr int TNN_BROW = 1024 + 128;               // bytes between the k-rows of the B part
-constexpr int TNN_SLOT = TN_A + 16 * TNN_BROW;     // 26,624 B; two slots: three workgroups per CU
-template <int MI>
-__global__ __launch_bounds__(256) void k_gemm_nn_thin(long long m, long long n, long long K, double alpha,
-                                                      const double* __restrict__ A, long long lda, const double* __restrict__ B,
-                                                      long long ldb, double beta, double* __restrict__ C, long long ldc) {
-  __shared__ __align__(16) char lds[2 * TNN_SLOT];
-  const unsigned lds0 = unsigned(size_t((__attribute__((address_space(3))) char*)lds));
-  const long long c_own = blockIdx.x * 128LL;                  // first column this workgroup stores
-  const long long c0 = std::min<long long>(c_own, n - 128);    // first column of its tile
-  // (grid.y > 1: A has more than 64 rows and a short K -- the lift  coefficients x basis : row tile blockIdx.y)
-  const long long r0 = blockIdx.y * 64LL;
-  A += r0 * lda;
-  C += r0 * ldc;
-  m = std::min<long long>(64, m - r0);
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int fr = lane & 15, kq = lane >> 4;
-  d4_t acc[MI][2];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
-  const int nfull = int(K / BK), rem = int(K % BK);
-  unsigned fa[4], fb[4];
-#pragma unroll
-  for (int kki = 0; kki < 4; ++kki) {
-    fa[kki] = unsigned(fr * 128) + unsigned((((2 * kki) ^ (kq >> 1) ^ (fr >> 1)) << 4) + (kq & 1) * 8);
-    fb[kki] = unsigned(TN_A + (4 * kki + kq) * TNN_BROW + (w * 32 + fr) * 8);
-  }
-#define TNN_FRAGS(SLOT_, KKI_, AF_, BF_)                                                                   \
-  do {                                                                                                     \
-    const char* pa_ = lds + (SLOT_) * TNN_SLOT + fa[KKI_];                                                 \
-    const char* pb_ = lds + (SLOT_) * TNN_SLOT + fb[KKI_];                                                 \
-    _Pragma("unroll") for (int i_ = 0; i_ < MI; ++i_) AF_[i_] = *reinterpret_cast<const double*>(pa_ + i_ * 2048); \
-    _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_) BF_[j_] = *reinterpret_cast<const double*>(pb_ + j_ * 128);   \
-  } while (0)
-  unsigned voA[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int rl = 16 * w + 8 * q + (lane >> 3);
-    const long long ra = std::min<long long>(rl, m - 1);
-    voA[q] = unsigned(ra * lda * 8) + unsigned(((lane & 7) ^ ((rl >> 1) & 7)) * 16);
-  }
-  const unsigned voB = unsigned(lane) * 16u;  // lane -> columns 2 lane, 2 lane + 1 of the tile
-  const char* sA = reinterpret_cast<const char*>(A);
-  const char* sB = reinterpret_cast<const char*>(B + c0);
-  const size_t brow = size_t(ldb) * 8;
-#define TNN_ISSUE(SLOT_)                                                                                     \
-  do {                                                                                                       \
-    const unsigned sl_ = lds0 + unsigned(SLOT_) * TNN_SLOT;                                                  \
-    _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) T_DMA(sl_ + unsigned(16 * w + 8 * q_) * 128u, sA, voA[q_]);  \
-    _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                                                         \
-        T_DMA(sl_ + TN_A + unsigned(4 * w + q_) * unsigned(TNN_BROW), sB + size_t(4 * w + q_) * brow, voB);  \
-    sA += BK * 8;                                                                                            \
-    sB += BK * brow;                                                                                         \
-  } while (0)
-  if (nfull > 0) {
-    TNN_ISSUE(0);
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    double af[2][MI], bf[2][2];
-    TNN_FRAGS(0, 0, af[0], bf[0]);
-    for (int ch = 0; ch < nfull; ++ch) {
-      const int slot = ch & 1;
-      if (ch + 1 < nfull) TNN_ISSUE(slot ^ 1);
-#pragma unroll
-      for (int kki = 0; kki < 4; ++kki) {
-        const int pb = kki & 1;
-        if (kki < 3) TNN_FRAGS(slot, kki + 1, af[pb ^ 1], bf[pb ^ 1]);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[pb][i], bf[pb][j], acc[i][j], 0, 0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-      if (ch + 1 < nfull) TNN_FRAGS(slot ^ 1, 0, af[0], bf[0]);
-    }
-  }
-#undef TNN_ISSUE
-#undef TNN_FRAGS
-  if (rem > 0) {
-    // [A 64 x LDK doubles | B 16 x 144 doubles]: the last k-rows, zero padded to one chunk
-    double* st = reinterpret_cast<double*>(lds);
-    double* stb = st + 64 * LDK;
-    const long long k0 = (long long)nfull * BK;
-    {
-      const int sk = threadIdx.x & 15, sr0 = threadIdx.x >> 4;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const long long ra = sr0 + 16 * x;
-        st[ra * LDK + sk] = (ra < m && sk < rem) ? A[ra * lda + k0 + sk] : 0.0;
-      }
-      const int cc = threadIdx.x & 127, kr0 = threadIdx.x >> 7;
-#pragma unroll
-      for (int x = 0; x < 8; ++x) {
-        const int kr = kr0 + 2 * x;
-        stb[kr * 144 + cc] = kr < rem ? B[(k0 + kr) * ldb + c0 + cc] : 0.0;
-      }
-    }
-    __syncthreads();
-    const double* pa = st + fr * LDK + kq;
-    const double* pb = stb + kq * 144 + w * 32 + fr;
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      double af[MI], bf[2];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[i] = pa[i * 16 * LDK + kk];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bf[j] = pb[kk * 144 + j * 16];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const long long r = i * 16 + (lane >> 4) + 4 * g;
-      if (r >= m) continue;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const long long c = c0 + w * 32 + j * 16 + (lane & 15);
-        if (c < c_own) continue;
-        double* p = C + r * ldc + c;
-        *p = beta == 0.0 ? alpha * acc[i][j][g] : alpha * acc[i][j][g] + beta * *p;
-      }
-    }
-}
-#undef T_DMA
 
 // ============================================================================================
 // NN GEMM: C[m,n] = alpha * sum_k A[m,k] B[k,n] + beta C   (k small: the lift  c . basis)
@@ -847,14 +786,9 @@ static bool gemm_nn_thin(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t l
 static long long gemm_nn_splits(int64_t m, int64_t n, int64_t k, long long* kper_out) {
   // a handful of output tiles under a long K (the sketches of a FACTORED block: 24 x 272 x 1024): split-K, 64 rows of B each
   const long long tiles = ((n + 63) / 64) * ((m + 63) / 64);
-  long long splits = 1, kper = k;
-  if (tiles <= 32 && k >= 256) {
-    splits = std::min<long long>((256 + tiles - 1) / tiles, k / 64);
-    kper = ((k + splits - 1) / splits + BK - 1) / BK * BK;
-    splits = (k + kper - 1) / kper;
-  }
-  *kper_out = kper;
-  return splits;
+  *kper_out = k;
+  if (tiles <= 32 && k >= 256) return splitk_plan(k, std::min<long long>((256 + tiles - 1) / tiles, k / 64), kper_out);
+  return 1;
 }
 
 size_t rom_gemm_nn_partial_doubles(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb) {
@@ -875,12 +809,9 @@ int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alp
     else rom_prof_name(nm, sizeof nm, "gemm_nn", "_thin_%lldx%lldx%lld", (long long)m, (long long)n, (long long)k);
     ROM_PROF(ctx, nm, 2.0 * m * n * k, 8.0 * (double(m) * k + double(n) * k + double(m) * n));
     const dim3 grid{unsigned((n + 127) / 128), unsigned((m + 63) / 64)};
-    switch (m > 64 ? 4 : (m + 15) / 16) {
-      case 1: k_gemm_nn_thin<1><<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc); break;
-      case 2: k_gemm_nn_thin<2><<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc); break;
-      case 3: k_gemm_nn_thin<3><<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc); break;
-      default: k_gemm_nn_thin<4><<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc); break;
-    }
+    dispatch_mi(m, [&](auto mi) {
+      k_gemm_nn_thin<decltype(mi)::value><<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
+    });
     ROM_HIP(hipGetLastError());
     return ROM_OK;
   }
@@ -901,11 +832,8 @@ int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alp
     k_gemm_nn<<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, kper, part);
   }
   ROM_HIP(hipGetLastError());
-  if (splits > 1) {
-    ROM_PROF(ctx, "splitk_reduce", double(splits) * m * n, 8.0 * double(splits + 1) * m * n);
-    k_splitk_reduce<<<unsigned((m * n + 255) / 256), 256, 0, ctx->stream>>>(m, n, int(splits), alpha, part, beta, C, ldc, 0);
-    ROM_HIP(hipGetLastError());
-  }
+  // (the entry-per-thread reducer whatever the shape: the sums of this route keep their order)
+  if (splits > 1) ROM_TRY(launch_splitk_reduce(ctx, m, n, int(splits), alpha, part, beta, C, ldc, 0, true));
   return ROM_OK;
 }
 

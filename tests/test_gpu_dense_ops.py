@@ -40,7 +40,8 @@ def _ceil(a, b):
 # route table (rom_ops.hip)
 # =====================================================================================================================
 def _reducer(splits, mn):
-    """k_splitk_reduce_{quad,wave,} choice: rom_ops.hip:210-217 (thin) and :275-280 (general) -- the same conditions."""
+    """k_splitk_reduce_{quad,wave,} choice of launch_splitk_reduce (the thin and the general NT routes; the general NN
+    route asks for the plain reducer whatever the shape: route_gemm_nn)."""
     if splits <= 1:
         return "none"
     if splits >= 8 and 4096 <= mn <= (1 << 20):
@@ -51,34 +52,34 @@ def _reducer(splits, mn):
 
 
 def _nt_thin(m, n, k, transposed):
-    """launch_gemm_nt_thin (rom_ops.hip:183): (m, n) are the THIN operand's rows and the other's."""
+    """launch_gemm_nt_thin: (m, n) are the THIN operand's rows and the other's; last: the columns of K in the last split."""
     tiles = _ceil(n, 128)
-    splits = max(1, min(_ceil(768, tiles), k // 512))                      # :188
-    kper = _ceil(_ceil(k, splits), BK) * BK                                 # :189
-    splits = _ceil(k, kper)                                                 # :190
-    return dict(route="nt_thin_T" if transposed else "nt_thin", mi=min(4, _ceil(m, 16)), splits=splits,  # :200
-                reducer=_reducer(splits, m * n), kmin=None)
+    splits = max(1, min(_ceil(768, tiles), k // 512))                      # the splits it asks splitk_plan for
+    kper = _ceil(_ceil(k, splits), BK) * BK                                 # splitk_plan
+    splits = _ceil(k, kper)
+    return dict(route="nt_thin_T" if transposed else "nt_thin", mi=min(4, _ceil(m, 16)), splits=splits,  # dispatch_mi
+                reducer=_reducer(splits, m * n), kmin=None, last=k - (splits - 1) * kper)
 
 
 def route_gemm_nt(m, n, k, lda, ldb, a_off, b_off, lower_only=0, no_thin=False):
-    """rom_launch_gemm_nt_ex (rom_ops.hip:231); a_off / b_off: element offsets into 256-byte aligned buffers."""
-    if m <= 0 or n <= 0:                                                    # :234
+    """rom_launch_gemm_nt_ex; a_off / b_off: element offsets into 256-byte aligned buffers."""
+    if m <= 0 or n <= 0:
         return dict(route="noop", splits=0, reducer="none", mi=None, kmin=None)
     if not lower_only and m <= 64 and n >= 256 and k >= 2048 and lda * 8 * 64 < 2 ** 32 and ldb * 8 * 128 < 2 ** 32 \
-            and not no_thin:                                                # :235
+            and not no_thin:                                                # thin A
         return _nt_thin(m, n, k, False)
     if not lower_only and n <= 64 and m >= 256 and k >= 2048 and ldb * 8 * 64 < 2 ** 32 and lda * 8 * 128 < 2 ** 32 \
-            and not no_thin:                                                # :238
+            and not no_thin:                                                # thin B: the transposed product
         return _nt_thin(n, m, k, True)
     nt = _ceil(m, 64)
-    tiles = nt * (nt + 1) // 2 if lower_only else nt * _ceil(n, 64)        # :242
+    tiles = nt * (nt + 1) // 2 if lower_only else nt * _ceil(n, 64)        # tiles that do work
     splits, kmin = 1, None
-    if k >= 1024 and tiles < 512:                                           # :244
-        kmin = 128 if tiles <= 4 else 512                                   # :246
-        splits = max(1, min(_ceil(768, tiles), _ceil(k, kmin)))            # :247-248
-    kper = _ceil(_ceil(k, splits), BK) * BK or BK                           # :250-251
-    splits = max(1, _ceil(k, kper))                                         # :252-253
-    aligned = lda % 2 == 0 and ldb % 2 == 0 and a_off % 2 == 0 and b_off % 2 == 0 and kper % 4 == 0   # :256
+    if k >= 1024 and tiles < 512:
+        kmin = 128 if tiles <= 4 else 512
+        splits = max(1, min(_ceil(768, tiles), _ceil(k, kmin)))
+    kper = _ceil(_ceil(k, splits), BK) * BK or BK                           # splitk_plan, with its guards for k == 0
+    splits = max(1, _ceil(k, kper))
+    aligned = lda % 2 == 0 and ldb % 2 == 0 and a_off % 2 == 0 and b_off % 2 == 0 and kper % 4 == 0
     if lower_only:
         route = "gram_lower"
     else:
@@ -87,16 +88,16 @@ def route_gemm_nt(m, n, k, lda, ldb, a_off, b_off, lower_only=0, no_thin=False):
 
 
 def route_gram(m, k, lda, a_off):
-    """rom_launch_gram (rom_ops.hip:490): the 128-tile kernel from 512 rows and 4096 columns, else the lower-only engine."""
+    """rom_launch_gram: the 128-tile kernel from 512 rows and 4096 columns, else the lower-only engine."""
     if m <= 0:
         return dict(route="noop", splits=0, reducer="none", mi=None, kmin=None)
-    if m >= 512 and k >= 4096 and lda * 8 * 128 < 2 ** 32:                 # :492
+    if m >= 512 and k >= 4096 and lda * 8 * 128 < 2 ** 32:                 # launch_gram128
         return dict(route="gram128", splits=None, reducer="finish", mi=None, kmin=None)
-    return route_gemm_nt(m, m, k, lda, lda, a_off, a_off, lower_only=1)   # :493
+    return route_gemm_nt(m, m, k, lda, lda, a_off, a_off, lower_only=1)
 
 
 def route_gemm_nn(m, n, k, lda, ldb, no_thin=False):
-    """rom_launch_gemm_nn (rom_ops.hip, gemm_nn_thin / gemm_nn_splits)."""
+    """rom_launch_gemm_nn (gemm_nn_thin / gemm_nn_splits)."""
     if m <= 0 or n <= 0:
         return dict(route="noop", splits=0, reducer="none", mi=None, kmin=None)
     if (k >= 128 if m <= 64 else 16 <= k <= 256) and n >= 1024 and lda * 8 * 64 < 2 ** 32 \
@@ -123,18 +124,23 @@ def route_of(case, no_thin=False):
 
 
 def tags(r):
-    """What a case covers: route / reducer, the 16-row block count of a thin operand, the kmin branch of the split."""
+    """What a case covers: route / reducer, the 16-row block count of a thin operand, the kmin branch of the split, a last
+    split of a thin NT product shorter than one K chunk (no full chunk: the kernel goes from its zero-padded tail straight
+    to the store)."""
     t = {f"{r['route']}/{r['reducer']}"}
     if r["mi"] is not None and r["route"] in ("nt_thin", "nt_thin_T", "nn_thin"):
         t.add(f"{r['route']}/mi{r['mi']}")
     if r["kmin"] is not None:
         t.add(f"{r['route']}/kmin{r['kmin']}")
+    if r.get("last") is not None and r["last"] < BK:
+        t.add(f"{r['route']}/last_split_below_BK")
     return t
 
 
 REQUIRED = (
     {f"nt_thin/{x}" for x in ("plain", "wave", "quad")} | {f"nt_thin/mi{i}" for i in (1, 2, 3, 4)}
     | {f"nt_thin_T/{x}" for x in ("plain", "wave", "quad")}
+    | {"nt_thin/last_split_below_BK", "nt_thin_T/last_split_below_BK"}
     | {f"nt_general_{a}/{x}" for a in ("aligned", "unaligned") for x in ("none", "plain", "wave", "quad")}
     | {f"nt_general_{a}/kmin{q}" for a in ("aligned", "unaligned") for q in (128, 512)}
     | {f"gram_lower/{x}" for x in ("none", "plain", "wave", "quad")} | {"gram_lower/kmin128", "gram_lower/kmin512"}
@@ -147,6 +153,8 @@ ROUTE_CASES = [
     # thin A (m <= 64, n >= 256, k >= 2048): MI = 1..4 and every reducer
     ("nt", 16, 256, 8192, "un"), ("nt", 1, 257, 8192, "un"), ("nt", 33, 513, 2049, "un"), ("nt", 24, 1024, 4100, "al"),
     ("nt", 64, 300, 2048, "un"), ("nt", 49, 1000, 5007, "al"),
+    # 40 splits of 528 columns, the last of ONE column (odd leading dimensions), plain and transposed
+    ("nt", 17, 300, 20593, "un"), ("nt", 300, 17, 20593, "al"),
     # thin B: the transposed product (C[c * ldc + r])
     ("nt", 256, 16, 8192, "un"), ("nt", 300, 1, 8192, "al"), ("nt", 1000, 50, 2049, "un"),
     # the general 64 x 64 engine: no split (k < 1024), kmin = 128 (<= 4 tiles), kmin = 512; every reducer
@@ -293,7 +301,8 @@ def test_exact_products_on_every_route(ctx, case, beta):
 # =====================================================================================================================
 # rounding cases: the rigorous bound against a long-double product; same bits twice and over a poisoned scratch area
 # =====================================================================================================================
-ROUND_CASES = [("nt", 16, 256, 8192, "un"), ("nt", 1, 257, 8192, "un"), ("nt", 33, 513, 2049, "un"), ("nt", 256, 16, 8192, "un"),
+ROUND_CASES = [("nt", 16, 256, 8192, "un"), ("nt", 1, 257, 8192, "un"), ("nt", 33, 513, 2049, "un"), ("nt", 17, 300, 20593, "un"),
+               ("nt", 256, 16, 8192, "un"),
                ("nt", 300, 1, 8192, "al"), ("nt", 65, 127, 1000, "un"), ("nt", 129, 65, 1100, "al"), ("nt", 63, 64, 2047, "al"),
                ("nt", 64, 64, 2049, "un"), ("nt", 129, 129, 4500, "al"), ("gram", 63, 63, 2049, "al"),
                ("gram", 127, 127, 4096, "un"), ("gram", 200, 200, 1100, "un"), ("gram", 70, 70, 1000, "al"),
