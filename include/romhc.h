@@ -441,6 +441,39 @@ int rom_poly_query(rom_poly* h, int64_t* out8);
 int rom_poly_download(rom_poly* h, int what, double* host, size_t count);
 int rom_poly_destroy(rom_poly* h);
 
+/* ---- regression trees and bagged forests on columns of a tall block (src/experiments/NonLinearROM.py:54-70,136-137) ----------
+ * What the reference's DecisionTreeRegressor() and RandomForestRegressor(n_estimators=10) compute: T multi-output CART trees
+ * from m input columns (1 <= m <= 16) to q target columns (1 <= q <= 128) over M rows, 1 <= T <= 256, built LEVEL BY LEVEL
+ * over all trees at once.  counts_host (T x M int32 >= 0, or NULL: all 1) are the bootstrap multiplicities of the rows per
+ * tree; a row of count 0 does not exist for that tree; a tree without rows is an error.
+ * Criterion: weighted MSE summed over the targets -- the candidate that maximises sum_k S_Lk^2 / n_L + S_Rk^2 / n_R, the sums
+ * formed on targets shifted by the node's mean.  Candidates lie between consecutive distinct values lo < hi of one input among
+ * the node's rows, both sides keeping a weighted count >= min_samples_leaf; threshold lo + (hi - lo) / 2 (lo if that is >=
+ * hi); a row goes left iff x <= threshold.  Ties: largest gain, then lowest input, then lowest position.  A node is a leaf
+ * iff n < min_samples_split, depth == max_depth (0: no limit), no valid candidate, or every target is constant over its rows.
+ * Leaf value: weighted mean (bit for bit the row when the targets are constant).  Forest prediction: mean over the trees,
+ * summed in tree order.  No floating-point atomics: the same bits on a repeated call.  NaN / Inf among the training inputs
+ * or targets are an error.  One host synchronisation per level. */
+typedef struct rom_tree rom_tree;
+/* (src/experiments/NonLinearROM.py:54-70,136-137: model.fit) X, Y as in rom_poly_fit; neither is modified.  info_host (8
+ * doubles or NULL): nodes, leaves, deepest level, levels run, kernel launches, host synchronisations, bytes of workspace, 0. */
+int rom_tree_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q,
+                 int64_t M, int T, const int32_t* counts_host, int max_depth, int min_samples_split, int min_samples_leaf,
+                 rom_tree** out, double* info_host);
+/* (src/experiments/NonLinearROM.py:54-70,136-137: model.predict and the error) as rom_poly_predict: OUT (may be NULL) <-
+ * prediction, or Yref - prediction; sumsq_host (q, may be NULL): column sums of squares of that, from fixed-order partials.
+ * OUT must not overlap X.  One host synchronisation. */
+int rom_tree_predict(rom_tree* h, rom_buf* X, size_t x_off, int64_t ldx, int64_t M, rom_buf* OUT, size_t o_off, int64_t ldo,
+                     rom_buf* Yref, size_t r_off, int64_t ldr, double* sumsq_host);
+/* (src/experiments/NonLinearROM.py:54-70,136-137) out8: m, q, T, M_train, nodes in all trees, deepest level, kernel launches,
+ * host synchronisations so far */
+int rom_tree_query(rom_tree* h, int64_t* out8);
+/* (src/experiments/NonLinearROM.py:54-70,136-137) host copies, the trees one after the other, each in breadth-first order:
+ * what = 0 first node of each tree (T + 1), 1 input of the split (-1 at a leaf), 2 threshold, 3 left child (the right child is
+ * left + 1; -1 at a leaf), 4 weighted count (one value per node each), 5 values (nodes x q).  count must be the size. */
+int rom_tree_download(rom_tree* h, int what, double* host, size_t count);
+int rom_tree_destroy(rom_tree* h);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

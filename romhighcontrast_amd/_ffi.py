@@ -126,6 +126,13 @@ PROTOTYPES = {
     "rom_poly_query": (C.c_int, [_vp, _vp]),
     "rom_poly_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
     "rom_poly_destroy": (C.c_int, [_vp]),
+    "rom_tree_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
+                               _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
+    "rom_tree_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
+                                   _vp]),
+    "rom_tree_query": (C.c_int, [_vp, _vp]),
+    "rom_tree_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
+    "rom_tree_destroy": (C.c_int, [_vp]),
     "rom_comm_unique_id": (C.c_int, [C.c_char_p, C.c_size_t]),
     "rom_comm_init": (C.c_int, [_vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int]),
     "rom_comm_destroy": (C.c_int, [_vp]),
@@ -322,6 +329,13 @@ class Context:
         x_off, row stride ldx) to the q columns of Y over M rows.  Neither block is modified.  Returns the PolyMap."""
         return PolyMap(self, X, x_off, ldx, m, Y, y_off, ldy, q, M, degree, rcond)
 
+    def tree_fit(self, X: "Buffer", x_off, ldx, m, Y: "Buffer", y_off, ldy, q, M, T=1, counts=None, max_depth=None,
+                 min_samples_split=2, min_samples_leaf=1) -> "TreeMapHandle":
+        """rom_tree_fit: T regression trees (a bagged forest) from the m columns of X (from element x_off, row stride ldx) to the
+        q columns of Y over M rows, built level by level on the device.  ``counts``: (T, M) integer multiplicities of the rows
+        per tree (the bootstrap), None: every row once.  Neither block is modified.  Returns the TreeMapHandle."""
+        return TreeMapHandle(self, X, x_off, ldx, m, Y, y_off, ldy, q, M, T, counts, max_depth, min_samples_split, min_samples_leaf)
+
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):
         check(self.lib.rom_symmetric_orthonormalize(self.h, V.h, v_row0, n, dim))
 
@@ -493,6 +507,70 @@ class PolyMap:
     def free(self):
         if getattr(self, "h", None):
             self.ctx.lib.rom_poly_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class TreeMapHandle:
+    """Handle of a fitted tree / forest (rom_tree_*): owns the device node arrays, destroyed on collection."""
+
+    _PARTS = ("first", "feature", "threshold", "left", "count", "value")
+
+    def __init__(self, ctx: Context, X: Buffer, x_off, ldx, m, Y: Buffer, y_off, ldy, q, M, T=1, counts=None, max_depth=None,
+                 min_samples_split=2, min_samples_leaf=1):
+        self.ctx = ctx
+        self.h = None
+        cnt = None
+        if counts is not None:
+            cnt = np.ascontiguousarray(counts, dtype=np.int32)
+            assert cnt.shape == (int(T), int(M)), f"tree_fit: counts of shape {cnt.shape}, expected ({T}, {M})"
+        h, info = _vp(), np.zeros(8)
+        check(ctx.lib.rom_tree_fit(ctx.h, X.h if X is not None else None, int(x_off), int(ldx), int(m),
+                                   Y.h if Y is not None else None, int(y_off), int(ldy), int(q), int(M), int(T),
+                                   cnt.ctypes.data if cnt is not None else None, int(max_depth or 0), int(min_samples_split),
+                                   int(min_samples_leaf), C.byref(h), info.ctypes.data))
+        self.h = h
+        self.m, self.q, self.T = int(m), int(q), int(T)
+        self.info = dict(nodes=int(info[0]), leaves=int(info[1]), deepest_level=int(info[2]), levels=int(info[3]),
+                         launches=int(info[4]), host_syncs=int(info[5]), workspace_bytes=int(info[6]))
+
+    def query(self) -> dict:
+        out = np.zeros(8, dtype=np.int64)
+        check(self.ctx.lib.rom_tree_query(self.h, out.ctypes.data))
+        keys = ("m", "q", "T", "M_train", "nodes", "deepest_level", "launches", "host_syncs")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def nodes(self) -> dict:
+        """Host copies of the node arrays, the trees one after the other (tree t: nodes first[t] .. first[t + 1] - 1, breadth
+        first): "first" (T + 1,), "feature" (-1 at a leaf), "threshold", "left" (the right child is left + 1; -1 at a leaf),
+        "count" (weighted), "value" (nodes, q)."""
+        n = self.info["nodes"]
+        out = {}
+        for what, part in enumerate(self._PARTS):
+            a = np.zeros(self.T + 1 if what == 0 else n * self.q if what == 5 else n)
+            check(self.ctx.lib.rom_tree_download(self.h, what, a.ctypes.data, a.size))
+            out[part] = a.reshape(n, self.q) if what == 5 else a if what in (2, 4) else a.astype(np.int64)
+        return out
+
+    def predict(self, X: Buffer, x_off, ldx, M, OUT: "Buffer | None" = None, o_off=0, ldo=None, Yref: "Buffer | None" = None, r_off=0,
+                ldr=None, sumsq=False):
+        """rom_tree_predict: as PolyMap.predict -- OUT <- the prediction for the M rows of X, or Yref - prediction; with
+        ``sumsq`` returns the q column sums of squares of that (OUT may then be None)."""
+        ss = np.zeros(self.q) if sumsq else None
+        check(self.ctx.lib.rom_tree_predict(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M),
+                                            OUT.h if OUT is not None else None, int(o_off), int(self.q if ldo is None else ldo),
+                                            Yref.h if Yref is not None else None, int(r_off), int(self.q if ldr is None else ldr),
+                                            ss.ctypes.data if sumsq else None))
+        return ss
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.rom_tree_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -3,8 +3,9 @@ PCA coordinates of a solution from its leading ones"): the parameter sweep, the 
 the index bookkeeping of the regression experiments.  The sweep runs on the device (SolutionsManagerFEM) and the PCA is
 ``pca_tall`` (rom_pca_tall: 25,000 x 81 is M >> dim, the shape rom_pod was not designed for).  The polynomial regressions
 of the third stage have a device path as well (``PolynomialMap``, ``learn_eigenvalues_device``, ``nonlinear_reconstruction``:
-rom_poly_fit / rom_poly_predict); trees, forests and MLPs stay scikit-learn's.  The plots and the PerplexityLab LabPipeline
-driver of the reference are out of scope.
+rom_poly_fit / rom_poly_predict), and so have the regression tree and the random forest of the model list (``TreeMap``,
+``ForestMap``: rom_tree_fit / rom_tree_predict, CART trees built level by level over all trees of a forest at once); MLPs
+stay scikit-learn's.  The plots and the PerplexityLab LabPipeline driver of the reference are out of scope.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from .lib.ReducedBasis import pca_tall
 from .lib.SolutionsManagers import DeviceArray, SolutionsManagerFEM
 
 __all__ = ["ZERO", "Bounds", "MWhere", "draw_parameters", "vn_family_sampler", "do_pca", "get_known_unknown_indexes",
-           "learn_eigenvalues", "PolynomialMap", "learn_eigenvalues_device", "nonlinear_reconstruction"]
+           "learn_eigenvalues", "PolynomialMap", "TreeMap", "ForestMap", "learn_eigenvalues_device", "nonlinear_reconstruction"]
 
 ZERO = 1e-15
 Bounds = namedtuple("Bounds", "lower upper")
@@ -155,8 +156,68 @@ class PolynomialMap:
         return res if isinstance(X, DeviceArray) else res.numpy()
 
 
-def learn_eigenvalues_device(degree, rcond=0.0, ctx=None):
-    """(:54-70) ``learn_eigenvalues`` with the device fit: the same experiment function, but ``pca_projections`` is the
+class TreeMap(PolynomialMap):
+    """(:136) ``DecisionTreeRegressor()`` as one device fit (rom_tree_fit): a multi-output CART tree with the weighted-MSE
+    criterion summed over the targets, thresholds halfway between consecutive distinct values of fp64 inputs, ties to the
+    lowest input and position (scikit-learn draws them at random).  The protocol of PolynomialMap: ``fit`` / ``fit_columns`` /
+    ``predict`` on host arrays or DeviceArrays, ``map_`` (the TreeMapHandle), ``info_``, ``steps``."""
+
+    _name = "Tree device"
+
+    def __init__(self, max_depth=None, min_samples_split=2, min_samples_leaf=1, ctx=None):
+        self.max_depth, self.min_samples_split, self.min_samples_leaf = max_depth, int(min_samples_split), int(min_samples_leaf)
+        self._ctx = ctx
+        self.steps = [(self._name, self)]
+        self.map_ = None
+        self.counts_ = None
+
+    def _counts(self, M):
+        """(T, M) multiplicities of the rows per tree, or None: every row once."""
+        return None
+
+    n_trees = 1
+
+    def fit_columns(self, Xd, xcols, Yd, ycols, row0, rows):
+        from . import _ffi
+        self.counts_ = self._counts(int(rows))
+        try:
+            self.map_ = self._context().tree_fit(Xd.buf, row0 * Xd.dim + xcols[0], Xd.dim, xcols[1] - xcols[0], Yd.buf,
+                                                 row0 * Yd.dim + ycols[0], Yd.dim, ycols[1] - ycols[0], rows, self.n_trees,
+                                                 self.counts_, self.max_depth, self.min_samples_split, self.min_samples_leaf)
+        except _ffi.RomLibraryError as e:
+            if "NaN / Inf" in str(e):   # (scikit-learn's estimators raise ValueError on such input)
+                raise ValueError(str(e)) from None
+            raise
+        self.info_ = self.map_.info
+        return self
+
+
+class ForestMap(TreeMap):
+    """(:137) ``RandomForestRegressor(n_estimators)`` as one device fit: ``n_estimators`` trees on bootstrap samples of the
+    rows, all built together level by level; the prediction is the mean over the trees.  Every input is a split candidate at
+    every node, as in scikit-learn's regressor (max_features = 1.0).  The draw is
+    ``np.random.default_rng(random_state).integers(0, M, (T, M))``, kept per tree as the counts ``counts_`` (T, M)."""
+
+    _name = "RF device"
+
+    def __init__(self, n_estimators=10, bootstrap=True, random_state=0, max_depth=None, min_samples_split=2, min_samples_leaf=1,
+                 ctx=None):
+        super().__init__(max_depth, min_samples_split, min_samples_leaf, ctx)
+        self.n_estimators, self.bootstrap, self.random_state = int(n_estimators), bool(bootstrap), random_state
+        self.n_trees = self.n_estimators
+
+    def _counts(self, M):
+        return self.bootstrap_counts(self.n_estimators, M, self.random_state) if self.bootstrap else None
+
+    @staticmethod
+    def bootstrap_counts(T, M, random_state=0):
+        draw = np.random.default_rng(random_state).integers(0, M, (T, M))
+        return np.stack([np.bincount(row, minlength=M) for row in draw]).astype(np.int32)
+
+
+def learn_eigenvalues_device(degree=None, rcond=0.0, ctx=None, model=None):
+    """(:54-70) ``learn_eigenvalues`` with the device fit (``model``: a TreeMap / ForestMap / PolynomialMap instance used
+    instead of the polynomial of ``degree``; it is fitted again for every range of unknowns): the same experiment function, but ``pca_projections`` is the
     DeviceArray of scores (``pca_tall(..., download=False).scores``) and nothing of size (rows, modes) comes to the host
     except the (n_test, unknown) errors.  Fit on rows [n_test, n_test + n_train), predict rows [0, n_test).  A
     non-contiguous unknown list (``learn_higher_modes_only=False``) is fitted as its contiguous ranges.  Returns
@@ -170,22 +231,25 @@ def learn_eigenvalues_device(degree, rcond=0.0, ctx=None):
         known, unknown = get_known_unknown_indexes(mwhere, np.empty((0, S.dim)), learn_higher_modes_only, only_j)
         errors, rmse = [], []
         for lo, hi in _contiguous_ranges(unknown):
-            model = PolynomialMap(degree, rcond, c).fit_columns(S, (int(known[0]), int(known[-1]) + 1), S, (lo, hi), n_test, n_train)
+            fitted = PolynomialMap(degree, rcond, c) if model is None else model
+            if fitted._ctx is None:
+                fitted._ctx = c
+            fitted.fit_columns(S, (int(known[0]), int(known[-1]) + 1), S, (lo, hi), n_test, n_train)
             E = c.alloc(max(n_test * (hi - lo), 1))
-            ss = model.map_.predict(S.buf, int(known[0]), S.dim, n_test, OUT=E, Yref=S.buf, r_off=lo, ldr=S.dim, sumsq=True)
+            ss = fitted.map_.predict(S.buf, int(known[0]), S.dim, n_test, OUT=E, Yref=S.buf, r_off=lo, ldr=S.dim, sumsq=True)
             errors.append(E.download(n_test * (hi - lo), shape=(n_test, hi - lo)))
             rmse.append(np.sqrt(ss / n_test))
         if not errors:
             return {"error": np.zeros((n_test, 0)), "rmse": np.zeros(0)}
         return {"error": np.hstack(errors), "rmse": np.concatenate(rmse)}
 
-    experiment.__name__ = " ".join(step[0] for step in PolynomialMap(degree).steps)
+    experiment.__name__ = " ".join(step[0] for step in (PolynomialMap(degree) if model is None else model).steps)
     return experiment
 
 
 def nonlinear_reconstruction(pca, poly, known_scores, known_start=0, unknown_start=None, download=True):
     """The reduced model the fitted map defines: u = mean + known scores . their components + predicted scores . theirs.
-    ``pca``: a TallPCA; ``poly``: a fitted PolynomialMap (or PolyMap) from m known to q unknown score columns;
+    ``pca``: a TallPCA; ``poly``: a fitted PolynomialMap, TreeMap or ForestMap (or its handle) from m known to q unknown score columns;
     ``known_scores``: (K, m) host array or DeviceArray; the known columns are the components [known_start, known_start + m)
     and the predicted ones [unknown_start, unknown_start + q) (default: right after the known ones).  Two rom_gemm_nn
     products on the device."""
