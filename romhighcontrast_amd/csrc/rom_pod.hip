@@ -16,9 +16,6 @@
 #include "rom_small_dense.h"
 
 // =====================================================================================================================
-// POD (the PCA fit of ReducedBasisPCA.build, src/lib/ReducedBasis.py:189-200)
-// =====================================================================================================================
-// =====================================================================================================================
 // The Gram route (slowly decaying spectra): Gram matrix on MFMA, leading eigenpairs by a pivoted-Cholesky low-rank factor or
 // by subspace iteration IN M SPACE -- an iteration costs 2 M^2 b flops there instead of two passes over the block
 // =====================================================================================================================
@@ -38,8 +35,6 @@ __global__ void kb_inv(const double* __restrict__ x, double* __restrict__ out, i
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = x[i] > 0.0 ? 1.0 / x[i] : 0.0;
 }
-
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Low-rank factor of a symmetric PSD matrix by diagonally pivoted Cholesky, ONE workgroup of 1024 threads:
@@ -167,7 +162,6 @@ __global__ void kp_scale_eigvec_rows(double* __restrict__ W, long long M, const 
   for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < M; j += (long long)gridDim.x * blockDim.x) row[j] *= a;
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Fused small kernels of the sketch passes.  A pass is four thin products over the snapshot block plus ~70 small dense
 // operations on b <= 32 rows; launched one by one (Gram product, split-K reduction, mirror, factorisation, apply, copy
@@ -255,7 +249,6 @@ __global__ __launch_bounds__(256) void kp_combine_rows_mma(int bo, int b1, int b
       }
     }
 }
-
 
 // Rayleigh-Ritz rounds on a tall factor given TRANSPOSED, Tt (b x M, ld M, b <= 32), one workgroup of 256 threads:
 // per round  H = Tt Tt^T (MFMA, one 16 x 16 output block per wave),  H = S^T diag(sig2) S (jacobi32_run),  Tt <- S Tt,
@@ -453,7 +446,7 @@ constexpr double NOISE_FLOOR = 1e-13;    // modes below this fraction of sigma_1
 constexpr int PASS_MODES = 24;           // modes asked of one sketch pass (+ 8 rows of oversampling = 32: the one-workgroup small kernels)
 
 struct PodInfo {
-  int gram_passes = 0, sketch_passes = 0, completed = 0, resolved = 0, eig_iterations = 0, lowrank = 0, full_eig = 0, unconverged = 0;
+  int gram_passes = 0, sketch_passes = 0, completed = 0, eig_iterations = 0, unconverged = 0;
   double executed = 0.0;
 };
 
@@ -462,13 +455,28 @@ constexpr int LOWRANK_CAP = 96;          // most steps of the pivoted Cholesky t
 constexpr double LOWRANK_TOL = 1e-14;    // its stopping pivot, relative to the first one
 constexpr double LOWRANK_RESIDUAL = 2e-14;  // accepted ||G - L L^T|| (bounded by the trace of the remaining diagonal) / lambda_1
 
+// What every eigen-route hands to its caller: the leading min(nev, r) of the r eigenpairs found -- rows Wr (ld M), values
+// lam (device) and lam_host -- as W (nev x M), theta_dev and theta_host (nev values, not negative), zero behind them.
+// Enqueued only.
+int publish_eigenpairs(rom_ctx* ctx, int M, const double* Wr, const double* lam, const double* lam_host, int r, int nev, double* W,
+                       double* theta_dev, std::vector<double>& theta_host) {
+  const int ncopy = std::min(nev, r);
+  ROM_HIP(hipMemcpyAsync(W, Wr, size_t(ncopy) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  if (ncopy < nev) ROM_HIP(hipMemsetAsync(W + size_t(ncopy) * M, 0, size_t(nev - ncopy) * M * sizeof(double), ctx->stream));
+  ROM_HIP(hipMemsetAsync(theta_dev, 0, size_t(nev) * sizeof(double), ctx->stream));
+  ROM_HIP(hipMemcpyAsync(theta_dev, lam, size_t(ncopy) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  theta_host.assign(nev, 0.0);
+  for (int i = 0; i < ncopy; ++i) theta_host[i] = std::max(lam_host[i], 0.0);
+  return ROM_OK;
+}
+
 // The leading eigenpairs of a numerically low-rank PSD matrix without iteration: G ~ Lt^T Lt by pivoted Cholesky (rank r,
 // one launch), the r x r problem Lt Lt^T = Q diag(theta) Q^T, eigenvectors w_i = Lt^T q_i / sqrt(theta_i).  The error
 // against the eigenpairs of G itself is that of a perturbation of norm <= trace(remaining diagonal), which the kernel
 // reports; the caller falls back to the subspace iteration when that bound is above LOWRANK_RESIDUAL x theta_0 or the
 // factor did not end within LOWRANK_CAP steps (a slowly decaying spectrum).  done = 1 on success.
 int lowrank_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W, std::vector<double>& theta_host, double* theta_dev,
-                       PodInfo& info, int& done) {
+                       int& done) {
   done = 0;
   const int rcap = std::min(M, LOWRANK_CAP);
   if (M <= rcap) return ROM_OK;  // (the full space: one exact Ritz step of the general path)
@@ -480,11 +488,9 @@ int lowrank_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W,
     // eigenproblem reads it from the device): ONE host synchronisation for the whole Gram stage when the block's Gram
     // matrix has numerical rank <= 32 -- a sweep over a handful of parameters -- instead of two round trips.
     constexpr int R32 = 32;
-    ROM_TRY(Lt.get(ctx, size_t(R32) * M));
-    ROM_TRY(H.get(ctx, size_t(R32) * R32));
-    ROM_TRY(St.get(ctx, size_t(R32) * R32));
+    for (Tmp* t : {&Lt, &Wr}) ROM_TRY(t->get(ctx, size_t(R32) * M));
+    for (Tmp* t : {&H, &St}) ROM_TRY(t->get(ctx, size_t(R32) * R32));
     ROM_TRY(lam.get(ctx, R32));
-    ROM_TRY(Wr.get(ctx, size_t(R32) * M));
     ROM_HIP(hipMemsetAsync(Lt.p(), 0, size_t(R32) * M * sizeof(double), ctx->stream));
     {
       ROM_PROF(ctx, "pivchol_lowrank", double(R32) * R32 * M, 8.0 * R32 * M);
@@ -507,17 +513,8 @@ int lowrank_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W,
     const int r = int(o[0]);
     if (r < 1) return ROM_OK;
     if (o[3] != 0.0 && o[4] > 0.0 && o[1] <= LOWRANK_RESIDUAL * o[4]) {
-      const int ncopy = std::min(nev, r);
-      ROM_HIP(hipMemcpyAsync(W, Wr.p(), size_t(ncopy) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      if (ncopy < nev) ROM_HIP(hipMemsetAsync(W + size_t(ncopy) * M, 0, size_t(nev - ncopy) * M * sizeof(double), ctx->stream));
-      ROM_HIP(hipMemsetAsync(theta_dev, 0, size_t(nev) * sizeof(double), ctx->stream));
-      ROM_HIP(hipMemcpyAsync(theta_dev, lam.p(), size_t(ncopy) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      theta_host.assign(nev, 0.0);
-      for (int i = 0; i < ncopy; ++i) theta_host[i] = std::max(o[4 + i], 0.0);
-      info.eig_iterations = 0;
-      info.lowrank = r;
       done = 1;
-      return ROM_OK;
+      return publish_eigenpairs(ctx, M, Wr, lam, o + 4, r, nev, W, theta_dev, theta_host);
     }
     if (o[3] != 0.0) return ROM_OK;   // (ended by tolerance but the residual bound failed: the general path)
   }
@@ -542,19 +539,10 @@ int lowrank_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W,
   ROM_TRY(download(ctx, lam, th.data(), r));
   if (!(th[0] > 0.0) || o[1] > LOWRANK_RESIDUAL * th[0]) return ROM_OK;
   ROM_TRY(rom_launch_gemm_nn(ctx, r, M, r, 1.0, St, r, Lt, M, 0.0, Wr, M));
-  const int ncopy = std::min(nev, r);
-  kp_scale_eigvec_rows<<<dim3(unsigned(std::min((M + 255) / 256, 64)), ncopy), 256, 0, ctx->stream>>>(Wr, M, lam, 0.0);
+  kp_scale_eigvec_rows<<<dim3(unsigned(std::min((M + 255) / 256, 64)), std::min(nev, r)), 256, 0, ctx->stream>>>(Wr, M, lam, 0.0);
   ROM_HIP(hipGetLastError());
-  ROM_HIP(hipMemcpyAsync(W, Wr.p(), size_t(ncopy) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  if (ncopy < nev) ROM_HIP(hipMemsetAsync(W + size_t(ncopy) * M, 0, size_t(nev - ncopy) * M * sizeof(double), ctx->stream));
-  ROM_HIP(hipMemsetAsync(theta_dev, 0, size_t(nev) * sizeof(double), ctx->stream));
-  ROM_HIP(hipMemcpyAsync(theta_dev, lam.p(), size_t(ncopy) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  theta_host.assign(nev, 0.0);
-  for (int i = 0; i < ncopy; ++i) theta_host[i] = std::max(th[i], 0.0);
-  info.eig_iterations = 0;
-  info.lowrank = r;
   done = 1;
-  return ROM_OK;
+  return publish_eigenpairs(ctx, M, Wr, lam, th.data(), r, nev, W, theta_dev, theta_host);
 }
 
 // Leading nev eigenpairs of the symmetric PSD matrix G (M x M) by subspace iteration with Rayleigh-Ritz; the projected
@@ -562,11 +550,9 @@ int lowrank_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W,
 int top_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W, std::vector<double>& theta_host, double* theta_dev,
                    PodInfo& info,
                    int oversample = 12, double tol = 2e-14, int max_iter = 300, double accept = GRAM_ACCEPT) {
-  {
-    int done = 0;
-    ROM_TRY(lowrank_eigenpairs(ctx, G, M, nev, W, theta_host, theta_dev, info, done));
-    if (done) return ROM_OK;
-  }
+  int done = 0;
+  ROM_TRY(lowrank_eigenpairs(ctx, G, M, nev, W, theta_host, theta_dev, done));
+  if (done) return ROM_OK;
   // the whole Gram matrix diagonalised at once (Jacobi: the eigenvalues to the accuracy of the matrix entries whatever the
   // gaps): when the request is most of the spectrum -- an iteration would diagonalise a block of nearly that order EVERY
   // step -- and as the last resort of an iteration that did not converge (below)
@@ -581,23 +567,16 @@ int top_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W, std
     ROM_HIP(hipMemcpyAsync(theta_dev, lamf.p(), size_t(nev) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     ROM_HIP(hipMemcpyAsync(W, Tf.p(), size_t(nev) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     ROM_HIP(hipStreamSynchronize(ctx->stream));   // (Tf / lamf go back to the pool when this scope ends)
-    info.full_eig = 1;
     return ROM_OK;
   };
   if (M <= SE_GRID_MAX && 2 * (nev + oversample) >= M) return full_eig();
   const int b0 = std::min(M, nev + oversample);
   int b = b0;  // rows in play: shrinks once the spectrum shows how many pairs the caller can use (see below)
-  Tmp Y, Z, H, St, lam, Yr, Zr, Res, res, Zs, scr, nrm;
-  ROM_TRY(Y.get(ctx, size_t(b) * M));
-  ROM_TRY(Z.get(ctx, size_t(b) * M));
+  Tmp Y, Z, H, St, lam, Yr, Zr, Res, Zs, scr, nrm;
+  for (Tmp* t : {&Y, &Z, &Yr, &Zr, &Res, &Zs, &scr}) ROM_TRY(t->get(ctx, size_t(b) * M));
   ROM_TRY(H.get(ctx, size_t(b) * b));
   ROM_TRY(St.get(ctx, size_t(b) * b));
   ROM_TRY(lam.get(ctx, 2 * size_t(b)));
-  ROM_TRY(Yr.get(ctx, size_t(b) * M));
-  ROM_TRY(Zr.get(ctx, size_t(b) * M));
-  ROM_TRY(Res.get(ctx, size_t(b) * M));
-  ROM_TRY(Zs.get(ctx, size_t(b) * M));
-  ROM_TRY(scr.get(ctx, size_t(b) * M));
   ROM_TRY(nrm.get(ctx, b));
   double* d_res = lam.p() + b0;
   ROM_TRY(romb_fill_random(ctx, Y, size_t(b) * M, 0x5eed0000ull + unsigned(b) * 131u + unsigned(M), true));
@@ -675,35 +654,46 @@ int top_eigenpairs(rom_ctx* ctx, const double* G, int M, int nev, double* W, std
     if (M <= SE_GRID_MAX) return full_eig();
     info.unconverged = 1;
   }
-  theta_host.assign(th.begin(), th.begin() + nev);
-  for (int i = b; i < nev; ++i) theta_host[i] = 0.0;
-  const int ncopy = std::min(nev, b);
-  ROM_HIP(hipMemsetAsync(theta_dev, 0, size_t(nev) * sizeof(double), ctx->stream));
-  ROM_HIP(hipMemcpyAsync(theta_dev, lam.p(), size_t(ncopy) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  ROM_HIP(hipMemcpyAsync(W, Yr.p(), size_t(ncopy) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  if (ncopy < nev) ROM_HIP(hipMemsetAsync(W + size_t(ncopy) * M, 0, size_t(nev - ncopy) * M * sizeof(double), ctx->stream));
-  return ROM_OK;
+  // (the b Ritz pairs in play; th holds zeros for the pairs dropped from the block)
+  return publish_eigenpairs(ctx, M, Yr, lam, th.data(), b, nev, W, theta_dev, theta_host);
 }
-
 
 // ---- launchers of the fused kernels --------------------------------------------------------------------------------
 constexpr int FUSED_ROWS = 32;   // row blocks up to this size take the fused kernels (one Jacobi / Cholesky wave, LDS resident)
 
-// OUT (bo x ncols) = T1 Y + alpha2 T2 V2 (see kp_combine_rows_mma); bo <= 64
-int combine_rows(rom_ctx* ctx, int bo, int b1, const double* T1, int ldt1, int b2, const double* T2, int ldt2, double alpha2,
-                 const double* Y, int64_t ldy, const double* V2, int64_t ldv, double* OUT, int64_t ldo, int64_t ncols) {
+// the fused route of apply_rows: packed operands (ld = row length; 0 for an operand that is absent), bo <= 64
+int combine_rows(rom_ctx* ctx, int bo, int b1, const double* T1, int b2, const double* T2, double alpha2, const double* Y,
+                 const double* V2, double* OUT, int64_t ncols) {
   if (bo <= 0 || ncols <= 0) return ROM_OK;
   ROM_CHECK(bo <= 64, "combine_rows: %d output rows", bo);
-  const unsigned grid = unsigned((ncols + 255) / 256);
   ROM_PROF(ctx, "combine_rows", 2.0 * bo * ((T1 ? b1 : 0) + b2) * double(ncols), 8.0 * double(ncols) * (bo + (T1 ? b1 : bo) + b2));
-  if (bo <= 16) {
-    kp_combine_rows_mma<1><<<grid, 256, 0, ctx->stream>>>(bo, b1, b2, T1, ldt1, T2, ldt2, alpha2, Y, ldy, V2, ldv, OUT, ldo, ncols);
-  } else if (bo <= 32) {
-    kp_combine_rows_mma<2><<<grid, 256, 0, ctx->stream>>>(bo, b1, b2, T1, ldt1, T2, ldt2, alpha2, Y, ldy, V2, ldv, OUT, ldo, ncols);
-  } else {
-    kp_combine_rows_mma<4><<<grid, 256, 0, ctx->stream>>>(bo, b1, b2, T1, ldt1, T2, ldt2, alpha2, Y, ldy, V2, ldv, OUT, ldo, ncols);
-  }
+  auto* kernel = kp_combine_rows_mma<1>;   // (NRB = ceil(bo / 16) row blocks, 3 rounded up to 4)
+  if (bo > 16) kernel = bo <= 32 ? kp_combine_rows_mma<2> : kp_combine_rows_mma<4>;
+  kernel<<<unsigned((ncols + 255) / 256), 256, 0, ctx->stream>>>(bo, b1, b2, T1, T1 ? b1 : 0, T2, b2, alpha2, Y, ncols, V2,
+                                                                  V2 ? ncols : 0, OUT, ncols, ncols);
   ROM_HIP(hipGetLastError());
+  return ROM_OK;
+}
+
+// The row map of this file: OUT (bo x ncols) = T1 (bo x b1) Y + alpha2 T2 (bo x b2) V2, every matrix packed.  In use: the
+// TRANSFORM OUT = T1 Y (T2 == nullptr, b2 = 0) and the CORRECTION OUT = Y + alpha2 T2 V2 (T1 == nullptr, b1 = bo); OUT may
+// be Y.  `fused` is the CALLER's route, never derived from the sizes here (the sites' predicates differ, and a result's bits
+// depend on the route): true = kp_combine_rows_mma; false = GEMM -- the transform with beta = 0, in place through a scratch
+// block and a copy back; the correction as a copy Y -> OUT (unless in place) and a product with beta = 1.
+int apply_rows(rom_ctx* ctx, bool fused, int bo, int b1, const double* T1, int b2, const double* T2, double alpha2, const double* Y,
+               const double* V2, double* OUT, int64_t ncols) {
+  if (fused) return combine_rows(ctx, bo, b1, T1, b2, T2, alpha2, Y, V2, OUT, ncols);
+  const size_t bytes = size_t(bo) * ncols * sizeof(double);
+  if (!T1) {
+    if (OUT != Y) ROM_HIP(hipMemcpyAsync(OUT, Y, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return rom_launch_gemm_nn(ctx, bo, ncols, b2, alpha2, T2, b2, V2, ncols, 1.0, OUT, ncols);
+  }
+  ROM_CHECK(b2 == 0, "apply_rows: a transform with a correction takes the fused route");
+  if (OUT != Y) return rom_launch_gemm_nn(ctx, bo, ncols, b1, 1.0, T1, b1, Y, ncols, 0.0, OUT, ncols);
+  Tmp scr;
+  ROM_TRY(scr.get(ctx, size_t(bo) * ncols));
+  ROM_TRY(rom_launch_gemm_nn(ctx, bo, ncols, b1, 1.0, T1, b1, Y, ncols, 0.0, scr, ncols));
+  ROM_HIP(hipMemcpyAsync(OUT, scr.p(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
   return ROM_OK;
 }
 
@@ -726,22 +716,20 @@ int whiten_rows(rom_ctx* ctx, double* X, int b, int64_t dim, double rel_tol, int
   for (int r = 0; r < rounds; ++r) {
     ROM_TRY(rom_launch_gemm_nt(ctx, b, b, dim, 1.0, X, dim, X, dim, 0.0, G, b, "gram_small"));
     ROM_TRY(romb_pivchol_whiten(ctx, b, G, b, lam, Tm, b, r == 0 ? rel_tol : 1e-8));
-    ROM_TRY(combine_rows(ctx, b, b, Tm, b, 0, nullptr, 0, 0.0, X, dim, nullptr, 0, X, dim, dim));
+    ROM_TRY(apply_rows(ctx, true, b, b, Tm, 0, nullptr, 0.0, X, nullptr, X, dim));   // (b <= FUSED_ROWS here)
   }
   return ROM_OK;
 }
 
 // nearly orthonormal rows X (b x dim) <- (X X^T)^(-1/2) X in place; T_out (b x b, device): the transform that was applied
-int lowdin_rows(rom_ctx* ctx, double* X, int b, int64_t dim, double* G, double* lam, double* T_out) {
+int lowdin_rows(rom_ctx* ctx, double* X, int b, int64_t dim, Tmp& T_out) {
   if (b <= 0) return ROM_OK;
+  Tmp G, lam;
+  for (Tmp* t : {&G, &T_out}) ROM_TRY(t->get(ctx, size_t(b) * b));
+  ROM_TRY(lam.get(ctx, b));
   ROM_TRY(rom_launch_gram(ctx, b, dim, X, dim, G, b));
   ROM_TRY(romb_small_eig(ctx, b, G, b, lam, T_out, b, SE_LOWDIN, 1e-30));
-  if (b <= 64) return combine_rows(ctx, b, b, T_out, b, 0, nullptr, 0, 0.0, X, dim, nullptr, 0, X, dim, dim);
-  Tmp Y;
-  ROM_TRY(Y.get(ctx, size_t(b) * dim));
-  ROM_TRY(rom_launch_gemm_nn(ctx, b, dim, b, 1.0, T_out, b, X, dim, 0.0, Y, dim));
-  ROM_HIP(hipMemcpyAsync(X, Y.p(), size_t(b) * dim * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  return ROM_OK;
+  return apply_rows(ctx, b <= 64, b, b, T_out, 0, nullptr, 0.0, X, nullptr, X, dim);
 }
 
 // Right singular vectors / singular values of a tall factor given TRANSPOSED, Tt (b x M, ld M): Rayleigh-Ritz rounds on
@@ -759,26 +747,14 @@ int tall_svd_rotation(rom_ctx* ctx, double* Tt, int b, int M, double* Rt, double
     ROM_HIP(hipGetLastError());
     return ROM_OK;
   }
-  Tmp H, St, T2, R2;
-  ROM_TRY(H.get(ctx, size_t(b) * b));
-  ROM_TRY(St.get(ctx, size_t(b) * b));
-  if (b > 64) ROM_TRY(T2.get(ctx, size_t(b) * M));
-  ROM_TRY(R2.get(ctx, size_t(b) * b));
+  Tmp H, St;
+  for (Tmp* t : {&H, &St}) ROM_TRY(t->get(ctx, size_t(b) * b));
   for (int r = 0; r < rounds; ++r) {
     ROM_TRY(rom_launch_gemm_nt(ctx, b, b, M, 1.0, Tt, M, Tt, M, 0.0, H, b, "gemm_nt"));
     ROM_TRY(romb_small_eig(ctx, b, H, b, sig2, St, b, SE_EIG, 0.0));
-    if (b <= 64) {
-      ROM_TRY(combine_rows(ctx, b, b, St, b, 0, nullptr, 0, 0.0, Tt, M, nullptr, 0, Tt, M, M));   // Tt <- S Tt in place
-    } else {
-      ROM_TRY(rom_launch_gemm_nn(ctx, b, M, b, 1.0, St, b, Tt, M, 0.0, T2, M));
-      ROM_HIP(hipMemcpyAsync(Tt, T2.p(), size_t(b) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (r == 0) {
-      ROM_HIP(hipMemcpyAsync(Rt, St.p(), size_t(b) * b * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-      ROM_TRY(rom_launch_gemm_nn(ctx, b, b, b, 1.0, St, b, Rt, b, 0.0, R2, b));
-      ROM_HIP(hipMemcpyAsync(Rt, R2.p(), size_t(b) * b * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    ROM_TRY(apply_rows(ctx, b <= 64, b, b, St, 0, nullptr, 0.0, Tt, nullptr, Tt, M));   // Tt <- S Tt
+    if (r > 0) ROM_TRY(apply_rows(ctx, false, b, b, St, 0, nullptr, 0.0, Rt, nullptr, Rt, b));   // Rt <- S Rt
+    else ROM_HIP(hipMemcpyAsync(Rt, St.p(), size_t(b) * b * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   }
   return ROM_OK;
 }
@@ -831,146 +807,66 @@ int sketch_ahead_take(rom_ctx* ctx, SketchAhead& sa, int b, int seed, bool& hit)
   return ROM_OK;
 }
 
-// One sketch pass over the DEFLATED remainder of the (M, dim) block X: a randomised range finder with one power iteration,
-// thin products (2 b M dim flops each) instead of the 2 M^2 dim of a Gram matrix.
-// The block is deflated IMPLICITLY: X_d = X - Bt^T V with the `found` modes accepted so far (V: found x dim, orthonormal
-// rows; Bt: found x M, row j = X v_j).  Every product with X_d is the product with X followed by a rank-`found`
-// correction -- X itself is never rewritten, which saves a read + write of the whole block per accepted batch of modes.
-// The rounding error is what the explicit subtraction leaves in X_d as well: eps x sigma_1.
-// Out: Q (b x dim): orthonormal rows spanning the sketch; Rt (b x b): rows = right singular vectors of Q X_d^T in Q's
-// coordinates (mode i = row i of Rt Q); Traw (b x M) = Q X^T, the coefficients of the UNDEFLATED block (mode i's
-// coefficient row X v_i = row i of Rt Traw: the caller's next deflation needs no pass over X); ss_host: b singular values.
-// `pilot` (first pass only; returns true to abandon the pass -- ss_host then comes back empty): called after the first two
-// products with estimates of the sketch's singular values, the pivots of the M-space orthonormalisation.
-template <class Hook, class Pilot>
-int sketch_pass(rom_ctx* ctx, const double* X, int M, int64_t dim, const double* V, const double* Bt, int found, int b, int seed,
-                double* Q, const double* Om_ready, double* Rt, double* Traw, std::vector<double>& ss_host, PodInfo& info,
-                Hook before_rotation, int power, Pilot pilot) {
-  Tmp Om_own, Tt, Cc, Tm, lam, s2;
-  if (!Om_ready) ROM_TRY(Om_own.get(ctx, size_t(b) * M));
-  const double* Om = Om_ready ? Om_ready : Om_own.p();
-  ROM_TRY(Tt.get(ctx, size_t(b) * M));
-  ROM_TRY(Cc.get(ctx, size_t(b) * std::max(found, 1)));
-  ROM_TRY(Tm.get(ctx, size_t(b) * b));
-  ROM_TRY(lam.get(ctx, b));
-  ROM_TRY(s2.get(ctx, b));
-  const bool fused = found <= 512;   // (the correction kernel walks the found rows one by one: fine for any POD request)
-  // out (b x dim) -= (left (b x M) Bt^T) V
-  auto correct_rows = [&](double* out, const double* left) -> int {
-    if (found == 0) return ROM_OK;
-    ROM_TRY(rom_launch_gemm_nt(ctx, b, found, M, 1.0, left, M, Bt, M, 0.0, Cc, found, "gemm_nt"));
-    if (fused && b <= 64) return combine_rows(ctx, b, b, nullptr, 0, found, Cc, found, -1.0, out, dim, V, dim, out, dim, dim);
-    return rom_launch_gemm_nn(ctx, b, dim, found, -1.0, Cc, found, V, dim, 1.0, out, dim);
-  };
-  if (!Om_ready) {   // (else Q = Omega X is there already: started ahead on the second stream)
-    ROM_TRY(romb_fill_random(ctx, Om_own, size_t(b) * M, 0xabcd0000ull + unsigned(seed) * 7919u, true));
-    ROM_TRY(rom_launch_gemm_nn(ctx, b, dim, M, 1.0, Om, M, X, dim, 0.0, Q, dim));               // Q = Omega X_d
-  }
-  ROM_TRY(correct_rows(Q, Om));
-  info.executed += 2.0 * b * M * double(dim);
-  double* Tdefl = Tt;
-  for (int it = 0; it <= power; ++it) {
-    // orthonormal rows (rank may drop: zero rows), one round of Cholesky whitening each time.  Before the power step the
-    // rows only have to span the sketch and be aligned with its principal directions.  After it they are T' X_d with
-    // orthonormal T': graded and nearly orthogonal, the case in which a pivoted Cholesky factor of their Gram matrix is
-    // accurate relative to each row (its error follows the condition number of the SCALED matrix), so one round leaves
-    // them orthonormal to ~1e-15 (measured: the same singular values, angles and orthonormality as two rounds on the C2
-    // block and on spectra of 1 and 3 modes per decade over 13 orders -- tools/dev/pod_synth.py); the accepted modes are
-    // orthonormalised again by the caller
-    ROM_TRY(whiten_rows(ctx, Q, b, dim, 1e-26, 1, Tm, lam));
-    // Q X^T (b, M).  Without deflation it IS the factor of the step: before the power step it goes straight to Tt (nobody
-    // needs the undeflated copy of that step); at the end to Traw, which the one-workgroup Rayleigh-Ritz kernel reads without
-    // writing (one round), so that no copy is needed there either
-    const bool last = it == power;
-    double* Tout = (!found && !last) ? Tt.p() : Traw;
-    ROM_TRY(rom_launch_gemm_nt(ctx, b, M, dim, 1.0, Q, dim, X, dim, 0.0, Tout, M, "gemm_nt"));
-    if (found) {                                                                                  // Q X_d^T = Q X^T - (Q V^T) Bt
-      ROM_TRY(rom_launch_gemm_nt(ctx, b, found, dim, 1.0, Q, dim, V, dim, 0.0, Cc, found, "gemm_nt"));
-      if (fused && b <= 64) {
-        ROM_TRY(combine_rows(ctx, b, b, nullptr, 0, found, Cc, found, -1.0, Traw, M, Bt, M, Tt, M, M));
-      } else {
-        ROM_HIP(hipMemcpyAsync(Tt.p(), Traw, size_t(b) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        ROM_TRY(rom_launch_gemm_nn(ctx, b, M, found, -1.0, Cc, found, Bt, M, 1.0, Tt, M));
-      }
-    } else if (last && !tall_svd_is_fused(b, M)) {
-      ROM_HIP(hipMemcpyAsync(Tt.p(), Traw, size_t(b) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    info.executed += 2.0 * b * M * double(dim) + 4.0 * b * b * double(dim);
-    if (last) break;
-    // the coefficient rows orthonormalised in M space BEFORE the second product: a row dominated by its own direction (see
-    // SKETCH_ACCEPT) is cleaned of the strong directions to eps here, so the second product leaves eps r of them instead of
-    // the eps r^3 that limited a pass to four orders of magnitude -- one pass now reaches seven
-    ROM_TRY(whiten_rows(ctx, Tdefl, b, M, 1e-26, 1, Tm, lam));
-    if (it == 0) {
-      // (lam: the squared pivots of that orthonormalisation, in pivot order = the squared norms of the coefficient rows with
-      // the stronger rows taken out: sigma_k^2 of the sketch to a small factor, before any power step)
-      std::vector<double> est(b);
-      bool abandon = false;
-      ROM_TRY(pilot(lam, est, abandon));
-      if (abandon) {
-        ss_host.clear();
-        return ROM_OK;
-      }
-    }
-    ROM_TRY(rom_launch_gemm_nn(ctx, b, dim, M, 1.0, Tdefl, M, X, dim, 0.0, Q, dim));              // Q X_d^T X_d (Q is rebuilt)
-    ROM_TRY(correct_rows(Q, Tdefl));
-    info.executed += 2.0 * b * M * double(dim);
-  }
-  ROM_TRY(before_rotation());   // (the last pass over the block is enqueued: what may run beside the small problems starts here)
-  // X_d ~ T Q: the right singular vectors of the small factor rotate Q into the modes
-  // (one round: the pass only has to separate its leading directions from the rest and to rank them for the accept rule --
-  // the Rayleigh-Ritz step over ALL collected modes at the end of rom_pod_ex iterates to convergence)
-  ROM_TRY(tall_svd_rotation(ctx, (!found && tall_svd_is_fused(b, M)) ? Traw : Tt.p(), b, M, Rt, s2, 1));
-  ss_host.resize(b);
-  ROM_TRY(download(ctx, s2, ss_host.data(), b));
-  for (double& v : ss_host) v = std::sqrt(std::max(v, 0.0));
-  return ROM_OK;
-}
+// The cost model of the route decisions, in seconds, from the block's shape: one thin product over the block (HBM bound), a
+// sketch pass (four of them + its small problems), the Gram route (the Gram matrix on MFMA + its eigenproblem).
+struct PodCost {
+  double t_prod, t_pass, t_gram;
+  PodCost(int M, int64_t dim) : t_prod(double(M) * double(dim) * 8.0 / 4.5e12 + 30e-6), t_pass(4.0 * t_prod + 0.5e-3),
+                                t_gram(double(M) * double(M) * double(dim) / 55e12 + 1.5e-3) {}
+};
 
-}  // namespace
+// One sketch pass: what the driver's steps hand to each other.  A pass accepts modes over seven orders of magnitude
+// (SKETCH_ACCEPT) -- two dozen of them in a spectrum that decays like the snapshot blocks' do -- so it asks for at most
+// PASS_MODES (+ 8 of oversampling): the thin products scale with b, the small dense problems with b^3, and 32 rows is what
+// the one-workgroup kernels hold.  (A request with hundreds of modes left asks for more per pass: 24 per pass would be
+// n / 24 passes over the block.  Never fewer than 32 rows: the thin products are bound by the read of the block and the small
+// kernels hold 32 rows at the same cost, and every extra row lowers sigma_{b+1} -- what the accuracy of the accepted modes is
+// measured against)
+struct PodPass {
+  int p, left, want, b;     // number (= seed), modes still asked for, modes asked of this pass, sketch rows
+  bool hit = false;         // Q = Omega X is there already (taken from the product ahead, or the mean's product)
+  Tmp Q, Om, Rt, Traw;      // see PodRun::sketch_pass
+  std::vector<double> ss;   // the b singular values of the pass; empty: abandoned by the pilot
+  PodPass(int p, int left, int64_t range) : p(p), left(left), want(std::min(left, std::max(PASS_MODES, left / 4))),
+                                            b(int(std::min<int64_t>(range, std::max(want + 8, FUSED_ROWS)))) {}
+};
 
-// Leading n right singular vectors / singular values of the (M, dim) block X (overwritten when it is centred).
-// center != 0: subtract the column means first (sklearn PCA.fit).  V: (n, dim) rows = modes, sign convention of
-// sklearn's svd_flip(u_based_decision=False); sigma_host: n singular values (0 for completed modes);
-// info_host (8 doubles, may be null): resolved modes, completed modes, Gram passes (0 / 1), sketch passes, executed flops,
-// 8 n M dim (the thin products for the requested modes alone), subspace iterations of the Gram route, stop reason
-// (0 filled, 1 floor reached, 2 budget).
-// rel_floor: modes with sigma <= rel_floor * sigma_1 are not looked for (<= 0 or below the fp64 noise floor of the snapshots,
-// 1e-13: that floor -- what a full LAPACK SVD of the block resolves)
-extern "C" int rom_pod_ex(rom_ctx* ctx, rom_buf* Xb, int64_t x_row0, int M, int64_t dim, int n, int center, double rel_floor,
-                          rom_buf* Vb, int64_t v_row0, double* sigma_host, double* info_host) {
-  ROM_CHECK(ctx && Xb && Vb && (sigma_host || n == 0), "rom_pod: null argument");
-  const double floor_rel = rel_floor > NOISE_FLOOR ? rel_floor : NOISE_FLOOR;
-  ROM_CHECK(M >= 1 && dim >= 1 && n >= 0 && x_row0 >= 0 && v_row0 >= 0, "rom_pod: bad sizes");
-  ROM_CHECK(n <= std::min<int64_t>(M, dim), "rom_pod: %d modes requested from a %d x %lld block", n, M, (long long)dim);
-  ROM_CHECK(n + 12 <= SE_MAX, "rom_pod: at most %d modes", SE_MAX - 12);
-  ROM_CHECK(size_t(x_row0 + M) * dim <= Xb->n && size_t(v_row0 + n) * dim <= Vb->n, "rom_pod: buffers too small");
-  double* X = Xb->p + x_row0 * dim;
-  double* V = Vb->p + v_row0 * dim;
+// One call of rom_pod_ex: its arguments, the running state, and the steps of the driver in the order they run
+struct PodRun {
+  rom_ctx* ctx;
+  rom_buf* Vb;   // V = row v_row0 of it
+  int64_t v_row0;
+  double *X, *V;
+  int M;
+  int64_t dim;
+  int n, center;
+  double floor_rel;   // max(rel_floor, NOISE_FLOOR)
+  bool mean_from_sketch;   // the column means come out of the first pass's first product (kp_zero_sum_rows)
+  bool worth_ahead;        // the next pass's first product is started on the second stream
   PodInfo info;
-  // centring: the column means come out of the first pass's first product (kp_zero_sum_rows) when there is a pass
-  const bool mean_from_sketch = center && n > 0 && std::min<int64_t>(M, dim) >= 2;
-  if (center && !mean_from_sketch) {
+  int found = 0, power = 1;   // modes accepted so far (rows of V); power steps per pass (2 after a best-effort pass)
+  double sigma_1 = 0.0;
+  bool gram_done = false, at_floor_stop = false;
+  Tmp Bt;                  // coefficients of the accepted modes, (n, M): row j = X v_j
+  SketchAhead ahead;
+
+  // a sketch of b rows on top of the accepted modes spans the whole range of the block: exact
+  bool spans_range(int b) const { return b + found >= std::min<int64_t>(M, dim) - (center ? 1 : 0); }
+  // the rank-`found` corrections of a pass on the fused kernel (it walks the found rows one by one: fine for any POD request)
+  bool correction_fused(int b) const { return found <= 512 && b <= 64; }
+
+  int centre() {
+    if (!center || mean_from_sketch) return ROM_OK;
     Tmp mean;
     ROM_TRY(mean.get(ctx, dim));
-    ROM_TRY(rom_launch_center_rows(ctx, X, M, dim, mean));
+    return rom_launch_center_rows(ctx, X, M, dim, mean);
   }
-  for (int i = 0; i < n; ++i) sigma_host[i] = 0.0;
-  int found = 0;
-  double sigma_1 = 0.0;
-  Tmp Bt;  // coefficients of the accepted modes, (n, M): row j = X v_j
-  ROM_TRY(Bt.get(ctx, size_t(std::max(n, 1)) * M));
-  auto deflate = [&](int lo, int take) -> int {
-    // coefficients of the modes V[lo : lo + take] into Bt (row j = X v_j; the modes are orthogonal to the earlier ones, so
-    // X and the deflated block give the same coefficients).  X is not touched: the deflation is implicit (sketch_pass)
-    ROM_TRY(rom_launch_gemm_nt(ctx, take, M, dim, 1.0, V + size_t(lo) * dim, dim, X, dim, 0.0, Bt.p() + size_t(lo) * M, M, "gemm_nt"));
-    info.executed += 2.0 * take * M * double(dim);
-    return ROM_OK;
-  };
-  // The Gram route, for a spectrum that decays too slowly for the sketch passes (see the loop below): the leading modes
-  // from the M x M Gram matrix of the (centred) block -- eigenpairs to convergence in M space, modes down to 1e-5 sigma_1
-  // (GRAM_ACCEPT) lifted, orthonormalised, deflated; the passes below go on from there.
-  auto gram_route = [&]() -> int {
+
+  // The Gram route, for a spectrum that decays too slowly for the sketch passes: the leading modes from the M x M Gram
+  // matrix of the (centred) block -- eigenpairs to convergence in M space, modes down to 1e-5 sigma_1 (GRAM_ACCEPT) lifted,
+  // orthonormalised, deflated; the passes go on from there.  What the passes found so far is dropped.
+  int gram_route() {
+    gram_done = true;
     Tmp G, W, fac;
     ROM_TRY(G.get(ctx, size_t(M) * M));
     ROM_TRY(W.get(ctx, size_t(n) * M));
@@ -988,126 +884,167 @@ extern "C" int rom_pod_ex(rom_ctx* ctx, rom_buf* Xb, int64_t x_row0, int M, int6
     while (take < n && take < int(lam.size()) && lam[take] > GRAM_ACCEPT * lam[0] && lam[take] > 0 &&
            lam[take] > floor_rel * floor_rel * lam[0]) ++take;
     found = 0;
-    if (take) {
-      // rows of W / sigma_i, with the eigenvalues top_eigenpairs left on the device (no upload, no host synchronisation)
-      kp_scale_eigvec_rows<<<dim3(unsigned(std::min((M + 255) / 256, 64)), take), 256, 0, ctx->stream>>>(W, M, fac, 0.0);
-      ROM_HIP(hipGetLastError());
-      ROM_TRY(rom_launch_gemm_nn(ctx, take, dim, M, 1.0, W, M, X, dim, 0.0, V, dim));   // V = S^-1 W^T Xc
-      info.executed += 2.0 * take * M * double(dim);
-      {  // (lifted Gram modes are orthonormal to ~1e-6 at worst; the symmetric orthonormalisation is second order in that defect)
-        Tmp Gs, ls, Ts;
-        ROM_TRY(Gs.get(ctx, size_t(take) * take));
-        ROM_TRY(ls.get(ctx, take));
-        ROM_TRY(Ts.get(ctx, size_t(take) * take));
-        ROM_TRY(lowdin_rows(ctx, V, take, dim, Gs, ls, Ts));
-      }
-      ROM_TRY(deflate(0, take));
-      found = take;
-    }
+    if (!take) return ROM_OK;
+    // rows of W / sigma_i, with the eigenvalues top_eigenpairs left on the device (no upload, no host synchronisation)
+    kp_scale_eigvec_rows<<<dim3(unsigned(std::min((M + 255) / 256, 64)), take), 256, 0, ctx->stream>>>(W, M, fac, 0.0);
+    ROM_HIP(hipGetLastError());
+    ROM_TRY(rom_launch_gemm_nn(ctx, take, dim, M, 1.0, W, M, X, dim, 0.0, V, dim));   // V = S^-1 W^T Xc
+    info.executed += 2.0 * take * M * double(dim);
+    Tmp Ts;   // (lifted Gram modes are orthonormal to ~1e-6 at worst; the symmetric orthonormalisation is second order in that defect)
+    ROM_TRY(lowdin_rows(ctx, V, take, dim, Ts));
+    // their coefficients into Bt (row j = X v_j).  X is not touched: the deflation is implicit (sketch_pass)
+    ROM_TRY(rom_launch_gemm_nt(ctx, take, M, dim, 1.0, V, dim, X, dim, 0.0, Bt, M, "gemm_nt"));
+    info.executed += 2.0 * take * M * double(dim);
+    found = take;
     return ROM_OK;
-  };
-  // How many of the `take` leading modes of a pass have converged.  The range finder with one power step leaves
-  // (sigma_{b+1} / sigma_k)^3 of the directions beyond its b rows in mode k; sigma_{b+1} is not known, the smallest Ritz
-  // value of the sketch stands for it with a factor 10 (a Ritz value underestimates).  Wanted: LAPACK's own bound
-  // eps sigma_1 / sigma_k (x 10), or 1e-10 where that is smaller.  A sketch that spans the whole range is exact.
-  auto converged_prefix = [&](const std::vector<double>& ss, int b, int take, int power) -> int {
-    if (b + found >= std::min<int64_t>(M, dim) - (center ? 1 : 0) || take == 0) return take;
-    const double tail = 10.0 * ss[b - 1];
-    int k = 0;
-    while (k < take) {
-      const double rho = tail / ss[k];
-      if (std::pow(rho, 2 * power + 1) > std::max(1e-10, 10.0 * 1.1e-16 * sigma_1 / ss[k])) break;   // (q power steps: rho^(2 q + 1))
-      ++k;
-    }
-    return k;
-  };
-  bool gram_done = false;
-  int power = 1;   // power steps per pass: 2 once a pass has shown a spectrum too flat for one (best-effort regime below)
-  SketchAhead ahead;
-  // (blocks from 64 MB: below, the product is shorter than the stream hand-over.  dim >= 1024, M >= 128: the product then
-  // takes the thin LDS-DMA kernel; where it splits K instead, sketch_ahead_start gives it a partial buffer of its own --
-  // the context's scratch area belongs to the kernels of the main stream)
-  const bool worth_ahead = size_t(M) * dim * sizeof(double) >= (size_t(64) << 20) && dim >= 1024 && M >= 128;
-  // the sketch passes run until the request is filled or the spectrum has reached the floor; the budget below only guards
-  // against a pass that makes no progress (every pass accepts at least one mode or ends the loop)
-  const int passes = n + 2;
-  bool at_floor_stop = false;
-  for (int p = 1; p < passes; ++p) {
-    if (found >= n) break;
-    std::vector<double> ss;
-    // a pass accepts modes over seven orders of magnitude (SKETCH_ACCEPT) -- two dozen of them in a spectrum that decays
-    // like the snapshot blocks' do -- so it asks for at most PASS_MODES (+ 8 of oversampling): the thin products scale with
-    // b, the small dense problems with b^3, and 32 rows is what the one-workgroup kernels hold
-    // (a request with hundreds of modes left asks for more per pass: 24 per pass would be n / 24 passes over the block)
-    const int left = n - found;
-    const int want = std::min(left, std::max(PASS_MODES, left / 4));
-    // (never fewer than 32 rows: the thin products are bound by the read of the block and the small kernels hold 32 rows at
-    // the same cost, and every extra row lowers sigma_{b+1} -- what the accuracy of the accepted modes is measured against)
-    int b = int(std::min<int64_t>(std::min<int64_t>(M, dim), std::max(want + 8, FUSED_ROWS)));
-    Tmp Q, Om, Rt, Traw;
-    bool hit = false;
-    ROM_TRY(sketch_ahead_take(ctx, ahead, b, p, hit));
-    if (hit) {   // Q = Omega X of this pass is already there
-      std::swap(Q.b, ahead.Q.b);
-      std::swap(Om.b, ahead.Om.b);
+  }
+
+  // Q = Omega X of the pass, if it is there before the pass starts: taken from the product ahead, or -- first pass of a block
+  // still to be centred -- computed here for the sake of the column mean; and the pass's output blocks
+  int first_product(PodPass& ps) {
+    ROM_TRY(sketch_ahead_take(ctx, ahead, ps.b, ps.p, ps.hit));
+    if (ps.hit) {   // Q = Omega X of this pass is already there
+      std::swap(ps.Q.b, ahead.Q.b);
+      std::swap(ps.Om.b, ahead.Om.b);
     } else {
-      ROM_TRY(Q.get(ctx, size_t(b) * dim));
+      ROM_TRY(ps.Q.get(ctx, size_t(ps.b) * dim));
     }
-    if (p == 1 && mean_from_sketch) {
+    if (ps.p == 1 && mean_from_sketch) {
       // the first product on the block as it came, with zero-sum sketch rows and a row of 1 / M: its last row is the column
       // mean, which is then subtracted from the block (the one pass over X that the centring still costs); the pass goes on
       // with the b - 1 sketch rows.  (The product sees the uncentred values: its rounding is eps x THEIR size -- a sketch
       // only has to span the range, and every later product of the pass works on the centred block)
-      ROM_TRY(Om.get(ctx, size_t(b) * M));
-      ROM_TRY(romb_fill_random(ctx, Om, size_t(b) * M, 0xabcd0000ull + unsigned(p) * 7919u, true));
-      kp_zero_sum_rows<<<b, 256, 0, ctx->stream>>>(Om, M, b);
+      const int b = ps.b;
+      ROM_TRY(ps.Om.get(ctx, size_t(b) * M));
+      ROM_TRY(romb_fill_random(ctx, ps.Om, size_t(b) * M, 0xabcd0000ull + unsigned(ps.p) * 7919u, true));
+      kp_zero_sum_rows<<<b, 256, 0, ctx->stream>>>(ps.Om, M, b);
       ROM_HIP(hipGetLastError());
-      ROM_TRY(rom_launch_gemm_nn(ctx, b, dim, M, 1.0, Om, M, X, dim, 0.0, Q, dim));
-      ROM_TRY(rom_launch_subtract_row(ctx, X, M, dim, Q.p() + size_t(b - 1) * dim));
-      hit = true;
-      b -= 1;
+      ROM_TRY(rom_launch_gemm_nn(ctx, b, dim, M, 1.0, ps.Om, M, X, dim, 0.0, ps.Q, dim));
+      ROM_TRY(rom_launch_subtract_row(ctx, X, M, dim, ps.Q.p() + size_t(b - 1) * dim));
+      ps.hit = true;
+      ps.b -= 1;
     }
-    ROM_TRY(Rt.get(ctx, size_t(b) * b));
-    ROM_TRY(Traw.get(ctx, size_t(b) * M));
-    // the next pass's product beside this pass's Rayleigh-Ritz kernel: a next pass is certain -- unless the floor is reached --
-    // when this one cannot fill the request, and it asks for at most PASS_MODES + 8 rows as long as fewer than 4 PASS_MODES
-    // modes are left (32 rows are computed, the pass uses the leading b of them)
-    auto start_next = [&]() -> int {
-      if (left - want >= 1 && left - 1 <= 4 * PASS_MODES && worth_ahead)
-        return sketch_ahead_start(ctx, ahead, X, M, dim, int(std::min<int64_t>(std::min<int64_t>(M, dim), PASS_MODES + 8)), p + 1);
-      return ROM_OK;
-    };
-    // The first pass is a PILOT as well: after its first two products the pivots of the M-space orthonormalisation estimate the
-    // sketch's singular values.  If by them NO mode would meet the convergence rule (even without its safety factor) and the
-    // cost model prefers the Gram route, the pass is abandoned there -- its other two products over the block would be wasted
-    // (C5: 15 ms of 380).  A spectrum that decays fast never gets here: one read-back of b numbers.
-    auto pilot = [&](const double* d_lam, std::vector<double>& est, bool& abandon) -> int {
-      abandon = false;
-      if (p != 1 || found != 0 || gram_done || b + found >= std::min<int64_t>(M, dim) - (center ? 1 : 0)) return ROM_OK;
-      const double t_prod = double(M) * double(dim) * 8.0 / 4.5e12 + 30e-6, t_pass = 4.0 * t_prod + 0.5e-3;
-      const double t_gram = double(M) * double(M) * double(dim) / 55e12 + 1.5e-3;
-      if (2.0 * t_prod < 1e-3 || t_gram > 50.0 * t_pass) return ROM_OK;   // (nothing to save / the Gram route is not an option)
-      ROM_TRY(download(ctx, d_lam, est.data(), b));
-      for (double& v : est) v = std::sqrt(std::max(v, 0.0));
-      std::sort(est.begin(), est.end(), std::greater<double>());
-      if (!(est[0] > 0.0)) return ROM_OK;
-      const double rho = est[b - 1] / est[0];
-      abandon = rho * rho * rho > std::max(1e-10, 10.0 * 1.1e-16);   // (the rule of converged_prefix for the STRONGEST mode, no safety factor)
-      return ROM_OK;
-    };
-    ROM_TRY(sketch_pass(ctx, X, M, dim, V, Bt, found, b, p, Q, hit ? Om.p() : nullptr, Rt, Traw, ss, info, start_next, power, pilot));
-    if (ss.empty()) {   // the pilot said: a slowly decaying spectrum
-      gram_done = true;
-      ROM_TRY(gram_route());
-      if (found == 0) break;
-      continue;
+    ROM_TRY(ps.Rt.get(ctx, size_t(ps.b) * ps.b));
+    return ps.Traw.get(ctx, size_t(ps.b) * M);
+  }
+
+  // The first pass is a PILOT as well: after its first two products the pivots of the M-space orthonormalisation (d_lam:
+  // their squares, in pivot order = the squared norms of the coefficient rows with the stronger rows taken out: sigma_k^2
+  // of the sketch to a small factor, before any power step) estimate the sketch's singular values.  If by them NO mode
+  // would meet the convergence rule (even without its safety factor) and the cost model prefers the Gram route, the pass is
+  // abandoned there -- its other two products over the block would be wasted (C5: 15 ms of 380).  A spectrum that decays
+  // fast never gets here: one read-back of b numbers.
+  int pilot(const PodPass& ps, const double* d_lam, bool& abandon) {
+    abandon = false;
+    if (ps.p != 1 || found != 0 || gram_done || spans_range(ps.b)) return ROM_OK;
+    const PodCost c(M, dim);
+    if (2.0 * c.t_prod < 1e-3 || c.t_gram > 50.0 * c.t_pass) return ROM_OK;   // (nothing to save / the Gram route is not an option)
+    std::vector<double> est(ps.b);
+    ROM_TRY(download(ctx, d_lam, est.data(), ps.b));
+    for (double& v : est) v = std::sqrt(std::max(v, 0.0));
+    std::sort(est.begin(), est.end(), std::greater<double>());
+    if (!(est[0] > 0.0)) return ROM_OK;
+    const double rho = est[ps.b - 1] / est[0];
+    abandon = rho * rho * rho > std::max(1e-10, 10.0 * 1.1e-16);   // (the rule of converged_prefix for the STRONGEST mode, no safety factor)
+    return ROM_OK;
+  }
+
+  // the next pass's product beside this pass's Rayleigh-Ritz kernel: a next pass is certain -- unless the floor is reached --
+  // when this one cannot fill the request, and it asks for at most PASS_MODES + 8 rows as long as fewer than 4 PASS_MODES
+  // modes are left (32 rows are computed, the pass uses the leading b of them)
+  int start_next(const PodPass& ps) {
+    if (ps.left - ps.want >= 1 && ps.left - 1 <= 4 * PASS_MODES && worth_ahead)
+      return sketch_ahead_start(ctx, ahead, X, M, dim, int(std::min<int64_t>(std::min<int64_t>(M, dim), PASS_MODES + 8)), ps.p + 1);
+    return ROM_OK;
+  }
+
+  // out (b x dim) -= (left (b x M) Bt^T) V: the correction of a product with X to the product with the deflated block
+  int correct_rows(int b, double* Cc, double* out, const double* left) {
+    if (found == 0) return ROM_OK;
+    ROM_TRY(rom_launch_gemm_nt(ctx, b, found, M, 1.0, left, M, Bt, M, 0.0, Cc, found, "gemm_nt"));
+    return apply_rows(ctx, correction_fused(b), b, b, nullptr, found, Cc, -1.0, out, V, out, dim);
+  }
+
+  // One sketch pass over the DEFLATED remainder of the (M, dim) block X: a randomised range finder with `power` power
+  // iterations, thin products (2 b M dim flops each) instead of the 2 M^2 dim of a Gram matrix.
+  // The block is deflated IMPLICITLY: X_d = X - Bt^T V with the `found` modes accepted so far (V: found x dim, orthonormal
+  // rows; Bt: found x M, row j = X v_j).  Every product with X_d is the product with X followed by a rank-`found`
+  // correction -- X itself is never rewritten, which saves a read + write of the whole block per accepted batch of modes.
+  // The rounding error is what the explicit subtraction leaves in X_d as well: eps x sigma_1.
+  // Out: Q (b x dim): orthonormal rows spanning the sketch; Rt (b x b): rows = right singular vectors of Q X_d^T in Q's
+  // coordinates (mode i = row i of Rt Q); Traw (b x M) = Q X^T, the coefficients of the UNDEFLATED block (mode i's
+  // coefficient row X v_i = row i of Rt Traw: the next deflation needs no pass over X); ss: b singular values -- empty
+  // when the pilot abandoned the pass after its first two products.
+  int sketch_pass(PodPass& ps) {
+    const int b = ps.b;
+    double *Q = ps.Q, *Traw = ps.Traw;
+    Tmp Tt, Cc, Tm, lam, s2;
+    if (!ps.hit) ROM_TRY(ps.Om.get(ctx, size_t(b) * M));
+    ROM_TRY(Tt.get(ctx, size_t(b) * M));
+    ROM_TRY(Cc.get(ctx, size_t(b) * std::max(found, 1)));
+    ROM_TRY(Tm.get(ctx, size_t(b) * b));
+    ROM_TRY(lam.get(ctx, b));
+    ROM_TRY(s2.get(ctx, b));
+    if (!ps.hit) {   // (else Q = Omega X is there already)
+      ROM_TRY(romb_fill_random(ctx, ps.Om, size_t(b) * M, 0xabcd0000ull + unsigned(ps.p) * 7919u, true));
+      ROM_TRY(rom_launch_gemm_nn(ctx, b, dim, M, 1.0, ps.Om, M, X, dim, 0.0, Q, dim));            // Q = Omega X_d
     }
-    info.sketch_passes += 1;
+    ROM_TRY(correct_rows(b, Cc, Q, ps.Om));
+    info.executed += 2.0 * b * M * double(dim);
+    for (int it = 0; it <= power; ++it) {
+      // orthonormal rows (rank may drop: zero rows), one round of Cholesky whitening each time.  Before the power step the
+      // rows only have to span the sketch and be aligned with its principal directions.  After it they are T' X_d with
+      // orthonormal T': graded and nearly orthogonal, the case in which a pivoted Cholesky factor of their Gram matrix is
+      // accurate relative to each row (its error follows the condition number of the SCALED matrix), so one round leaves
+      // them orthonormal to ~1e-15 (measured: the same singular values, angles and orthonormality as two rounds on the C2
+      // block and on spectra of 1 and 3 modes per decade over 13 orders -- tools/dev/pod_synth.py); the accepted modes are
+      // orthonormalised again by accept()
+      ROM_TRY(whiten_rows(ctx, Q, b, dim, 1e-26, 1, Tm, lam));
+      // Q X^T (b, M).  Without deflation it IS the factor of the step: before the power step it goes straight to Tt (nobody
+      // needs the undeflated copy of that step); at the end to Traw, which the one-workgroup Rayleigh-Ritz kernel reads without
+      // writing (one round), so that no copy is needed there either
+      const bool last = it == power;
+      double* Tout = (!found && !last) ? Tt.p() : Traw;
+      ROM_TRY(rom_launch_gemm_nt(ctx, b, M, dim, 1.0, Q, dim, X, dim, 0.0, Tout, M, "gemm_nt"));
+      if (found) {                                                                                  // Q X_d^T = Q X^T - (Q V^T) Bt
+        ROM_TRY(rom_launch_gemm_nt(ctx, b, found, dim, 1.0, Q, dim, V, dim, 0.0, Cc, found, "gemm_nt"));
+        ROM_TRY(apply_rows(ctx, correction_fused(b), b, b, nullptr, found, Cc, -1.0, Traw, Bt, Tt, M));
+      } else if (last && !tall_svd_is_fused(b, M)) {
+        ROM_HIP(hipMemcpyAsync(Tt.p(), Traw, size_t(b) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      info.executed += 2.0 * b * M * double(dim) + 4.0 * b * b * double(dim);
+      if (last) break;
+      // the coefficient rows orthonormalised in M space BEFORE the second product: a row dominated by its own direction (see
+      // SKETCH_ACCEPT) is cleaned of the strong directions to eps here, so the second product leaves eps r of them instead of
+      // the eps r^3 that limited a pass to four orders of magnitude -- one pass now reaches seven
+      ROM_TRY(whiten_rows(ctx, Tt, b, M, 1e-26, 1, Tm, lam));
+      if (it == 0) {
+        bool abandon = false;
+        ROM_TRY(pilot(ps, lam, abandon));
+        if (abandon) return ROM_OK;   // (ss stays empty)
+      }
+      ROM_TRY(rom_launch_gemm_nn(ctx, b, dim, M, 1.0, Tt, M, X, dim, 0.0, Q, dim));              // Q X_d^T X_d (Q is rebuilt)
+      ROM_TRY(correct_rows(b, Cc, Q, Tt));
+      info.executed += 2.0 * b * M * double(dim);
+    }
+    ROM_TRY(start_next(ps));   // (the last pass over the block is enqueued: what may run beside the small problems starts here)
+    // X_d ~ T Q: the right singular vectors of the small factor rotate Q into the modes
+    // (one round: the pass only has to separate its leading directions from the rest and to rank them for the accept rule --
+    // rayleigh_ritz over ALL collected modes iterates to convergence)
+    ROM_TRY(tall_svd_rotation(ctx, (!found && tall_svd_is_fused(b, M)) ? Traw : Tt.p(), b, M, ps.Rt, s2, 1));
+    ps.ss.resize(b);
+    ROM_TRY(download(ctx, s2, ps.ss.data(), b));
+    for (double& v : ps.ss) v = std::sqrt(std::max(v, 0.0));
+    return ROM_OK;
+  }
+
+  // Nothing came out of the first pass.  A block of zeros is one reason (take_count deals with it); the others are not
+  // silent: NaN / Inf entries (scikit-learn's PCA raises on those) and entries so large or small that their squares leave
+  // the range of fp64 -- every inner product of the passes is then Inf or 0.  One more look at the block tells them apart;
+  // no call with a first singular value pays for it.
+  int diagnose_empty_first_pass(const PodPass& ps) {
+    const std::vector<double>& ss = ps.ss;
     if (found == 0 && !gram_done && !(ss[0] > 0.0 && ss[0] <= 1.7976931348623157e308)) {
-      // nothing came out of the first pass.  A block of zeros is one reason (the floor logic below deals with it); the others
-      // are not silent: NaN / Inf entries (scikit-learn's PCA raises on those) and entries so large or small that their
-      // squares leave the range of fp64 -- every inner product of the passes is then Inf or 0.  One more look at the block
-      // tells them apart; no call with a first singular value pays for it.
       Tmp st;
       ROM_TRY(st.get(ctx, 2));
       unsigned long long* d_st = reinterpret_cast<unsigned long long*>(st.p());
@@ -1127,152 +1064,208 @@ extern "C" int rom_pod_ex(rom_ctx* ctx, rom_buf* Xb, int64_t x_row0, int M, int6
     // range of fp64 and the rotations stop silently -- LAPACK would rescale; this library says so)
     ROM_CHECK(found > 0 || gram_done || ss[0] == 0.0 || (ss[0] < 1e70 && ss[0] > 1e-70),
               "rom_pod: singular values of magnitude %.3g -- their fourth powers leave the range of fp64; rescale the block", ss[0]);
+    return ROM_OK;
+  }
+
+  // How many of the `take` leading modes of a pass have converged.  The range finder with q power steps leaves
+  // (sigma_{b+1} / sigma_k)^(2 q + 1) of the directions beyond its b rows in mode k; sigma_{b+1} is not known, the smallest
+  // Ritz value of the sketch stands for it with a factor 10 (a Ritz value underestimates).  Wanted: LAPACK's own bound
+  // eps sigma_1 / sigma_k (x 10), or 1e-10 where that is smaller.  A sketch that spans the whole range is exact.
+  int converged_prefix(const PodPass& ps, int take) const {
+    if (spans_range(ps.b) || take == 0) return take;
+    const double tail = 10.0 * ps.ss[ps.b - 1];
+    int k = 0;   // (rho = tail / ss[k]; q power steps: rho^(2 q + 1))
+    while (k < take && !(std::pow(tail / ps.ss[k], 2 * power + 1) > std::max(1e-10, 10.0 * 1.1e-16 * sigma_1 / ps.ss[k]))) ++k;
+    return k;
+  }
+
+  // How many modes of the pass are accepted: 0 = none (stop; at_floor_stop says whether the floor is the reason), -1 = the
+  // result of the first pass is dropped and the Gram route takes over.
+  int take_count(const PodPass& ps) {
+    const std::vector<double>& ss = ps.ss;
+    const int b = ps.b;
     if (found == 0) sigma_1 = ss.empty() ? 0.0 : ss[0];
     int take = 0;
-    while (take < std::min(b, want) && ss[take] > SKETCH_ACCEPT * ss[0] && ss[take] > floor_rel * sigma_1) ++take;
+    while (take < std::min(b, ps.want) && ss[take] > SKETCH_ACCEPT * ss[0] && ss[take] > floor_rel * sigma_1) ++take;
     if (take == 0) {
       at_floor_stop = b == 0 || ss[0] <= floor_rel * sigma_1;
-      break;
+      return 0;
     }
-    {
-      // A slowly decaying spectrum: only a prefix of the modes has converged (the rest stays in the deflated block for the
-      // next pass, at the top of its sketch).  When the first pass shows that the passes would cost more than the Gram
-      // route -- whose iterations run in M space, 2 M^2 b flops each instead of two passes over the block -- its result is
-      // dropped and the Gram route takes over; later passes without a converged mode accept what the rules above give.
-      const int good = converged_prefix(ss, b, take, power);
-      if (good < take && found == 0 && !gram_done) {
-        const double t_prod = double(M) * double(dim) * 8.0 / 4.5e12 + 30e-6, t_pass = 4.0 * t_prod + 0.5e-3;
-        const double t_gram = double(M) * double(M) * double(dim) / 55e12 + 1.5e-3;
-        const double passes_left = good > 0 ? std::ceil(double(left) / good) : 1e9;
-        if (passes_left * t_pass > t_gram + t_pass) {
-          gram_done = true;
-          ROM_TRY(gram_route());
-          if (found == 0) break;   // (a zero block)
-          continue;
-        }
-      }
-      if (good >= 1) {
-        take = good;
-      } else {
-        // no mode of this pass meets the bound (a slowly decaying spectrum below the reach of the Gram route): best effort --
-        // the modes at least a factor 4 above the bottom of the sketch (their share of the directions beyond the sketch is
-        // ~(1/4)^3), at least one; the rest is left for the next pass, where it sits at the top
-        int k = 0;
-        while (k < take && ss[k] >= 4.0 * ss[b - 1]) ++k;
-        // (none: a plateau -- typically the rounding noise of a block with a large mean, above the floor because the floor
-        // is relative to sigma_1 of the CENTRED block -- whose directions no method tells apart: a quarter of the sketch per pass)
-        take = k > 0 ? k : std::max(1, std::min(take, b / 4));
-        power = 2;   // (and the passes from here on take a second power step: (1/4)^5 instead of (1/4)^3)
-      }
+    // A slowly decaying spectrum: only a prefix of the modes has converged (the rest stays in the deflated block for the
+    // next pass, at the top of its sketch).  When the first pass shows that the passes would cost more than the Gram
+    // route -- whose iterations run in M space, 2 M^2 b flops each instead of two passes over the block -- its result is
+    // dropped and the Gram route takes over; later passes without a converged mode accept what the rules above give.
+    const int good = converged_prefix(ps, take);
+    if (good < take && found == 0 && !gram_done) {
+      const PodCost c(M, dim);
+      const double passes_left = good > 0 ? std::ceil(double(ps.left) / good) : 1e9;
+      if (passes_left * c.t_pass > c.t_gram + c.t_pass) return -1;
     }
+    if (good >= 1) return good;
+    // no mode of this pass meets the bound (a slowly decaying spectrum below the reach of the Gram route): best effort --
+    // the modes at least a factor 4 above the bottom of the sketch (their share of the directions beyond the sketch is
+    // ~(1/4)^3), at least one; the rest is left for the next pass, where it sits at the top
+    int k = 0;
+    while (k < take && ss[k] >= 4.0 * ss[b - 1]) ++k;
+    power = 2;   // (and the passes from here on take a second power step: (1/4)^5 instead of (1/4)^3)
+    // (none: a plateau -- typically the rounding noise of a block with a large mean, above the floor because the floor
+    // is relative to sigma_1 of the CENTRED block -- whose directions no method tells apart: a quarter of the sketch per pass)
+    return k > 0 ? k : std::max(1, std::min(take, b / 4));
+  }
+
+  // The first `take` modes of the pass join V and Bt: rows of Rt Q and of Rt Traw (their coefficient rows X v_i), made
+  // orthogonal to the earlier modes (block Gram-Schmidt, twice) and orthonormal among themselves (symmetric
+  // orthonormalisation); every step is a small linear map of the new rows and of the old ones, so the coefficient rows
+  // follow by the same maps in M space: X (v - C V_old)^T = X v^T - C Bt_old -- no pass over the block for the deflation
+  int accept(const PodPass& ps, int take) {
+    const int b = ps.b;
     double* Vn = V + size_t(found) * dim;
     double* Bn = Bt.p() + size_t(found) * M;
-    // the accepted modes = the first `take` rows of Rt Q, written where they belong; their coefficient rows X v_i = Rt Traw
-    if (b <= 64 && take <= 64) {
-      ROM_TRY(combine_rows(ctx, take, b, Rt, b, 0, nullptr, 0, 0.0, Q, dim, nullptr, 0, Vn, dim, dim));
-      ROM_TRY(combine_rows(ctx, take, b, Rt, b, 0, nullptr, 0, 0.0, Traw, M, nullptr, 0, Bn, M, M));
-    } else {
-      ROM_TRY(rom_launch_gemm_nn(ctx, take, dim, b, 1.0, Rt, b, Q, dim, 0.0, Vn, dim));
-      ROM_TRY(rom_launch_gemm_nn(ctx, take, M, b, 1.0, Rt, b, Traw, M, 0.0, Bn, M));
-    }
+    ROM_TRY(apply_rows(ctx, b <= 64 && take <= 64, take, b, ps.Rt, 0, nullptr, 0.0, ps.Q, nullptr, Vn, dim));
+    ROM_TRY(apply_rows(ctx, b <= 64 && take <= 64, take, b, ps.Rt, 0, nullptr, 0.0, ps.Traw, nullptr, Bn, M));
     info.executed += 2.0 * take * b * double(dim);
-    // orthogonal to the earlier modes (block Gram-Schmidt, twice), orthonormal among themselves (symmetric
-    // orthonormalisation); every step is a small linear map of the new rows and of the old ones, so the coefficient rows
-    // follow by the same maps in M space: X (v - C V_old)^T = X v^T - C Bt_old -- no pass over the block for the deflation
-    {
-      Tmp C, Gs, ls, Ts;
-      ROM_TRY(C.get(ctx, size_t(take) * std::max(found, 1)));
-      ROM_TRY(Gs.get(ctx, size_t(take) * take));
-      ROM_TRY(ls.get(ctx, take));
-      ROM_TRY(Ts.get(ctx, size_t(take) * take));
-      for (int r = 0; r < 2 && found > 0; ++r) {
-        ROM_TRY(rom_launch_gemm_nt(ctx, take, found, dim, 1.0, Vn, dim, V, dim, 0.0, C, found, "gemm_nt"));
-        if (take <= 64) {
-          ROM_TRY(combine_rows(ctx, take, take, nullptr, 0, found, C, found, -1.0, Vn, dim, V, dim, Vn, dim, dim));
-          ROM_TRY(combine_rows(ctx, take, take, nullptr, 0, found, C, found, -1.0, Bn, M, Bt, M, Bn, M, M));
-        } else {
-          ROM_TRY(rom_launch_gemm_nn(ctx, take, dim, found, -1.0, C, found, V, dim, 1.0, Vn, dim));
-          ROM_TRY(rom_launch_gemm_nn(ctx, take, M, found, -1.0, C, found, Bt, M, 1.0, Bn, M));
-        }
-      }
-      ROM_TRY(lowdin_rows(ctx, Vn, take, dim, Gs, ls, Ts));
-      if (take <= 64) {
-        ROM_TRY(combine_rows(ctx, take, take, Ts, take, 0, nullptr, 0, 0.0, Bn, M, nullptr, 0, Bn, M, M));
-      } else {
-        Tmp B2;
-        ROM_TRY(B2.get(ctx, size_t(take) * M));
-        ROM_TRY(rom_launch_gemm_nn(ctx, take, M, take, 1.0, Ts, take, Bn, M, 0.0, B2, M));
-        ROM_HIP(hipMemcpyAsync(Bn, B2.p(), size_t(take) * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      }
+    Tmp C, Ts;
+    ROM_TRY(C.get(ctx, size_t(take) * std::max(found, 1)));
+    for (int r = 0; r < 2 && found > 0; ++r) {
+      ROM_TRY(rom_launch_gemm_nt(ctx, take, found, dim, 1.0, Vn, dim, V, dim, 0.0, C, found, "gemm_nt"));
+      ROM_TRY(apply_rows(ctx, take <= 64, take, take, nullptr, found, C, -1.0, Vn, V, Vn, dim));
+      ROM_TRY(apply_rows(ctx, take <= 64, take, take, nullptr, found, C, -1.0, Bn, Bt, Bn, M));
     }
+    ROM_TRY(lowdin_rows(ctx, Vn, take, dim, Ts));
+    ROM_TRY(apply_rows(ctx, take <= 64, take, take, Ts, 0, nullptr, 0.0, Bn, nullptr, Bn, M));
     // the first value NOT accepted says "floor reached" only if the pass resolves values that small: below 1e-8 of its top
     // (eps r^2 ~ 1, see SKETCH_ACCEPT) a Ritz value is rounding noise -- a cliff of more than eight orders behind the accepted
     // modes hides whatever lies between the cliff's foot and the floor, and the next pass, on the deflated block, looks there
-    const bool at_floor = take < b && ss[take] <= floor_rel * sigma_1 && floor_rel * sigma_1 >= 1e-8 * ss[0];
+    at_floor_stop = take < b && ps.ss[take] <= floor_rel * sigma_1 && floor_rel * sigma_1 >= 1e-8 * ps.ss[0];
     found += take;
-    if (at_floor) {  // the spectrum has reached the floor: nothing left to find
-      at_floor_stop = true;
-      break;
-    }
+    return ROM_OK;
   }
-  {
-    bool unused = false;
-    ROM_TRY(sketch_ahead_take(ctx, ahead, -1, -1, unused));   // (a product started for a pass that did not happen)
-  }
-  if (found) {
-    // Rayleigh-Ritz on the collected subspace: X ~ B V  ->  the SVD of B orders / rotates the modes
-    Tmp Rt, s2, Vr;
+
+  // Rayleigh-Ritz on the collected subspace: X ~ B V  ->  the SVD of B orders / rotates the modes
+  int rayleigh_ritz(double* sigma_host) {
+    if (!found) return ROM_OK;
+    Tmp Rt, s2;
     ROM_TRY(Rt.get(ctx, size_t(found) * found));
     ROM_TRY(s2.get(ctx, found));
     ROM_TRY(tall_svd_rotation(ctx, Bt, found, M, Rt, s2));
-    if (found <= 64) {
-      ROM_TRY(combine_rows(ctx, found, found, Rt, found, 0, nullptr, 0, 0.0, V, dim, nullptr, 0, V, dim, dim));   // in place
-    } else {
-      ROM_TRY(Vr.get(ctx, size_t(found) * dim));
-      ROM_TRY(rom_launch_gemm_nn(ctx, found, dim, found, 1.0, Rt, found, V, dim, 0.0, Vr, dim));
-      ROM_HIP(hipMemcpyAsync(V, Vr.p(), size_t(found) * dim * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    ROM_TRY(apply_rows(ctx, found <= 64, found, found, Rt, 0, nullptr, 0.0, V, nullptr, V, dim));
     info.executed += 2.0 * found * found * double(dim);
     std::vector<double> s(found);
     ROM_TRY(download(ctx, s2, s.data(), found));
     for (int i = 0; i < found; ++i) sigma_host[i] = std::sqrt(std::max(s[i], 0.0));
+    return ROM_OK;
   }
-  if (found < n) {
-    // complete the basis: random directions orthonormalised against the modes; they carry no variance (LAPACK and
-    // scikit-learn return SOME orthonormal directions there too).  Seeded by the count of resolved modes: deterministic.
+
+  // complete the basis: random directions orthonormalised against the modes; they carry no variance (LAPACK and
+  // scikit-learn return SOME orthonormal directions there too).  Seeded by the count of resolved modes: deterministic.
+  int complete() {
     const int rest = n - found;
-    if (rest <= FUSED_ROWS && found <= 512) {   // (the fused row kernels; same seed as rom_complete_orthonormal)
-      double* Vn = V + size_t(found) * dim;
-      Tmp C, Tm, lam;
-      ROM_TRY(C.get(ctx, size_t(rest) * std::max(found, 1)));
-      ROM_TRY(Tm.get(ctx, size_t(rest) * rest));
-      ROM_TRY(lam.get(ctx, rest));
-      ROM_TRY(romb_fill_random(ctx, Vn, size_t(rest) * dim, 0xc0de0000ull + unsigned(found), false));
-      for (int r = 0; r < 2 && found > 0; ++r) {
-        ROM_TRY(rom_launch_gemm_nt(ctx, rest, found, dim, 1.0, Vn, dim, V, dim, 0.0, C, found, "gemm_nt"));
-        ROM_TRY(combine_rows(ctx, rest, rest, nullptr, 0, found, C, found, -1.0, Vn, dim, V, dim, Vn, dim, dim));
-      }
-      ROM_TRY(whiten_rows(ctx, Vn, rest, dim, 1e-26, 1, Tm, lam));
-    } else {
-      ROM_TRY(rom_complete_orthonormal(ctx, Vb, v_row0, found, rest, dim));
-    }
+    if (rest <= 0) return ROM_OK;
     info.completed = rest;
+    if (rest > FUSED_ROWS || found > 512) return rom_complete_orthonormal(ctx, Vb, v_row0, found, rest, dim);
+    // (the fused row kernels; same seed as rom_complete_orthonormal)
+    double* Vn = V + size_t(found) * dim;
+    Tmp C, Tm, lam;
+    ROM_TRY(C.get(ctx, size_t(rest) * std::max(found, 1)));
+    ROM_TRY(Tm.get(ctx, size_t(rest) * rest));
+    ROM_TRY(lam.get(ctx, rest));
+    ROM_TRY(romb_fill_random(ctx, Vn, size_t(rest) * dim, 0xc0de0000ull + unsigned(found), false));
+    for (int r = 0; r < 2 && found > 0; ++r) {
+      ROM_TRY(rom_launch_gemm_nt(ctx, rest, found, dim, 1.0, Vn, dim, V, dim, 0.0, C, found, "gemm_nt"));
+      ROM_TRY(apply_rows(ctx, true, rest, rest, nullptr, found, C, -1.0, Vn, V, Vn, dim));   // (rest <= FUSED_ROWS here)
+    }
+    return whiten_rows(ctx, Vn, rest, dim, 1e-26, 1, Tm, lam);
   }
-  info.resolved = found;
-  if (n > 0) ROM_TRY(rom_launch_rows_sign_flip(ctx, V, n, dim));  // svd_flip(u_based_decision=False)
+
+  void write_info(double* info_host) const {
+    if (!info_host) return;
+    // (the fields: see rom_pod_ex.  Stopped short of n modes at the floor: the completed modes are not determined by the
+    // data; on the pass budget or without an accepted mode in a pass: modes above the floor may be missing)
+    const double stop = found >= n ? (info.unconverged ? 2.0 : 0.0) : (at_floor_stop || sigma_1 == 0.0 ? 1.0 : 2.0);
+    const double v[8] = {double(found), double(info.completed), double(info.gram_passes), double(info.sketch_passes),
+                         info.executed, 8.0 * n * M * double(dim), double(info.eig_iterations), stop};
+    std::copy(v, v + 8, info_host);
+  }
+};
+
+}  // namespace
+
+// Leading n right singular vectors / singular values of the (M, dim) block X (overwritten when it is centred).
+// center != 0: subtract the column means first (sklearn PCA.fit).  V: (n, dim) rows = modes, sign convention of
+// sklearn's svd_flip(u_based_decision=False); sigma_host: n singular values (0 for completed modes);
+// info_host (8 doubles, may be null): resolved modes, completed modes, Gram passes (0 / 1), sketch passes, executed flops,
+// 8 n M dim (the thin products for the requested modes alone), subspace iterations of the Gram route, stop reason
+// (0 filled, 1 floor reached, 2 budget).
+// rel_floor: modes with sigma <= rel_floor * sigma_1 are not looked for (<= 0 or below the fp64 noise floor of the snapshots,
+// 1e-13: that floor -- what a full LAPACK SVD of the block resolves)
+// The route table (names as in tests/test_gpu_pod_routes.py: ROUTES) -> the code that takes the route, and when:
+//   centre_explicit       PodRun::centre: center and no pass to take the mean from (n = 0, M = 1 or dim = 1)
+//   centre_sketch         PodRun::first_product, p == 1 && mean_from_sketch: the mean is the last row of the first product
+//   ahead_hit             PodRun::start_next (left - want >= 1, left - 1 <= 96, worth_ahead); first_product takes the product
+//   one_pass, multi_pass  the loop below: PodPass (its rows), first_product, sketch_pass, take_count, accept -- once / repeated
+//   pilot                 PodRun::pilot in the first sketch_pass leaves ss empty (its comment has the conditions): gram_route
+//   gram                  PodRun::take_count == -1 (first pass, good < take, ceil(left / good) t_pass > t_gram + t_pass):
+//                         gram_route -> top_eigenpairs, whose branches are
+//     lowrank_first / lowrank_second   lowrank_eigenpairs: the 32-step / the LOWRANK_CAP-step factor ended by tolerance, accepted
+//     lowrank_rejected      lowrank_eigenpairs: done = 0 after a factor that ended by tolerance (LOWRANK_RESIDUAL)
+//     full_eig_size / full_eig_stall   full_eig at once, M <= SE_GRID_MAX and 2 (n + 12) >= M / after the iteration stalled
+//     subspace_iter(_large) the iteration converged (M <= 2048 / M > 2048)
+//   best_effort           PodRun::take_count, good == 0 and no Gram route: ss >= 4 ss[b - 1] (or b / 4 rows), power = 2
+//   combine_rows          apply_rows(fused = true), at every site whose own predicate holds
+//   correction_gemm       PodRun::correct_rows and the Traw deflation of sketch_pass, !correction_fused(b): found > 512 or b > 64
+//   pass_gemm             PodRun::accept, b > 64 and take > 64: Rt Q, Rt Traw, Gram-Schmidt and the Loewdin map by GEMM
+//   pass_gemm_small_take  PodRun::accept, b > 64 and take <= 64: Rt Q, Rt Traw by GEMM, the other maps (take <= 64) fused
+//   cliff                 PodRun::accept leaves at_floor_stop false while floor sigma_1 < 1e-8 ss[0]: the next pass looks below
+//   floor, floor_rel      PodRun::take_count (take == 0, ss[0] <= floor_rel sigma_1) or accept (ss[take] <= floor_rel sigma_1)
+//   zero_block            sigma_1 == 0: take_count returns 0 in the first pass (or gram_route leaves found == 0)
+//   tall_svd_unfused      tall_svd_rotation, !tall_svd_is_fused(found, M), from PodRun::rayleigh_ritz
+//   final_gemm            PodRun::rayleigh_ritz, found > 64: V <- Rt V by GEMM
+//   complete_fused / complete_general   PodRun::complete: rest <= 32 && found <= 512 / else rom_complete_orthonormal
+//   n_full, m_gt_dim, row_offsets   the argument checks and row offsets below; spans_range: a sketch of the full range is exact
+extern "C" int rom_pod_ex(rom_ctx* ctx, rom_buf* Xb, int64_t x_row0, int M, int64_t dim, int n, int center, double rel_floor,
+                          rom_buf* Vb, int64_t v_row0, double* sigma_host, double* info_host) {
+  ROM_CHECK(ctx && Xb && Vb && (sigma_host || n == 0), "rom_pod: null argument");
+  const double floor_rel = rel_floor > NOISE_FLOOR ? rel_floor : NOISE_FLOOR;
+  ROM_CHECK(M >= 1 && dim >= 1 && n >= 0 && x_row0 >= 0 && v_row0 >= 0, "rom_pod: bad sizes");
+  ROM_CHECK(n <= std::min<int64_t>(M, dim), "rom_pod: %d modes requested from a %d x %lld block", n, M, (long long)dim);
+  ROM_CHECK(n + 12 <= SE_MAX, "rom_pod: at most %d modes", SE_MAX - 12);
+  ROM_CHECK(size_t(x_row0 + M) * dim <= Xb->n && size_t(v_row0 + n) * dim <= Vb->n, "rom_pod: buffers too small");
+  // (worth_ahead: blocks from 64 MB -- below, the product is shorter than the stream hand-over.  dim >= 1024, M >= 128: the
+  // product then takes the thin LDS-DMA kernel; where it splits K instead, sketch_ahead_start gives it a partial buffer)
+  PodRun run{ctx, Vb, v_row0, Xb->p + x_row0 * dim, Vb->p + v_row0 * dim, M, dim, n, center, floor_rel,
+             center && n > 0 && std::min<int64_t>(M, dim) >= 2,
+             size_t(M) * dim * sizeof(double) >= (size_t(64) << 20) && dim >= 1024 && M >= 128};
+  ROM_TRY(run.centre());
+  for (int i = 0; i < n; ++i) sigma_host[i] = 0.0;
+  ROM_TRY(run.Bt.get(ctx, size_t(std::max(n, 1)) * M));
+  // the sketch passes run until the request is filled or the spectrum has reached the floor; the budget only guards
+  // against a pass that makes no progress (every pass accepts at least one mode or ends the loop)
+  for (int p = 1; p < n + 2 && run.found < n; ++p) {
+    PodPass ps(p, n - run.found, std::min<int64_t>(M, dim));
+    ROM_TRY(run.first_product(ps));
+    ROM_TRY(run.sketch_pass(ps));
+    int take = -1;   // (the pilot abandoned the pass: a slowly decaying spectrum)
+    if (!ps.ss.empty()) {
+      run.info.sketch_passes += 1;
+      ROM_TRY(run.diagnose_empty_first_pass(ps));
+      take = run.take_count(ps);
+    }
+    if (take < 0) {
+      ROM_TRY(run.gram_route());
+      if (run.found == 0) break;   // (a zero block)
+      continue;
+    }
+    if (take == 0) break;
+    ROM_TRY(run.accept(ps, take));
+    if (run.at_floor_stop) break;   // the spectrum has reached the floor: nothing left to find
+  }
+  bool unused = false;
+  ROM_TRY(sketch_ahead_take(ctx, run.ahead, -1, -1, unused));   // (a product started for a pass that did not happen)
+  ROM_TRY(run.rayleigh_ritz(sigma_host));
+  ROM_TRY(run.complete());
+  if (n > 0) ROM_TRY(rom_launch_rows_sign_flip(ctx, run.V, n, dim));  // svd_flip(u_based_decision=False)
   ROM_HIP(hipStreamSynchronize(ctx->stream));
-  if (info_host) {
-    info_host[0] = info.resolved;
-    info_host[1] = info.completed;
-    info_host[2] = info.gram_passes;
-    info_host[3] = info.sketch_passes;
-    info_host[4] = info.executed;
-    info_host[5] = 8.0 * n * M * double(dim);   // the four thin products of a pass for the n requested modes alone (no oversampling)
-    info_host[6] = info.eig_iterations;
-    // why the call stopped short of n modes: 0 request filled, 1 the spectrum reached the floor (the completed modes are
-    // not determined by the data), 2 no accepted mode in a pass / pass budget (modes above the floor may be missing)
-    info_host[7] = found >= n ? (info.unconverged ? 2.0 : 0.0) : (at_floor_stop || sigma_1 == 0.0 ? 1.0 : 2.0);
-  }
+  run.write_info(info_host);
   return ROM_OK;
 }
 

@@ -26,7 +26,8 @@ def routes_of(case, info, prof):
     names = {nm: rec for nm, rec in prof.items() if rec["launches"] > 0}
     gp, sp = info["gram_passes"], info["sketch_passes"]
     nn_block = nt_iter = 0
-    pass_gemm = final_gemm = False
+    pass_gemm = final_gemm = small_take = correction_gemm = False
+    shapes = {(m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))) for m in map(GEMM.match, names) if m}
     for nm, rec in names.items():
         m = GEMM.match(nm)
         if not m:
@@ -38,6 +39,14 @@ def routes_of(case, info, prof):
             pass_gemm = True                       # the accepted rows of a pass with b > 64 rows, take > 64
         if op == "gemm_nn" and b == dim and a > 64 and k == a:
             final_gemm = True                      # the final rotation of found > 64 modes
+        # <= 64 rows out of an inner size > 64 that is not the block's M, in dim space AND in M space (the completion's
+        # products have no partner in M space): up to 512 the inner size is a pass's b (at most SE_MAX / 4 + 8) and the
+        # product its accepted rows Rt Q, Rt Traw; above, it is `found` and the product a pass's correction Cc V, Cc Bt
+        if op == "gemm_nn" and b == dim and a <= 64 < k and k != M and dim != M and ("gemm_nn", a, M, k) in shapes:
+            if k <= 512:
+                small_take = True
+            else:
+                correction_gemm = True
         if op == "gemm_nt" and b == M and k == M and dim != M:
             nt_iter += rec["launches"]             # Y G: a subspace-iteration step on the Gram matrix
     out = set()
@@ -50,6 +59,10 @@ def routes_of(case, info, prof):
         out.add("combine_rows")
     if pass_gemm:
         out.add("pass_gemm")
+    if small_take:
+        out.add("pass_gemm_small_take")
+    if correction_gemm:
+        out.add("correction_gemm")
     if final_gemm:
         out.add("final_gemm")
     # the final Rayleigh-Ritz step of `found` rows off the one-workgroup kernel: three rounds of GEMM + small_eig on the
@@ -92,9 +105,13 @@ def routes_of(case, info, prof):
     cr = names.get("center_rows")
     if cr:
         out.add("centre_sketch" if cr["flops"] == 1.0 * M * dim * cr["launches"] else "centre_explicit")
-    if 1 <= info["completed_modes"] <= 32:
+    rest = info["completed_modes"]
+    if 1 <= rest <= 32 and found <= 512:
         out.add("complete_fused")
-    if info["completed_modes"] > 32:
+    if rest > 32:
+        out.add("complete_general")
+    # (found > 512 rules the fused completion out whatever `rest`: rom_complete_orthonormal's own correction, rest x dim x found)
+    if 1 <= rest <= 32 and found > 512 and ("gemm_nn", rest, dim, found) in shapes:
         out.add("complete_general")
     return out, nn_block, nt_iter, piv
 

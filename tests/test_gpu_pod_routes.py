@@ -42,6 +42,8 @@ ROUTES = {
     "multi_pass": "several sketch passes; the implicit deflation and the accepted rows through combine_rows",
     "combine_rows": "kp_combine_rows_mma (row blocks <= 64)",
     "pass_gemm": "a pass with b > 64 rows accepting take > 64 modes: the accepted rows through GEMM",
+    "pass_gemm_small_take": "a pass with b > 64 rows accepting take <= 64 modes: the accepted rows through GEMM all the same",
+    "correction_gemm": "a pass with found > 512: its rank-found corrections through GEMM although b <= 64",
     "final_gemm": "the final Rayleigh-Ritz step with found > 64: the rotation through GEMM",
     "tall_svd_unfused": "the final tall SVD on the parallel path (found > 32 or M > 4096): no kp_tall_svd for it",
     "gram": "the Gram route after a complete first pass (the cost model prefers it)",
@@ -60,8 +62,8 @@ ROUTES = {
     "cliff": "a cliff of more than eight orders with modes below it, found by the next pass",
     "centre_sketch": "the column mean from the first pass's first product",
     "centre_explicit": "explicit centring (n = 0, M = 1 or dim = 1)",
-    "complete_fused": "completion on the fused row kernels (rest <= 32)",
-    "complete_general": "completion by rom_complete_orthonormal (rest > 32)",
+    "complete_fused": "completion on the fused row kernels (rest <= 32 and found <= 512)",
+    "complete_general": "completion by rom_complete_orthonormal (rest > 32 or found > 512)",
     "zero_block": "a block of zeros",
     "n_full": "n = min(M, dim)",
     "m_gt_dim": "M > dim",
@@ -146,6 +148,23 @@ CASES = [
           routes={"cliff", "multi_pass", "floor", "complete_fused"}, info=dict(gram_passes=0)),
     _case("n_full_m_gt_dim", 256, 64, 64, _geo(63, 0, 5), 64, routes={"n_full", "m_gt_dim", "floor"}),
     _case("ahead", 1024, 4096, 8192, _geo(24, 0, 11.5), 30, routes={"ahead_hit", "multi_pass", "floor"}, info=dict(gram_passes=0)),
+    # n = 240: the first pass asks for want = n / 4 = 60 modes with b = 68 > 64 rows and accepts the block's 40 (the other
+    # 28 rows are rounding noise: all 40 converged), take = 40 <= 64 < b: Rt Q and Rt Traw through GEMM, 40 x dim x 68 and
+    # 40 x M x 68 -- no other product of the call has 68 as its inner size and 40 rows.  The second pass (58 rows) finds
+    # the floor; 200 rows are completed
+    _case("pass_gemm_small_take", 256, 256, 320, _geo(40, 0, 4), 240,
+          routes={"pass_gemm_small_take", "combine_rows", "complete_general", "floor"}, info=dict(gram_passes=0)),
+    # found > 512 in front of a pass.  No sequence of passes gets there within M, dim <= 1024 (a first pass with unconverged
+    # modes hands over to the Gram route at these sizes, and converged passes cost 4.6 decades each), so the Gram route
+    # delivers them: 516 values over three decades (all above GRAM_ACCEPT; the request is most of the Gram matrix: it is
+    # diagonalised whole), then 16 values at 1e-8 .. 1e-9 for the pass behind it: 24 modes left, 32 rows, found = 516 --
+    # its corrections are 32 x dim x 516 and 32 x M x 516 GEMMs.  It stops at the floor with found = 532; the 8 rows left
+    # are completed by rom_complete_orthonormal (8 x dim x 532: found > 512 rules the fused kernels out).  Coherent: the
+    # child tells the Gram iteration's products from the sketch's by dim != M, and Hadamard left vectors with r >= 532 and
+    # M, dim <= 1024 would need M = dim = 1024
+    _case("correction_gemm", 640, 1024, 1024, np.concatenate([np.geomspace(1.0, 1e-3, 516), np.geomspace(1e-8, 1e-9, 16)]), 540,
+          routes={"correction_gemm", "gram", "final_gemm", "complete_general", "floor"},
+          eig={"full_eig_size"}, info=dict(gram_passes=1), coherent=True),
 ]
 COVERED = set()     # routes reached by cases whose truth checks passed
 
