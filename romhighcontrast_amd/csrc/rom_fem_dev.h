@@ -1,7 +1,8 @@
 // Device-side view of a rom_fem, shared constants and the kernels of the sweep (gfx950 only).
-// rom_fem_kernels.hip defines the kernels, rom_fem_setup.hip builds the tables (rom_fem_create),
-// rom_fem_solve.hip enqueues them (rom_solve_batch and friends).
+// rom_fem_kernels.hip defines the kernels, rom_fem_plan.hip builds the tables on the host, rom_fem_setup.hip uploads them
+// (rom_fem_create), rom_fem_solve.hip enqueues the kernels (rom_solve_batch and friends).
 #pragma once
+#include "rom_fem_plan.h"  // constants shared with the host planner, h0_row
 #include "rom_mma.h"
 
 // ============================================================================================
@@ -80,29 +81,11 @@ struct FemDev {
 
 FemDev make_dev(const rom_fem* f);
 
-constexpr int COEF_MAX = 64;   // term weights cached in LDS per pass
-#ifndef PAIR_RING_
-#define PAIR_RING_ 8
-#endif
-constexpr int PAIR_RING = PAIR_RING_;  // (term, block) pairs in flight in the single-tile assembly
 // k_solve1's dynamic LDS: the term weights of its four systems, four per-wave areas
 constexpr int S1_COEF_BYTES = 4 * COEF_MAX * 8, S1_WAVE_BYTES = (40 * 64 + 64 * 4 + 64 + 64 + 3 * 64 * 4) * 8;
 constexpr int S1_ITEM_PASSES = 4;  // coefficient items (64 per pass) whose descriptors k_solve1 reads ahead of its Cholesky
 constexpr int S1_DENSE_BYTES = 64 * 64 * 8;  // the matrix of the dense product of the tail (64 x ndi, ndi <= 64)
 constexpr int S1_LDS_BYTES = S1_COEF_BYTES + 4 * S1_WAVE_BYTES + S1_DENSE_BYTES;
-constexpr int DENSE_GROUPS_MAX = 8;  // closed-form edges whose coefficient blocks k_solve1 builds
-
-// row of H0 that holds the extension from side s evaluated at interior vertex (i,j), 1-based
-__host__ __device__ inline int h0_row(int s, int i, int j, int N, int n1) {
-  int ii, jj;
-  switch (s) {
-    case 0: ii = i; jj = j; break;
-    case 1: ii = N - i; jj = j; break;
-    case 2: ii = j; jj = i; break;
-    default: ii = N - j; jj = i; break;
-  }
-  return (ii - 1) * n1 + (jj - 1);
-}
 
 // ---- kernels (rom_fem_kernels.hip) ----------------------------------------------------------------
 __global__ void k_repack_table(const double* __restrict__ G, int ld, int nseg, int n1, int orient, double* __restrict__ Gs);
@@ -123,7 +106,6 @@ __global__ void k_extend(FemDev f, const double* __restrict__ a, int Mc, double*
 // Descriptors of up to X128_BLOCKS blocks for one k_extend128 launch, passed BY VALUE: kernel arguments are read
 // with scalar loads in one batch, whereas f.lr_blocks[z] -> f.sides[b] -> fields compiled into a chain of 14
 // dependent vector loads (each with its own s_waitcnt vmcnt(0)) at the head of every workgroup.
-constexpr int X128_BLOCKS = 16;
 struct X128Args {
   int blocks[X128_BLOCKS];
   BlockSide sides[X128_BLOCKS];
@@ -207,6 +189,5 @@ __device__ inline double lane_swap1(double v) {
 // two doubles at an address that is only 8-byte aligned (snapshot rows have odd length)
 typedef double double2_u __attribute__((ext_vector_type(2), aligned(8)));
 
-constexpr int EXT_ZERO_PAGE = 256;  // doubles of zeros behind FemDev::W (target of the lanes of k_extend128 that have nothing to load)
 __global__ void k_scatter_interface(FemDev f, int Mc, double* __restrict__ U, long long row0);
 __global__ void k_assemble_stencil(FemDev f, const double* __restrict__ a, int M, double* __restrict__ diag, double* __restrict__ east, double* __restrict__ north);

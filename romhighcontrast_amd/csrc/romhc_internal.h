@@ -233,7 +233,8 @@ struct rom_fem {
   int ncross, xb0;  // cross points and the position of their block in the interface vectors
   int T;       // tiles per dimension
   int nslots;  // nonzero lower tiles
-  // device tables
+  // device tables: every allocation of rom_fem_create is recorded in `tables`, which is what rom_fem_destroy frees
+  std::vector<void*> tables;
   double* d_G = nullptr;     // extension tables of the compressed edges
   double* d_Gs = nullptr;    // the same tables, segment-major and with the vertices of a mesh row adjacent (k_extend128)
   double* d_A0 = nullptr;    // (n1*n1) x n1p : Q[j,mode] rho_mode(i) (harmonic extension from side i=0, sine basis)
@@ -256,7 +257,7 @@ struct rom_fem {
   double* d_pool_acc = nullptr;  // k_solve1: the pairs' table pieces in accumulator layout, in the order its four waves walk them
   int* d_wmeta = nullptr;        // ... and their metas; wave w walks wp0[w] .. wp0[w + 1] - 1 (rom_fem_dev.h)
   int wp0[5] = {};
-  int* d_s1_items = nullptr;   // k_solve1: flat records of the dense items (24 ints) and of the coefficient items (4 ints), rom_fem_setup.hip
+  int* d_s1_items = nullptr;   // k_solve1: flat records of the dense items (24 ints) and of the coefficient items (4 ints), rom_fem_plan.hip
   int* d_s1_citems = nullptr;
   int* d_kptr = nullptr;     // nslots+1
   int* d_kpair = nullptr;    // 2*entries (slotA, slotB)
