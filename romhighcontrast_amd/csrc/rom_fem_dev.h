@@ -89,6 +89,8 @@ constexpr int S1_LDS_BYTES = S1_COEF_BYTES + 4 * S1_WAVE_BYTES + S1_DENSE_BYTES;
 
 // ---- kernels (rom_fem_kernels.hip) ----------------------------------------------------------------
 __global__ void k_repack_table(const double* __restrict__ G, int ld, int nseg, int n1, int orient, double* __restrict__ Gs);
+struct ExtThresholds { unsigned short thr[8]; };  // ExtSide::thr of one table, by value
+__global__ void k_mask_table(double* __restrict__ G, int ld, int n1, ExtThresholds th);
 __global__ void k_build_A0(double* A0, const double* Qp, const double* rho, int n1, int n1p, int N);
 __global__ void k_rhs(FemDev f, const double* __restrict__ a);
 __global__ void k_coef(FemDev f, const double* __restrict__ a);

@@ -60,6 +60,18 @@ __global__ void k_repack_table(const double* __restrict__ G, int ld, int nseg, i
   Gs[idx] = k < ld ? G[row * ld + k] : 0.0;
 }
 
+// Exact zeros for the entries of an extension table that the planner declares droppable (rom_fem_plan.hip, ext_truncation):
+// in a row at distance d from the side, the columns of the first (number of j with d >= thr[j]) K segments.  G and Gs then
+// hold the same zeros, so a kernel that walks them and one that skips them add up the same numbers.
+__global__ void k_mask_table(double* __restrict__ G, int ld, int n1, ExtThresholds th) {
+  const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (idx >= (long long)n1 * n1 * ld) return;
+  const int k = int(idx % ld), d = int(idx / ld / n1) + 1;
+  int skip = 0;
+  for (int j = 0; j < EXT_THRESHOLDS; ++j) skip += d >= int(th.thr[j]) ? 1 : 0;
+  if (k < 8 * skip) G[idx] = 0.0;
+}
+
 
 __device__ inline double readlane_f64(double v, int lane) {
   int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
@@ -1782,6 +1794,15 @@ __global__ __launch_bounds__(256) void k_extend(FemDev f, const double* __restri
 // reads conflict free.  Rows that do not exist (systems >= Mc, vertices behind the end of the mesh row / the block) are
 // clamped to the last one that does: their products are not stored.
 constexpr int X128_SLOT = 4 * 128 * 64;  // bytes
+static_assert(sizeof(FemDev) + sizeof(X128Args) + 64 <= 4096, "k_extend128's arguments must fit the kernel argument segment");
+
+// leading 8-wide K segments of a compressed side that are zero at distance d from it (ExtSide::thr, ascending)
+__device__ inline int x128_skip(const ExtSide& s, int d) {
+  int n = 0;
+#pragma unroll
+  for (int j = 0; j < EXT_THRESHOLDS; ++j) n += d >= int(s.thr[j]) ? 1 : 0;
+  return n;
+}
 
 // FLAT: the 128 vertices of a tile are consecutive in the block's row-major vertex numbering instead of lying in
 // one mesh row -- no padding when n1 is not close to a multiple of 128 (n1 = 170: 226 tiles per block instead of
@@ -1867,10 +1888,35 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   // ceil((rank + 1) / 8) segments of a side hold anything -- the second half of a side's last chunk is handed to the
   // next side (7-17 % fewer MFMAs where rank + 1 is just above a multiple of 16; products with the zero padding add
   // nothing, so the sums do not change).  A chunk = two consecutive segments of that walk.
-  const int cnt0 = sd.s[0].mode == 2 ? min(2 * sd.s[0].nch, (sd.s[0].r + 1 + 7) / 8) : 0;
-  const int cnt1 = sd.s[1].mode == 2 ? min(2 * sd.s[1].nch, (sd.s[1].r + 1 + 7) / 8) : 0;
-  const int cnt2 = sd.s[2].mode == 2 ? min(2 * sd.s[2].nch, (sd.s[2].r + 1 + 7) / 8) : 0;
-  const int cnt3 = sd.s[3].mode == 2 ? min(2 * sd.s[3].nch, (sd.s[3].r + 1 + 7) / 8) : 0;
+  // The directions of a side are ordered so that the ones that die fastest with the distance from the side come first
+  // (rom_fem_plan.hip, rotate_to_echelon): at the tile's distance the first sk segments of the side's table are exact
+  // zeros (k_mask_table) and the walk starts behind them.  The distance of a tile = that of its nearest vertex; a tile
+  // that walks more than it needs adds zeros, so every tiling gives the same bits.  Scalar code (the thresholds are
+  // kernel arguments).
+  int dist0, dist1, dist2, dist3;
+  if (FLAT) {
+    const int vend = min(vt0 + 127, nvert - 1), i_lo = vt0 / n1, i_hi = vend / n1;  // 0-based mesh rows of the tile
+    const bool one_row = i_lo == i_hi;  // (else the tile meets both ends of a mesh row)
+    dist0 = i_lo + 1;
+    dist1 = N - (i_hi + 1);
+    dist2 = one_row ? vt0 - i_lo * n1 + 1 : 1;
+    dist3 = one_row ? N - (vend - i_hi * n1 + 1) : 1;
+  } else {
+    dist0 = iv;
+    dist1 = N - iv;
+    dist2 = jv0;
+    dist3 = N - min(jv0 + 127, n1);
+  }
+#define X_SEGS(S_) min(2 * sd.s[S_].nch, (sd.s[S_].r + 1 + 7) / 8)
+  const int sk0 = sd.s[0].mode == 2 ? min(x128_skip(sd.s[0], dist0), X_SEGS(0) - 1) : 0;
+  const int sk1 = sd.s[1].mode == 2 ? min(x128_skip(sd.s[1], dist1), X_SEGS(1) - 1) : 0;
+  const int sk2 = sd.s[2].mode == 2 ? min(x128_skip(sd.s[2], dist2), X_SEGS(2) - 1) : 0;
+  const int sk3 = sd.s[3].mode == 2 ? min(x128_skip(sd.s[3], dist3), X_SEGS(3) - 1) : 0;
+  const int cnt0 = sd.s[0].mode == 2 ? X_SEGS(0) - sk0 : 0;
+  const int cnt1 = sd.s[1].mode == 2 ? X_SEGS(1) - sk1 : 0;
+  const int cnt2 = sd.s[2].mode == 2 ? X_SEGS(2) - sk2 : 0;
+  const int cnt3 = sd.s[3].mode == 2 ? X_SEGS(3) - sk3 : 0;
+#undef X_SEGS
   const int nseg = cnt0 + cnt1 + cnt2 + cnt3;
   const int tot = (nseg + 1) / 2;
   // ---- fragment addressing: lane (fr, kq) reads row fr (+ 16 i) at k = 4 kki + kq: half kki >> 1, unit
@@ -1929,8 +1975,9 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
     /* side 0: n1 (i - 1) + (j - 1); 1: n1 (n1 - i) + (j - 1); 2: n1 (i - 1) + (j - 1); 3: n1 (i - 1) + (n1 - j)  */     \
     const int ci_ = c_side == 1 ? -n1 : n1, cj_ = c_side == 3 ? -1 : 1;                                             \
     const int k0_ = c_side == 1 ? n1 * n1 - 1 : c_side == 3 ? -n1 + n1 : -n1 - 1;                                   \
-    pA = ybase + size_t(off_) * 8;                                                                                 \
-    pB = gsbase + size_t(gseg_) * 8;                                                                               \
+    const int sk_ = c_side == 0 ? sk0 : c_side == 1 ? sk1 : c_side == 2 ? sk2 : sk3; /* segments skipped */        \
+    pA = ybase + size_t(off_) * 8 + size_t(sk_) * 64;                                                              \
+    pB = gsbase + size_t(gseg_) * 8 + size_t(sk_) * seg_stride;                                                    \
     voB[0] = unsigned(ci_ * vi[0] + cj_ * vj[0] + k0_) * 64u + du16;                                               \
     voB[1] = unsigned(ci_ * vi[1] + cj_ * vj[1] + k0_) * 64u + du16;                                               \
   } while (0)

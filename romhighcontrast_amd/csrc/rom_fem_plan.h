@@ -15,6 +15,8 @@ constexpr int COEF_MAX = 64;   // term weights cached in LDS per pass
 constexpr int PAIR_RING = PAIR_RING_;  // (term, block) pairs in flight in the single-tile assembly
 constexpr int DENSE_GROUPS_MAX = 8;    // closed-form edges whose coefficient blocks k_solve1 builds
 constexpr int EXT_ZERO_PAGE = 256;  // doubles of zeros behind FemDev::W (target of the lanes of k_extend128 that have nothing to load)
+constexpr int EXT_THRESHOLDS = 7;   // distance thresholds of a compressed side (ExtSide::thr): K segments k_extend128 can skip
+constexpr long double EXT_TRUNC_CUT = 1e-18L;  // a table column is dropped where its bound is below this share of the largest
 constexpr int X128_BLOCKS = 16;     // blocks whose descriptors one k_extend128 launch takes by value (X128Args, rom_fem_dev.h)
 
 // row of H0 that holds the extension from side s evaluated at interior vertex (i,j), 1-based
@@ -30,10 +32,11 @@ __host__ __device__ inline int h0_row(int s, int i, int j, int N, int n1) {
 }
 
 // what rom_fem_create reads from the environment for the planner (ROMHC_NO_PREELIM, ROMHC_NO_COMPRESS,
-// ROMHC_NO_LOWRANK_EXT, ROMHC_NO_EXT_LR, ROMHC_VERBOSE, ROMHC_COMPRESS_TOL)
+// ROMHC_NO_LOWRANK_EXT, ROMHC_NO_EXT_LR, ROMHC_VERBOSE, ROMHC_COMPRESS_TOL, ROMHC_NO_EXT_TRUNC)
 struct FemSwitches {
   bool no_preelim, no_compress, no_lowrank_ext, no_ext_lr, verbose;
   long double compress_tol;
+  bool no_ext_trunc;  // keep the pivoted basis of the reduced unknowns and walk every K segment of the extension everywhere
 };
 
 struct FemPlan {
@@ -55,7 +58,17 @@ struct FemPlan {
   std::vector<CoefGroup> groups;
   std::vector<BlockSide> sides;
   // inputs of the device-side builds: G + off = A0 * Bh^T (rows x rp), Gs + gsoff = k_repack_table(G + goff); A0 from Qp, rho
-  struct GemmG { std::vector<double> Bh; long long off; int rp; };
+  // Rotated basis (entry non-empty): Bh[k] is zero in front of mode entry[k]; rows at distance d from the side need only
+  // the K segments from seg0[d] on (thr: the same as thresholds, ExtSide::thr) -- the others hold columns bounded by `cut`
+  // and are zeroed in G (k_mask_table)
+  struct GemmG {
+    std::vector<double> Bh; long long off; int rp;
+    int r = 0;
+    std::vector<int> entry, seg0;
+    std::vector<long double> W;  // the rotated basis itself (n1 x r; host copy for the checks, not uploaded)
+    unsigned short thr[8] = {0xffff, 0xffff, 0xffff, 0xffff, 0xffff, 0xffff, 0xffff, 0xffff};
+    double cut = 0;
+  };
   struct Repack { long long goff, gsoff; int ld, nseg, orient; };
   std::vector<GemmG> gemm_G;
   std::vector<Repack> repacks;

@@ -45,6 +45,7 @@ struct Comp {
   std::vector<ld> p0;  // n1       (K^-1 - P W^T K^-1) g_f
   Mat KiW;             // n1 x r   K^-1 W          (closed-form edges: u_e = (KiW c_e + wK) / s_e)
   std::vector<ld> wK;  // n1       K^-1 g_f
+  std::vector<int> entry;  // r    rotated basis (rotate_to_echelon): first sine mode of the direction's extension-table column
 };
 
 // run fn(0) ... fn(n-1) on up to hardware_concurrency host threads (the long-double table products are
@@ -228,6 +229,25 @@ bool compress_finish(const UnitBlock& ub, const Mat& Wfull, int r, int hv, bool 
   return true;
 }
 
+// The basis of the reduced unknowns is ours to choose: any W E with E orthogonal spans the same space and gives the same
+// solution.  Choose E so that the sine coefficients of the type's extension table, (P E)^T Q (variant 0, active edges) or
+// (K^-1 W E)^T Q (variant 1, closed-form edges), are in row-echelon form in mode order: direction k then carries only modes
+// >= entry[k] and dies with the distance from the side like rho_entry[k](d) -- far from the side the kernel can skip it,
+// by the criterion kmax applies to the sine modes.  The directions are stored in DESCENDING entry mode: the ones that can
+// be dropped come first, a tile starts its walk at a later K segment and 1/s stays last.
+bool rotate_to_echelon(const UnitBlock& ub, int hv, int variant, Comp& cp) {
+  const int n1 = ub.n1, r = cp.r;
+  std::vector<int> entry;
+  const Mat E = hostla::echelon_rotation(hostla::mul_tn(variant == 0 ? cp.P : cp.KiW, ub.Q), &entry);
+  const Mat WE = hostla::mul(cp.W, E);
+  Mat Wr(n1, r);
+  for (int i = 0; i < n1; ++i)
+    for (int k = 0; k < r; ++k) Wr(i, k) = WE(i, r - 1 - k);
+  if (!compress_finish(ub, Wr, r, hv, true, cp)) return false;
+  cp.entry.assign(entry.rbegin(), entry.rend());
+  return true;
+}
+
 struct TermAcc {
   std::array<int, 5> key;
   std::vector<double> tab;
@@ -400,10 +420,12 @@ struct Compression {
   std::vector<Comp> comps;
   std::vector<int> kmax, rp;           // kmax[d]: see extension_ranks; rp: padded width of a type's [z, 1/s] block
   std::vector<char> use_lr;            // the type enters the extension through its reduced unknowns
+  std::vector<char> variant;           // rotated bases: 0 the type of active edges, 1 of closed-form edges (two records where
+                                       // the same surroundings serve both: the two extension tables need different rotations)
   double kavg = 0;
 };
 
-void edge_types(const Topology& t, Compression& c) {
+void edge_types(const Topology& t, const Elimination& el, bool by_variant, Compression& c) {
   std::map<std::vector<int>, int> sig_id;
   c.comp_of.assign(t.E, -1);
   for (int e = 0; e < t.E; ++e) {
@@ -417,11 +439,13 @@ void edge_types(const Topology& t, Compression& c) {
     bool x0 = false, x1 = false;
     for (auto& x : t.xc)
       if (x.edge == e) (x.node == 0 ? x0 : x1) = true;
-    sig.push_back(100 + (x0 ? 1 : 0) + (x1 ? 2 : 0));
+    const int variant = by_variant && el.is_pre[e] ? 1 : 0;
+    sig.push_back(100 + (x0 ? 1 : 0) + (x1 ? 2 : 0) + 4 * variant);
     auto it = sig_id.find(sig);
     if (it == sig_id.end()) {
       it = sig_id.emplace(sig, int(c.sigs.size())).first;
       c.sigs.push_back(sig);
+      c.variant.push_back(char(variant));
     }
     c.comp_of[e] = it->second;
   }
@@ -477,7 +501,10 @@ bool compress_edges(UnitBlock& ub, const Topology& t, const Elimination& el, con
     };
     r_use = tiles(r_fill) <= tiles(r_drop) ? r_fill : r_drop;
   }
-  parallel_for(ntype, [&](size_t k) { ok[k] = compress_finish(ub, Wfull[k], r_use[k], c.sigs[k][0], compress, c.comps[k]); });
+  parallel_for(ntype, [&](size_t k) {
+    ok[k] = compress_finish(ub, Wfull[k], r_use[k], c.sigs[k][0], compress, c.comps[k]);
+    if (ok[k] && compress && !sw.no_ext_trunc && c.comps[k].r < n1) ok[k] = rotate_to_echelon(ub, c.sigs[k][0], c.variant[k], c.comps[k]);
+  });
   return std::find(ok.begin(), ok.end(), 0) == ok.end();
 }
 
@@ -1156,6 +1183,38 @@ void unit_block_tables(UnitBlock& ub, const BtTables& bt, FemPlan& p) {
 // = A0 (Q [P_c, p0_c]), one (n1*n1) x rp_c table per (compressed-edge type, variant) that a block side actually uses.
 // Here: the sine coefficients Q^T [P_c, p0_c] of every table: long-double products, one host thread per table.
 using GOffsets = std::map<std::pair<int, int>, long long>;  // (type, variant) -> offset in G
+
+// Rotated basis: the stored coefficients below the echelon are exact zeros (in long double they are rounding residue of about
+// 1e-18 of the table, far below what fp64 keeps -- but multiplied by rho ~ 1 of the low modes they would defeat the bound).
+// Column k of the table at distance d from the side is bounded by sqrt(2/N) b(k, d), b(k, d) = sum_m rho_m(d) |Bh[k][m]|;
+// a column is needed at d while b(k, d) reaches 1e-18 of the largest b(k, 1) -- the cut kmax applies to rho itself.
+// seg0[d]: the first 8-wide segment that holds a needed column (b falls with d, so seg0 rises); the last segment, with
+// 1/s, is always walked.  thr[j] = the first distance with seg0 > j.
+void ext_truncation(const UnitBlock& ub, const Comp& cp, int n1p, FemPlan::GemmG& g) {
+  const int n1 = ub.n1, N = ub.N, r = cp.r, nseg = segs8(r);
+  g.entry = cp.entry;
+  g.W = cp.W.v;
+  for (int k = 0; k < r; ++k)
+    for (int m = 0; m < std::min(cp.entry[k], n1); ++m) g.Bh[size_t(k) * n1p + m] = 0.0;
+  auto bound = [&](int k, int d) {
+    ld b = 0;
+    for (int m = 0; m < n1; ++m) b += ub.rho(m, d) * fabsl(ld(g.Bh[size_t(k) * n1p + m]));
+    return b;
+  };
+  ld top = 0;
+  for (int k = 0; k < r; ++k) top = std::max(top, bound(k, 1));
+  const ld cut = EXT_TRUNC_CUT * top;
+  g.cut = double(cut);
+  for (int d = 1; d <= n1; ++d) {
+    int first = 0;
+    while (first < r && bound(first, d) < cut) ++first;
+    g.seg0[d] = std::min({first / 8, nseg - 1, EXT_THRESHOLDS});
+  }
+  g.seg0[N] = g.seg0[n1];
+  for (int j = 0; j < EXT_THRESHOLDS; ++j)
+    for (int d = n1; d >= 1; --d)
+      if (g.seg0[d] > j) g.thr[j] = (unsigned short)d;
+}
 GOffsets g_tables(const UnitBlock& ub, const Topology& t, const Elimination& el, const Compression& c, const Layout& L, FemPlan& p) {
   const int n1 = t.n1, n1p = p.n1p;
   GOffsets goff;
@@ -1181,6 +1240,9 @@ GOffsets g_tables(const UnitBlock& ub, const Topology& t, const Elimination& el,
       for (int k = 0; k < n1; ++k) sacc += pv[k] * ub.Q(k, m);
       Bh[size_t(cp.r) * n1p + m] = double(sacc);
     }
+    p.gemm_G[gi].r = cp.r;
+    p.gemm_G[gi].seg0.assign(t.N + 1, 0);
+    if (!cp.entry.empty()) ext_truncation(ub, cp, n1p, p.gemm_G[gi]);
   });
   return goff;
 }
@@ -1203,7 +1265,7 @@ void extension_sides(const Topology& t, const Elimination& el, const Compression
       if (e < 0) continue;
       const int k = c.comp_of[e], r = c.comps[k].r;
       if (L.cpos[e] >= 0) {
-        es = ExtSide{2, L.cpos[e], c.rp[k] / BK, r, int(goff.at({k, int(el.is_pre[e])})), 0, t.edges[e].b0, t.edges[e].b1};
+        es = ExtSide{2, L.cpos[e], c.rp[k] / BK, r, int(goff.at({k, int(el.is_pre[e])})), 0, t.edges[e].b0, t.edges[e].b1, {}};
         // segment-major copy for k_extend128: rows ordered for this side's orientation (one per table and orientation)
         const auto key = std::make_tuple(k, int(el.is_pre[e]), sdx >= 2 ? 1 : 0);
         if (!gsoff.count(key)) {
@@ -1211,7 +1273,15 @@ void extension_sides(const Topology& t, const Elimination& el, const Compression
           p.gstotal += (long long)segs8(r) * hrows * 8;
         }
         es.gseg = int(gsoff[key]);
-        fl += 2.0 * double(n1) * n1 * (r + 1);
+        const FemPlan::GemmG* gg = nullptr;
+        for (const FemPlan::GemmG& cand : p.gemm_G)
+          if (cand.off == es.gtab) gg = &cand;
+        memcpy(es.thr, gg->thr, sizeof(es.thr));
+        if (gg->entry.empty()) {
+          fl += 2.0 * double(n1) * n1 * (r + 1);
+        } else {  // the products the rows at distance d need: the columns from the first needed segment on
+          for (int d = 1; d <= n1; ++d) fl += 2.0 * double(n1) * (r + 1 - 8 * gg->seg0[d]);
+        }
       } else {
         es.mode = 1;
         es.off = L.npos[e];
@@ -1281,6 +1351,14 @@ void report(const FemPlan& p, const Compression& c) {
   for (size_t k = 0; k < c.comps.size(); ++k)
     fprintf(stderr, "romhc:   edge type %zu: rank %d (padded %d), %d edges, extension %s\n", k, c.comps[k].r, c.rp[k],
             int(std::count(c.comp_of.begin(), c.comp_of.end(), int(k))), c.use_lr[k] ? "from the reduced unknowns" : "sine modes");
+  for (size_t i = 0; i < p.gemm_G.size(); ++i) {  // K segments of k_extend128 per mesh row parallel to the side: needed against full
+    const FemPlan::GemmG& g = p.gemm_G[i];
+    const int full = segs8(g.r);
+    long long need = 0;
+    for (int d = 1; d <= p.n1; ++d) need += full - g.seg0[d];
+    fprintf(stderr, "romhc:   extension table %zu: rank %d, %s basis, K segments needed %lld of %lld (%.2f)\n", i, g.r,
+            g.entry.empty() ? "pivoted" : "echelon", need, (long long)full * p.n1, p.n1 > 0 ? double(need) / (double(full) * p.n1) : 1.0);
+  }
   fprintf(stderr, "romhc:   blocks extended by the 128-tile kernel: %d, general kernel: %d\n", int(p.lr_blocks.size()), int(p.gen_blocks.size()));
   // how sparse the term tables are: non-zero 16 x 16 blocks, bounding rectangles
   size_t nzb = 0, rect = 0, rows16 = 0;
@@ -1343,7 +1421,7 @@ int rom_fem_plan(int nrb, int ncb, int N, const FemSwitches& sw, FemPlan* out, s
   phase.next("unit-block tables in long double, compression of the edges");
   UnitBlock ub(N, t.E > 0);
   Compression c;
-  edge_types(t, c);
+  edge_types(t, el, !sw.no_ext_trunc && !sw.no_compress, c);
   if (!compress_edges(ub, t, el, sw, c)) return fail("internal: compressed edge block not positive definite");
   extension_ranks(ub, n1p, sw.no_lowrank_ext, c);
   p.kmax = c.kmax;

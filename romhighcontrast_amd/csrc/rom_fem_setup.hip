@@ -2,6 +2,7 @@
 // every parameter-independent table), uploads the tables and runs the three device-side builds (A0, G, Gs).
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 
 #include "rom_fem_dev.h"
@@ -98,6 +99,12 @@ int build_extension_tables(rom_fem* f, const FemPlan& p) {
     ROM_TRY(upload(ctx->stream, tmp.list, &d_B, g.Bh));
     ROM_TRY(rom_launch_gemm_nt(ctx, int64_t(hrows), g.rp, n1p, 1.0, f->d_A0, n1p, d_B, n1p, 0.0, f->d_G + g.off, g.rp,
                                "setup_gemm_G"));
+    if (!g.entry.empty() && hrows > 0) {  // the entries the distance thresholds declare droppable become exact zeros
+      ExtThresholds th;
+      memcpy(th.thr, g.thr, sizeof(th.thr));
+      k_mask_table<<<unsigned((hrows * g.rp + 255) / 256), 256, 0, ctx->stream>>>(f->d_G + g.off, g.rp, n1, th);
+      ROM_HIP(hipGetLastError());
+    }
     ROM_HIP(hipStreamSynchronize(ctx->stream));
   }
   ROM_TRY(dev_alloc(f->tables, &f->d_Gs, size_t(p.gstotal)));
@@ -141,6 +148,7 @@ extern "C" int rom_fem_create(rom_ctx* ctx, int nrb, int ncb, int N, rom_fem** o
   sw.verbose = getenv("ROMHC_VERBOSE") != nullptr;
   sw.compress_tol = 1e-14L;
   if (const char* s = getenv("ROMHC_COMPRESS_TOL")) sw.compress_tol = (long double)atof(s);
+  sw.no_ext_trunc = getenv("ROMHC_NO_EXT_TRUNC") != nullptr;
   FemPlan p;
   std::string why;
   if (rom_fem_plan(nrb, ncb, N, sw, &p, &why) != ROM_OK) {  // (nothing is allocated yet)

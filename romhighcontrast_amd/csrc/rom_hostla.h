@@ -3,6 +3,7 @@
 // rounded to fp64 when they are uploaded.
 #pragma once
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstddef>
 #include <thread>
@@ -219,6 +220,55 @@ inline Mat identity(int n) {
   Mat I(n, n);
   for (int i = 0; i < n; ++i) I(i, i) = 1.0L;
   return I;
+}
+
+// Orthogonal E (r x r) that brings C (r x n: row = direction, column = sine mode) to row-echelon form in mode order:
+// row k of E^T C is zero (to rounding) in front of column entry[k].  Householder reflections over the columns in their
+// order, no pivoting; a mode whose residual in the remaining rows is below rounding adds no direction.  A row that finds
+// no mode at all (C rank deficient) gets entry n.
+inline Mat echelon_rotation(const Mat& C, std::vector<int>* entry) {
+  const int r = C.r, n = C.c;
+  Mat A = C;
+  ld scale = 0;
+  for (ld x : A.v) scale += x * x;
+  scale = sqrtl(scale);
+  std::vector<std::vector<ld>> refl;  // reflection k acts on rows k .. r - 1 (H = I - 2 v v^T)
+  entry->assign(r, n);
+  int k = 0;
+  for (int m = 0; m < n && k < r; ++m) {
+    ld s = 0;
+    for (int i = k; i < r; ++i) s += A(i, m) * A(i, m);
+    s = sqrtl(s);
+    if (!(s > 1e3L * LDBL_EPSILON * scale)) continue;
+    std::vector<ld> v(r, 0.0L);
+    const ld alpha = A(k, m) > 0 ? -s : s;
+    ld vn = 0;
+    for (int i = k; i < r; ++i) {
+      v[i] = A(i, m) - (i == k ? alpha : 0.0L);
+      vn += v[i] * v[i];
+    }
+    vn = sqrtl(vn);
+    for (int i = k; i < r && vn > 0.0L; ++i) v[i] /= vn;
+    for (int j = m; j < n; ++j) {
+      ld d = 0;
+      for (int i = k; i < r; ++i) d += v[i] * A(i, j);
+      d *= 2;
+      for (int i = k; i < r; ++i) A(i, j) -= d * v[i];
+    }
+    refl.push_back(v);
+    (*entry)[k++] = m;
+  }
+  Mat E = identity(r);  // E = H_0 H_1 ... H_{K-1}
+  for (int q = int(refl.size()) - 1; q >= 0; --q) {
+    const std::vector<ld>& v = refl[q];
+    for (int j = 0; j < r; ++j) {
+      ld d = 0;
+      for (int i = q; i < r; ++i) d += v[i] * E(i, j);
+      d *= 2;
+      for (int i = q; i < r; ++i) E(i, j) -= d * v[i];
+    }
+  }
+  return E;
 }
 
 }  // namespace hostla

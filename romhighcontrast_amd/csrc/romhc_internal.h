@@ -159,6 +159,9 @@ struct ExtSide {
   int gtab;    // mode 2: offset (doubles) of the (n1*n1) x (nch*BK) table H_0 [P_f, p0_f]
   int gseg;    // mode 2: offset (doubles) of the segment-major copy of that table in Gs (k_extend128)
   int b0, b1;  // mode 2: blocks of the edge (s_f = a_b0 + a_b1)
+  // mode 2: at distance d from the side the first (number of j < 7 with d >= thr[j]) 8-wide K segments of the table are
+  // zero (0xffff: never; rom_fem_plan.hip, ext_truncation)
+  unsigned short thr[8];
 };
 // coefficient block of one closed-form edge on the single-tile path (k_solve1): see the dense product there
 struct DenseGroup {
