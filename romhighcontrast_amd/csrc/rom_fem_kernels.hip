@@ -1778,7 +1778,7 @@ __global__ __launch_bounds__(256) void k_extend(FemDev f, const double* __restri
 // The same extension for blocks whose sides are all compressed, with 128 x 128 workgroup tiles (128 systems x
 // one mesh row of up to 128 interior vertices): K is only sum(rank + 1) ~ 64, so a 64 x 64 tile spends most of its
 // life in its prologue and epilogue; four times the outputs per workgroup amortise them.  Eight waves, 2 x 4 wave
-// tiles of 64 systems x 32 vertices = 4 x 2 MFMA accumulators (106 VGPRs): two waves of the workgroup on every
+// tiles of 64 systems x 32 vertices = 4 x 2 MFMA accumulators (110 VGPRs): two waves of the workgroup on every
 // SIMD, and the two halves of the workgroup take turns fetching the chunks -- a wave held up at the issue of its
 // loads (a fifth of the launch goes there while the neighbour workgroup's stores fill the CU's memory pipeline,
 // profiles/r02_extend128_kloop_probes.txt) leaves the MFMA pipe to its twin.  (Four waves of 64 x 64 with 184 VGPRs,
@@ -1796,21 +1796,13 @@ __global__ __launch_bounds__(256) void k_extend(FemDev f, const double* __restri
 constexpr int X128_SLOT = 4 * 128 * 64;  // bytes
 static_assert(sizeof(FemDev) + sizeof(X128Args) + 64 <= 4096, "k_extend128's arguments must fit the kernel argument segment");
 
-// leading 8-wide K segments of a compressed side that are zero at distance d from it (ExtSide::thr, ascending)
-__device__ inline int x128_skip(const ExtSide& s, int d) {
-  int n = 0;
-#pragma unroll
-  for (int j = 0; j < EXT_THRESHOLDS; ++j) n += d >= int(s.thr[j]) ? 1 : 0;
-  return n;
-}
-
 // FLAT: the 128 vertices of a tile are consecutive in the block's row-major vertex numbering instead of lying in
 // one mesh row -- no padding when n1 is not close to a multiple of 128 (n1 = 170: 226 tiles per block instead of
 // 340); a pair of adjacent vertices may then straddle two mesh rows and is stored as two 8-byte halves.
 template <bool FLAT>
 __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, const double* __restrict__ a, int Mc,
                                                       double* __restrict__ U, long long row0, int with_expand,
-                                                      int sys_fast) {
+                                                      int sys_fast, int wave_skip) {
   __shared__ __align__(16) char lds_bytes[2 * X128_SLOT];  // two chunk slots = 65,536 B: two workgroups per CU
   __shared__ double scs[128];                               // h^2 / a_b of the workgroup's systems
   double* const lds = reinterpret_cast<double*>(lds_bytes);
@@ -1864,6 +1856,13 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   const int jv0 = 128 * (bx % nct) + 1;  // first vertex of the tile                (!FLAT)
   const int vt0 = 128 * bx;              // first vertex of the tile, block-local   (FLAT)
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wr = w >> 2, wc = w & 3;
+  // The wave's 32 vertices are column wcv of the tile.  Waves w and w + 4 share a SIMD; with per-wave skipping the
+  // columns near a perpendicular side do more work than the far ones, so the second row of waves takes the columns in
+  // reverse: every SIMD gets a near and a far column (X128_MIRROR = 0: the same column twice).  The fetch duty stays on wc.
+#ifndef X128_MIRROR
+#define X128_MIRROR 1
+#endif
+  const int wcv = X128_MIRROR && wr ? 3 - wc : wc;
   constexpr int NJ = 2;  // 16-vertex column blocks per wave (wave tile 64 x 32)
   const int fr = lane & 15, kq = lane >> 4;
   double my_sc = 0.0;  // h^2 / a_b of system threadIdx.x: requested now, parked in LDS after the k loop
@@ -1877,10 +1876,10 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     if (FLAT) {
-      const int v = vt0 + wc * (16 * NJ) + j * 16 + fr;
+      const int v = vt0 + wcv * (16 * NJ) + j * 16 + fr;
       w_own[j] = v < nvert ? f.W[v] : 0.0;
     } else {
-      const int jj = jv0 + wc * (16 * NJ) + j * 16 + fr;  // 1-based
+      const int jj = jv0 + wcv * (16 * NJ) + j * 16 + fr;  // 1-based
       w_own[j] = jj <= n1 ? f.W[(iv - 1) * n1 + (jj - 1)] : 0.0;
     }
   }
@@ -1893,32 +1892,35 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   // zeros (k_mask_table) and the walk starts behind them.  The distance of a tile = that of its nearest vertex; a tile
   // that walks more than it needs adds zeros, so every tiling gives the same bits.  Scalar code (the thresholds are
   // kernel arguments).
-  int dist0, dist1, dist2, dist3;
-  if (FLAT) {
-    const int vend = min(vt0 + 127, nvert - 1), i_lo = vt0 / n1, i_hi = vend / n1;  // 0-based mesh rows of the tile
-    const bool one_row = i_lo == i_hi;  // (else the tile meets both ends of a mesh row)
-    dist0 = i_lo + 1;
-    dist1 = N - (i_hi + 1);
-    dist2 = one_row ? vt0 - i_lo * n1 + 1 : 1;
-    dist3 = one_row ? N - (vend - i_hi * n1 + 1) : 1;
-  } else {
-    dist0 = iv;
-    dist1 = N - iv;
-    dist2 = jv0;
-    dist3 = N - min(jv0 + 127, n1);
-  }
-#define X_SEGS(S_) min(2 * sd.s[S_].nch, (sd.s[S_].r + 1 + 7) / 8)
-  const int sk0 = sd.s[0].mode == 2 ? min(x128_skip(sd.s[0], dist0), X_SEGS(0) - 1) : 0;
-  const int sk1 = sd.s[1].mode == 2 ? min(x128_skip(sd.s[1], dist1), X_SEGS(1) - 1) : 0;
-  const int sk2 = sd.s[2].mode == 2 ? min(x128_skip(sd.s[2], dist2), X_SEGS(2) - 1) : 0;
-  const int sk3 = sd.s[3].mode == 2 ? min(x128_skip(sd.s[3], dist3), X_SEGS(3) - 1) : 0;
-  const int cnt0 = sd.s[0].mode == 2 ? X_SEGS(0) - sk0 : 0;
-  const int cnt1 = sd.s[1].mode == 2 ? X_SEGS(1) - sk1 : 0;
-  const int cnt2 = sd.s[2].mode == 2 ? X_SEGS(2) - sk2 : 0;
-  const int cnt3 = sd.s[3].mode == 2 ? X_SEGS(3) - sk3 : 0;
-#undef X_SEGS
+  // A wave owns 32 of the tile's 128 vertices and is farther from the sides than the tile: from its own distances it gets
+  // its own counts wsk >= sk (x128_skip_counts, rom_fem_plan.h) and multiplies only the halves of the walk that hold a
+  // segment >= wsk of its side -- bit h of `live`, built here once per tile.  The DMA walk stays the tile's.
+  int tsk[4], wsk[4];
+  const bool has_vertices = x128_skip_counts<FLAT>(n1, N, bx, wcv, sd.s[0], sd.s[1], sd.s[2], sd.s[3], tsk, wsk);
+  const int sk0 = tsk[0], sk1 = tsk[1], sk2 = tsk[2], sk3 = tsk[3];
+  const int cnt0 = x128_segs(sd.s[0]) - sk0, cnt1 = x128_segs(sd.s[1]) - sk1;
+  const int cnt2 = x128_segs(sd.s[2]) - sk2, cnt3 = x128_segs(sd.s[3]) - sk3;
   const int nseg = cnt0 + cnt1 + cnt2 + cnt3;
   const int tot = (nseg + 1) / 2;
+  // (wave_skip = 0, ROMHC_NO_EXT_WAVE_SKIP: every wave multiplies every half of the tile's walk, the odd last one included,
+  // which is then fetched from the zero page; so does a walk too long for the mask)
+  const bool per_wave = wave_skip != 0 && nseg < 64;
+  long long live = -1;  // shifted down two bits per chunk, arithmetically
+  if (per_wave) {
+    unsigned long long m = 0;
+    int h0 = 0;
+#define X_LIVE(S_, CNT_)                                                                                           \
+  do { /* the side's halves h0 .. h0 + CNT_ - 1 hold its segments sk .. : live from wsk on */                      \
+    m |= ((1ull << (CNT_)) - (1ull << (wsk[S_] - tsk[S_]))) << h0;                                                  \
+    h0 += (CNT_);                                                                                                  \
+  } while (0)
+    X_LIVE(0, cnt0);
+    X_LIVE(1, cnt1);
+    X_LIVE(2, cnt2);
+    X_LIVE(3, cnt3);
+#undef X_LIVE
+    live = (long long)x128_uniform(has_vertices ? m : 0ull);  // (scalar: the k loop branches on its bits)
+  }
   // ---- fragment addressing: lane (fr, kq) reads row fr (+ 16 i) at k = 4 kki + kq: half kki >> 1, unit
   // (2 (kki & 1) + (kq >> 1)) ^ (fr >> 2), byte (kq & 1) * 8
   const unsigned fx = unsigned((kq >> 1) ^ (fr >> 2));
@@ -1928,7 +1930,7 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   do {                                                                                                             \
     const char* pf_ = lds_bytes + (SLOT_) * X128_SLOT + (((KKI_)&1) ? fa1 : fa0);                                  \
     const char* pa_ = pf_ + ((KKI_) >> 1) * 8192 + wr * 4096;                                                      \
-    const char* pb_ = pf_ + 16384 + ((KKI_) >> 1) * 8192 + wc * (1024 * NJ);                                       \
+    const char* pb_ = pf_ + 16384 + ((KKI_) >> 1) * 8192 + wcv * (1024 * NJ);                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) AF_[i_] = *reinterpret_cast<const double*>(pa_ + i_ * 1024);  \
     _Pragma("unroll") for (int i_ = 0; i_ < NJ; ++i_) BF_[i_] = *reinterpret_cast<const double*>(pb_ + i_ * 1024); \
   } while (0)
@@ -2000,7 +2002,7 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
       pB += seg_stride; /* the next 8-wide K segment of the table */                                              \
       --c_segs;                                                                                                    \
       if (--c_left == 0 && c_segs > 0) X_NEXT_SIDE();                                                              \
-    } else if (MINE_) { /* zeros: the odd half of the last chunk */                                                \
+    } else if ((MINE_) && !per_wave) { /* zeros: the odd half of the last chunk (per_wave: nobody reads it) */    \
       X_DMA(sb_, zbase, voZ);                                                                                      \
       X_DMA(sb_ + 1024, zbase, voZ);                                                                               \
       X_DMA(sb_ + 16384, zbase, voZ);                                                                              \
@@ -2018,7 +2020,21 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
     X_ISSUE_HALF(0, 1, w < 4);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     double af[2][4], bf[2][NJ];
-    X_FRAGS(0, 0, af[0], bf[0]);
+#define X_MFMAS(PB_)                                                                                               \
+  do {                                                                                                             \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                  \
+      _Pragma("unroll") for (int j = 0; j < NJ; ++j)                                                               \
+        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[PB_][i], bf[PB_][j], acc[i][j], 0, 0, 0);              \
+  } while (0)
+    // k-step kki of a chunk uses fragment buffer kki & 1, and its fragments are read under the MFMAs of the step before
+    // it.  `live`, bits 0 and 1: the halves of the chunk this wave multiplies (k-steps 0, 1 and 2, 3); the first fragments
+    // of the first live half of the next chunk are read behind the barrier, as before.  One straight line per case.
+#define X_FIRST_FRAGS(SLOT_)                                                                                       \
+  do {                                                                                                             \
+    if (live & 1) X_FRAGS(SLOT_, 0, af[0], bf[0]);                                                                 \
+    else if (live & 2) X_FRAGS(SLOT_, 2, af[0], bf[0]);                                                            \
+  } while (0)
+    X_FIRST_FRAGS(0);
     for (int ch = 0; ch < tot; ++ch) {
       const int slot = ch & 1;
       if (ch + 1 < tot) {  // (everybody left that slot at the barrier behind chunk ch - 1)
@@ -2026,21 +2042,24 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
         X_ISSUE_HALF(slot ^ 1, 0, mine);
         X_ISSUE_HALF(slot ^ 1, 1, mine);
       }
-#pragma unroll
-      for (int kki = 0; kki < 4; ++kki) {
-        const int pb = kki & 1;
-        if (kki < 3) X_FRAGS(slot, kki + 1, af[pb ^ 1], bf[pb ^ 1]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[pb][i], bf[pb][j], acc[i][j], 0, 0, 0);
+      // the live halves of a chunk are consecutive: h_lo .. h_hi - 1
+      const int h_lo = (live & 1) ? 0 : 1, h_hi = (live & 2) ? 2 : 1;
+#pragma unroll 1
+      for (int h = h_lo; h < h_hi; ++h) {
+        X_FRAGS(slot, 2 * h + 1, af[1], bf[1]);
+        X_MFMAS(0);
+        if (h + 1 < h_hi) X_FRAGS(slot, 2, af[0], bf[0]);
+        X_MFMAS(1);
       }
+      live >>= 2;
       {
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // chunk ch + 1 is in LDS for everybody
       }
-      if (ch + 1 < tot) X_FRAGS(slot ^ 1, 0, af[0], bf[0]);
+      if (ch + 1 < tot) X_FIRST_FRAGS(slot ^ 1);
     }
   }
+#undef X_FIRST_FRAGS
+#undef X_MFMAS
 #undef X_ISSUE_HALF
 #undef X_DMA
 #undef X_NEXT_SIDE
@@ -2076,7 +2095,7 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
     char* const rowp = reinterpret_cast<char*>(U) + size_t(row0 + m0 + wr * 64 + kq) * size_t(f.dim) * 8;
 #pragma unroll
     for (int hp = 0; hp < NHP; ++hp) {  // pair hp of column blocks: (0,1) and (2,3); even lanes take the first, odd the second
-      const int t = wc * (16 * NJ) + (2 * hp + (odd ? 1 : 0)) * 16 + fr - (odd ? 1 : 0);  // first of the two vertices, tile-local
+      const int t = wcv * (16 * NJ) + (2 * hp + (odd ? 1 : 0)) * 16 + fr - (odd ? 1 : 0);  // first of the two vertices, tile-local
       long long off0, off1;
       bool ok0, ok1;
       if (FLAT) {
@@ -2132,8 +2151,8 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
       }
     }
 }
-template __global__ void k_extend128<false>(FemDev, X128Args, const double*, int, double*, long long, int, int);
-template __global__ void k_extend128<true>(FemDev, X128Args, const double*, int, double*, long long, int, int);
+template __global__ void k_extend128<false>(FemDev, X128Args, const double*, int, double*, long long, int, int, int);
+template __global__ void k_extend128<true>(FemDev, X128Args, const double*, int, double*, long long, int, int, int);
 
 // interface values that k_expand does not write: cross points and the edges recovered node by node
 __global__ void k_scatter_interface(FemDev f, int Mc, double* __restrict__ U, long long row0) {

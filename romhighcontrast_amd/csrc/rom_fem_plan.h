@@ -31,6 +31,78 @@ __host__ __device__ inline int h0_row(int s, int i, int j, int N, int n1) {
   return (ii - 1) * n1 + (jj - 1);
 }
 
+// leading 8-wide K segments of a compressed side that are zero at distance d from it (ExtSide::thr, ascending)
+__host__ __device__ inline int x128_skip(const ExtSide& s, int d) {
+  int n = 0;
+#ifdef __HIP_DEVICE_COMPILE__
+#pragma unroll
+#endif
+  for (int j = 0; j < EXT_THRESHOLDS; ++j) n += d >= int(s.thr[j]) ? 1 : 0;
+  return n;
+}
+// 8-wide K segments of a side that k_extend128 walks at most (0 for a side that is not compressed): the tables are padded
+// to 16 per side, but only ceil((rank + 1) / 8) segments hold anything
+__host__ __device__ inline int x128_segs(const ExtSide& s) {
+  const int padded = 2 * s.nch, filled = (s.r + 1 + 7) / 8;
+  return s.mode == 2 ? (padded < filled ? padded : filled) : 0;
+}
+// skip count of one side at distance d, clamped: the last segment (with 1/s) is always walked
+__host__ __device__ inline int x128_skip_clamped(const ExtSide& s, int d) {
+  const int n = x128_skip(s, d), last = x128_segs(s) - 1;
+  return s.mode == 2 ? (n < last ? n : last) : 0;
+}
+
+// The K segments k_extend128 skips per side (0: i = 0, 1: i = N, 2: j = 0, 3: j = N) of vertex tile `tile` (tsk: the
+// DMA walk starts behind them) and of the 32 consecutive vertices of its wave column wc = 0 .. 3 (wsk >= tsk: the wave
+// multiplies nothing in front of them).  A distance is that of the nearest vertex; the tile is a mesh row's vertices
+// 128 (tile % nct) + 1 .. + 128, or (FLAT) vertices 128 tile .. + 127 of the block's row-major numbering, where a range
+// that spans two mesh rows meets both ends of one.  Returns false where the wave has no vertex at all (the tile pads).
+template <bool FLAT>
+__host__ __device__ inline bool x128_skip_counts(int n1, int N, int tile, int wc, const ExtSide& s0, const ExtSide& s1,
+                                                 const ExtSide& s2, const ExtSide& s3, int tsk[4], int wsk[4]) {
+  int dist0, dist1, dist2, dist3;  // the tile's
+  int wd0, wd1, wd2, wd3;          // the wave's
+  bool has;
+  if (FLAT) {
+    const int nvert = n1 * n1, vt0 = 128 * tile;
+    const int vend = vt0 + 127 < nvert - 1 ? vt0 + 127 : nvert - 1, i_lo = vt0 / n1, i_hi = vend / n1;  // 0-based mesh rows of the tile
+    const bool one_row = i_lo == i_hi;  // (else the tile meets both ends of a mesh row)
+    dist0 = i_lo + 1;
+    dist1 = N - (i_hi + 1);
+    dist2 = one_row ? vt0 - i_lo * n1 + 1 : 1;
+    dist3 = one_row ? N - (vend - i_hi * n1 + 1) : 1;
+    const int v0 = vt0 + 32 * wc, v1 = v0 + 31 < vend ? v0 + 31 : vend;
+    has = v0 <= vend;
+    const int w_lo = has ? v0 / n1 : i_lo, w_hi = has ? v1 / n1 : i_hi;
+    const bool w_one = w_lo == w_hi;
+    wd0 = w_lo + 1;
+    wd1 = N - (w_hi + 1);
+    wd2 = w_one ? v0 - w_lo * n1 + 1 : 1;
+    wd3 = w_one ? N - (v1 - w_hi * n1 + 1) : 1;
+  } else {
+    const int nct = (n1 + 127) / 128, iv = tile / nct + 1, jv0 = 128 * (tile % nct) + 1;
+    dist0 = iv;
+    dist1 = N - iv;
+    dist2 = jv0;
+    dist3 = N - (jv0 + 127 < n1 ? jv0 + 127 : n1);
+    const int jw = jv0 + 32 * wc;
+    has = jw <= n1;
+    wd0 = iv;
+    wd1 = N - iv;
+    wd2 = jw;
+    wd3 = N - (jw + 31 < n1 ? jw + 31 : n1);
+  }
+  tsk[0] = x128_skip_clamped(s0, dist0);
+  tsk[1] = x128_skip_clamped(s1, dist1);
+  tsk[2] = x128_skip_clamped(s2, dist2);
+  tsk[3] = x128_skip_clamped(s3, dist3);
+  wsk[0] = has ? x128_skip_clamped(s0, wd0) : tsk[0];
+  wsk[1] = has ? x128_skip_clamped(s1, wd1) : tsk[1];
+  wsk[2] = has ? x128_skip_clamped(s2, wd2) : tsk[2];
+  wsk[3] = has ? x128_skip_clamped(s3, wd3) : tsk[3];
+  return has;
+}
+
 // what rom_fem_create reads from the environment for the planner (ROMHC_NO_PREELIM, ROMHC_NO_COMPRESS,
 // ROMHC_NO_LOWRANK_EXT, ROMHC_NO_EXT_LR, ROMHC_VERBOSE, ROMHC_COMPRESS_TOL, ROMHC_NO_EXT_TRUNC)
 struct FemSwitches {

@@ -191,6 +191,7 @@ extern "C" int rom_fem_create(rom_ctx* ctx, int nrb, int ncb, int N, rom_fem** o
     ROM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve1), hipFuncAttributeMaxDynamicSharedMemorySize, S1_LDS_BYTES));
   f->sw_no_fused = getenv("ROMHC_NO_FUSED") != nullptr;
   f->sw_no_ext128 = getenv("ROMHC_NO_EXT128") != nullptr;
+  f->sw_no_ext_wave_skip = getenv("ROMHC_NO_EXT_WAVE_SKIP") != nullptr;
 #ifdef ROMHC_AB
   // The A/B build (libromhc_ab.so, `make ab`; only tests/ab_variants.py loads it) can FORCE choices that the product makes by
   // geometry -- tilings, workgroup orders, one system per workgroup, tiles assembled in registers -- to check that the forms

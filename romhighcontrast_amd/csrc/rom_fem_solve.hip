@@ -214,10 +214,11 @@ static int enqueue_solve(rom_fem* f, const FemDev& d, const double* am, int Mc, 
             const int extra = fold_expand && z0 == 0 ? (items + mt * nz - 1) / (mt * nz) : 0;
             const int order = f->sw_x128_sys_fast >= 0 ? f->sw_x128_sys_fast : (f->gs_bytes >= (size_t(64) << 20) && mt >= 16 ? 1 : 0);
             const int sys_fast = order == 1 ? mt : order == 2 ? -mt : 0;
+            const int wave_skip = f->sw_no_ext_wave_skip ? 0 : 1;  // every wave multiplies only the K segments its own vertices need
             const int nx = sys_fast < 0 ? (t128 + extra + 7) / 8 * 8 : t128 + extra;
             dim3 grid(sys_fast ? nx * mt : nx, sys_fast ? 1 : mt, nz);
-            if (flat) k_extend128<true><<<grid, 512, 0, st>>>(d, xa, am, Mc, U, row, extra, sys_fast);
-            else k_extend128<false><<<grid, 512, 0, st>>>(d, xa, am, Mc, U, row, extra, sys_fast);
+            if (flat) k_extend128<true><<<grid, 512, 0, st>>>(d, xa, am, Mc, U, row, extra, sys_fast, wave_skip);
+            else k_extend128<false><<<grid, 512, 0, st>>>(d, xa, am, Mc, U, row, extra, sys_fast, wave_skip);
           }
         } else {
           dim3 grid(f->n1 * ((f->n1 + 63) / 64), (Mc + 63) / 64, f->n_lr_blocks);

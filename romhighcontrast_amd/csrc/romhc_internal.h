@@ -289,6 +289,7 @@ struct rom_fem {
   // A/B switches of the kernel sequencing, read from the environment ONCE per FE space (rom_fem_create): ROMHC_NO_FUSED,
   // ROMHC_EXT_FLAT (-1: automatic), ROMHC_NO_EXT128, ROMHC_NO_FOLD_EXPAND
   bool sw_no_fused = false, sw_no_ext128 = false, sw_no_fold = false;
+  bool sw_no_ext_wave_skip = false;  // ROMHC_NO_EXT_WAVE_SKIP: every wave of k_extend128 walks its tile's K segments, zero half included
   int sw_x128_sys_fast = -1;   // -1: by table size
   size_t gs_bytes = 0;         // bytes of the segment-major extension tables (k_extend128's B operand)
    // k_extend128: system group fastest in the workgroup order (tables out of cache, not HBM)
