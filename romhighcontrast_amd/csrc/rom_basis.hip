@@ -223,9 +223,12 @@ __global__ __launch_bounds__(SE_TPB) void kb_small_eig(int n, const double* __re
       esum = fmax(esum, rs);
     }
     esum = block_max(esum);
-    // (||E||_2 < 1 is what the iteration needs; the row-sum bound is sufficient, not necessary: up to 3 it is tried and
-    // abandoned -- matrix reloaded, Jacobi below -- if the defect ||Z Y - I|| ever grows)
-    if (gmean > 0.0 && esum < 3.0) {
+    // (||E||_2 < 1 is what the theory asks for; the iteration is tried up to a row-sum bound of 2 and abandoned -- matrix
+    // reloaded, Jacobi below -- if the defect ||Z Y - I|| stops falling: a singular G.  Not beyond 2: an eigenvalue of G / g
+    // above 3 makes W_0 = (3 I - G / g) / 2 indefinite, and the iteration then CONVERGES, its defect falling all the way, to an
+    // inverse square root with a negative eigenvalue -- a whitening, but not the symmetric positive definite one.  Below 2
+    // the spectrum of G / g lies in (0, 3), every W stays positive definite and only the principal root can be reached)
+    if (gmean > 0.0 && esum < 2.0) {
       bool diverged = false;
       double dev_prev = 1e300;
       for (int i = t; i < n; i += SE_TPB) lam[i] = As[i * ld + i];

@@ -19,7 +19,7 @@ struct Jacobi32Lds {
   double A1[32 * J32_LD], V1[32 * J32_LD];   // buffer 1
   double nu2[2][32], ev[32];
   int perm[32];
-  int any;
+  int any[4];   // per wave: whether one of its threads rotated in the sweep
 };
 
 // One Jacobi rotation from the 2 x 2 pivot block (a_pp, a_pq; a_pq, a_qq) and the noise levels of its rows: applied when
@@ -140,12 +140,12 @@ __device__ inline bool jacobi32_run(int n, Jacobi32Lds& L, int gram_like, double
       cur ^= 1;
       __syncthreads();
     }
-    if (t < 64) {
-      const int any = __any(rotated);
-      if (t == 0) L.any = any;
-    }
+    // thread (k, l) records the rotation of slot k only, and the slots are spread over all four waves (wave 0 alone holds
+    // every slot only up to n = 16): the sweep-end flag is the OR over the waves
+    const int wave_any = __any(rotated);
+    if ((t & 63) == 0) L.any[t >> 6] = wave_any;
     __syncthreads();
-    const int any = L.any;
+    const int any = L.any[0] | L.any[1] | L.any[2] | L.any[3];
     __syncthreads();
     if (!any) break;
     ever = true;

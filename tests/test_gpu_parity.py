@@ -215,9 +215,10 @@ def test_greedy_call_matches_its_definition(api, mode_name):
 
 
 def test_small_symmetric_eigensolver_vs_lapack():
-    """The one-workgroup Jacobi kernel behind the whitening / Rayleigh-Ritz steps of rom_pod and rom_greedy, against
-    numpy.linalg.eigh: random symmetric matrices in LDS (n <= 96) and in the global workspace (n > 96), and a graded
-    positive definite matrix whose small eigenvalues must come out to high RELATIVE accuracy."""
+    """The Jacobi kernels behind the whitening / Rayleigh-Ritz steps of rom_pod and rom_greedy, against numpy.linalg.eigh:
+    random symmetric matrices on one workgroup (jacobi32_run up to n = 32, kb_small_eig in LDS up to n = 96) and on the
+    grid-wide Jacobi (n > 96: jacobi_grid, one launch per round), and a graded positive definite matrix whose small
+    eigenvalues must come out to high RELATIVE accuracy.  The truth tests of every route: tests/test_gpu_small_dense.py."""
     from romhighcontrast_amd import _ffi
     ctx = _ffi.get_context()
     rng = np.random.default_rng(3)
