@@ -12,6 +12,8 @@ PBDW (greedy basis, n in {0, 1, 10, 20}, m in {20, 50} separated points):
   the a-priori bound ||u - u*|| <= dist(u, V_n) / beta_n, reproduction of span V_n, n = 0 = minimum-norm interpolant;
 * a host restatement (SciPy representers + dense saddle point) at (2,2) N=8;
 * ndarray / DeviceArray bases give identical bits, return_coefs feeds the parameter estimators, ValueError cases.
+Representers, G and the norms against an 80-bit truth with derived bounds (grids with nr != nc across a 64-row tile, the
+split launch of the second transform): tests/test_gpu_sensor_truth.py; it shares _points with this module.
 """
 import numpy as np
 import pytest

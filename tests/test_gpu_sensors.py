@@ -9,6 +9,9 @@
   selection against random subsets and the a-priori bound with the selected points;
 * the contract: bit-identical repeats (also under ROMHC_POISON_WS), ndarray / DeviceArray bases, beta_target = prefix
   of the full run, the stop reasons, ValueError for n = 0, "outside the domain".
+These are fp64 restatements with flat tolerances on greedy snapshot bases.  The 80-bit truth with derived bounds, the n
+routes of the eigen-solver, m > 256, more than 1024 partials, dead rows and row offsets: tests/test_gpu_sensor_truth.py
+(truth and bounds: tests/sensor_truth.py).
 """
 import numpy as np
 import pytest
