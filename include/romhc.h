@@ -474,6 +474,25 @@ int rom_tree_query(rom_tree* h, int64_t* out8);
 int rom_tree_download(rom_tree* h, int what, double* host, size_t count);
 int rom_tree_destroy(rom_tree* h);
 
+/* ---- nearest rows of a tall library: the search of the library-based parameter estimation (src/lib/Estimators.py) ----------
+ * For each of the K query rows of P, the t rows of the library Q (M rows) at the smallest squared Euclidean distance.  Q and P:
+ * r columns from an element offset with a row stride, as in rom_poly_fit; neither is modified.  1 <= r <= 128, 1 <= t <= 8,
+ * t <= M; K = 0 is a no-op.
+ * dist2_host[k t + s] = sum_c (p_c - q_c)^2, formed from the original operands as differences (never a Gram expansion) by ONE
+ * device function with one summation order: within (r + 2) eps (eps = 2^-52) relative of the exact value, exactly 0.0 for a
+ * coincident row.  idx_host[k t .. + t) = the t rows that are smallest under the order (that value, row index), in that order:
+ * bit for bit what an exhaustive scan with that function returns.  NaN / Inf in either operand: ROM_ERR_INVALID.  No floating-
+ * point atomics: the same bits on a repeated call.
+ * mode 0: screened search -- scores |q~|^2 - 2 p~ . q~ on operands shifted by the library's column means, one MFMA kernel that
+ * writes only the minimum of every group of G = 32 rows and query (K x ceil(M / 32) doubles, the queries in passes when that
+ * would exceed the workspace limit); per query the T' = t + 4 groups of smallest minima are rescored exactly, and a certificate
+ * with a proven bound on the screen's error decides whether the rows not rescored can be excluded; the queries it does not
+ * certify go to the exhaustive kernel.  mode 1 (test hook): the exhaustive kernel for every query.
+ * info_host (8 doubles or NULL): G, T', queries certified by the screen, queries sent to the exhaustive kernel, kernel launches,
+ * host synchronisations, bytes of workspace, executed flops. */
+int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, int64_t M, rom_buf* P, size_t p_off, int64_t ldp, int K, int r,
+                int t, int mode, int64_t* idx_host, double* dist2_host, double* info_host);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

@@ -126,6 +126,8 @@ PROTOTYPES = {
     "rom_poly_query": (C.c_int, [_vp, _vp]),
     "rom_poly_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
     "rom_poly_destroy": (C.c_int, [_vp]),
+    "rom_nearest": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, C.c_int,
+                              C.c_int, _vp, _vp, _vp]),
     "rom_tree_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "rom_tree_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
@@ -335,6 +337,18 @@ class Context:
         q columns of Y over M rows, built level by level on the device.  ``counts``: (T, M) integer multiplicities of the rows
         per tree (the bootstrap), None: every row once.  Neither block is modified.  Returns the TreeMapHandle."""
         return TreeMapHandle(self, X, x_off, ldx, m, Y, y_off, ldy, q, M, T, counts, max_depth, min_samples_split, min_samples_leaf)
+
+    def nearest(self, Q: "Buffer", q_off, ldq, M, P: "Buffer", p_off, ldp, K, r, t=1, mode=0):
+        """rom_nearest: for the K rows of P the t rows of the library Q (M rows; both r columns from an element offset with a
+        row stride) at the smallest squared distance, sorted by (distance, row).  mode 1: the exhaustive kernel for every query.
+        Returns (idx (K, t) int64, dist2 (K, t), info dict)."""
+        idx, dist2, info = np.zeros((int(K), int(t)), dtype=np.int64), np.zeros((int(K), int(t))), np.zeros(8)
+        check(self.lib.rom_nearest(self.h, Q.h if Q is not None else None, int(q_off), int(ldq), int(M), P.h if P is not None else None,
+                                   int(p_off), int(ldp), int(K), int(r), int(t), int(mode), idx.ctypes.data, dist2.ctypes.data,
+                                   info.ctypes.data))
+        d = dict(group_size=int(info[0]), groups_rescored=int(info[1]), certified=int(info[2]), fallbacks=int(info[3]),
+                 launches=int(info[4]), host_syncs=int(info[5]), workspace_bytes=int(info[6]), executed_flops=float(info[7]))
+        return idx, dist2, d
 
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):
         check(self.lib.rom_symmetric_orthonormalize(self.h, V.h, v_row0, n, dim))

@@ -94,6 +94,7 @@ struct rom_ctx {
   unsigned long long host_syncs = 0;
   bool lds_optin_reduced_solve = false, lds_optin_small_eig = false, lds_optin_pivchol = false, lds_optin_pca_tall = false;
   bool lds_optin_poly_pass = false, lds_optin_poly_predict = false;
+  bool lds_optin_nn_screen = false, lds_optin_nn_exhaust = false;
 };
 
 struct rom_buf {

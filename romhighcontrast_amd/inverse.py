@@ -1,0 +1,214 @@
+"""Parameter estimation from sensor data through a library of reduced states.
+
+``EstimatorInv`` / ``EstimatorLinear`` read the parameters off the state-estimation coefficients: defined only for a basis whose
+rows are snapshots, they amplify measurement noise by cond(E) and say nothing about how well the data determine the parameters.
+Here the parameters are SEARCHED: ``rom_resid_eval`` solves the Galerkin ROM for M library parameters in one call and leaves
+their coordinates COEF (M x n) on the device; for K measurement vectors ``rom_nearest`` finds the library states that explain
+them best (the K x M misfits never exist), and a Gauss-Newton / Levenberg-Marquardt polish on the host (n x n systems,
+batched over the queries) refines the parameters from the best library entries.  Works for any basis.
+
+    lib = ParameterLibrary(sm, basis, a_library).observe(points)
+    est = lib.estimate(measurements)           # ParameterEstimate
+"""
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+from .lib.ReducedBasis import ResidualBound, ResidualEstimator
+from .lib.SolutionsManagers import DeviceArray
+
+
+class PolishResult(NamedTuple):
+    """``polish_parameters``: theta (K, k) = log a, misfit (K,) = ||w (y - E^T c(theta))||_2, coefficients (K, n), converged
+    and iterations (K,), sigma_min (K,) of the final Jacobian d(w E^T c) / d theta, start (K,) the start that won."""
+    theta: np.ndarray
+    misfit: np.ndarray
+    coefficients: np.ndarray
+    converged: np.ndarray
+    iterations: np.ndarray
+    sigma_min: np.ndarray
+    start: np.ndarray
+
+
+class ParameterEstimate(NamedTuple):
+    """``ParameterLibrary.estimate``: a (K, *blocks); misfit (K,) of the estimate; start_index / start_misfit (K, t): the library
+    rows the search returned and their misfits, nearest first; converged, iterations (K,) of the polish; sigma_min (K,): the
+    smallest singular value of the final Jacobian of the weighted predictions with respect to log a -- how well the data
+    determine the parameters; coefficients (K, n) of the reduced state in the A_1-orthonormal basis; error_bound: the
+    ``ResidualBound`` of the ROM at the estimate; states: DeviceArray (K, dim) of the reduced states, or None."""
+    a: np.ndarray
+    misfit: np.ndarray
+    start_index: np.ndarray
+    start_misfit: np.ndarray
+    converged: np.ndarray
+    iterations: np.ndarray
+    sigma_min: np.ndarray
+    coefficients: np.ndarray
+    error_bound: ResidualBound
+    states: Optional[DeviceArray]
+
+
+def _rom_state(Ahat, bhat, G, y, theta, jacobian=True):
+    """c(theta) (B, n), the weighted residual r = y - G c (B, m) and J = dr/dtheta (B, m, k) for B parameter rows; G = w E^T."""
+    ea = np.exp(theta)
+    A = np.einsum("bq,qij->bij", ea, Ahat)
+    c = np.linalg.solve(A, np.broadcast_to(bhat, (len(theta), len(bhat)))[..., None])[..., 0]
+    r = y - c @ G.T
+    if not jacobian:
+        return c, r, None
+    V = np.einsum("qij,bj->biq", Ahat, c) * ea[:, None, :]    # A_q c e^theta_q: columns of -A dc/dtheta
+    X = np.linalg.solve(A, V)                                   # -dc/dtheta_q = e^theta_q A^-1 A_q c
+    return c, r, np.einsum("mi,biq->bmq", G, X)                 # dr/dtheta = -G dc/dtheta
+
+
+def polish_parameters(Ahat, bhat, E, Y, theta0, lo, hi, weights=None, max_iter=30, misfit_tol=1e-3):
+    """Levenberg-Marquardt in theta = log a for  min ||w (y - E^T c(theta))||_2,  c(theta) = (sum_q e^theta_q Ahat_q)^-1 bhat,
+    dc/dtheta_q = -e^theta_q A^-1 Ahat_q c; pure NumPy, batched over the queries.  Ahat (k, n, n), bhat (n,): the reduced
+    model (``Resid.download("Ahat" / "bhat")``); E (n, m): the basis at the sensors; Y (K, m); theta0 (K, k) or (K, t, k):
+    the starts -- the polish runs from each and keeps the smallest misfit; theta stays in the box [lo, hi] (scalars or (k,)).
+    ``converged``: the iteration became stationary (or the misfit reached rounding level) AND the final misfit is at most
+    misfit_tol max|w y| -- on exact data a run that stalls in a local minimum ends far above that, under noise choose
+    misfit_tol above the noise level.  max_iter = 0 only evaluates the starts."""
+    Ahat, bhat, E = np.asarray(Ahat, dtype=np.float64), np.asarray(bhat, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+    K, m = Y.shape
+    k, n = Ahat.shape[0], Ahat.shape[1]
+    theta0 = np.asarray(theta0, dtype=np.float64).reshape(K, -1, k)
+    t = theta0.shape[1]
+    w = np.ones(m) if weights is None else np.asarray(weights, dtype=np.float64)
+    G = w[:, None] * E.T
+    lo, hi = np.broadcast_to(np.asarray(lo, dtype=np.float64), (k,)), np.broadcast_to(np.asarray(hi, dtype=np.float64), (k,))
+    y = np.repeat(w[None, :] * Y, t, axis=0)                     # (B, m), B = K t
+    B = K * t
+    theta = np.clip(theta0.reshape(B, k), lo, hi)
+    scale = np.maximum(np.abs(y).max(axis=1), np.finfo(float).tiny)
+    c, r, _ = _rom_state(Ahat, bhat, G, y, theta, jacobian=False)
+    f = np.einsum("bm,bm->b", r, r)
+    lam = np.full(B, 1e-3)
+    active = np.ones(B, dtype=bool)
+    stationary = np.zeros(B, dtype=bool)
+    iterations = np.zeros(B, dtype=np.int64)
+    for _ in range(int(max_iter)):
+        ia = np.flatnonzero(active)
+        if ia.size == 0:
+            break
+        iterations[ia] += 1
+        _, ra, Ja = _rom_state(Ahat, bhat, G, y[ia], theta[ia])
+        JtJ = np.einsum("bmq,bmp->bqp", Ja, Ja)
+        g = np.einsum("bmq,bm->bq", Ja, ra)
+        dJ = np.einsum("bqq->bq", JtJ)
+        todo = np.ones(ia.size, dtype=bool)
+        for _trial in range(8):
+            it = np.flatnonzero(todo)
+            if it.size == 0:
+                break
+            damp = lam[ia[it], None] * (dJ[it] + 1e-300) + 1e-30 * dJ[it].max(axis=1, keepdims=True)
+            H = JtJ[it] + damp[:, :, None] * np.eye(k)
+            step = -np.linalg.solve(H, g[it][..., None])[..., 0]
+            new = np.clip(theta[ia[it]] + step, lo, hi)
+            moved = np.abs(new - theta[ia[it]]).max(axis=1)
+            cn, rn, _ = _rom_state(Ahat, bhat, G, y[ia[it]], new, jacobian=False)
+            fn = np.einsum("bm,bm->b", rn, rn)
+            ok = fn < f[ia[it]]
+            still = moved <= 1e-13 * (1.0 + np.abs(new).max(axis=1))
+            acc = ia[it[ok]]
+            theta[acc], c[acc], r[acc], f[acc] = new[ok], cn[ok], rn[ok], fn[ok]
+            lam[acc] = np.maximum(lam[acc] / 3.0, 1e-12)
+            lam[ia[it[~ok]]] *= 4.0
+            # a step that no longer moves theta (accepted: below 1e-10 relative), or a misfit at rounding level: stationary
+            tiny = ok & (moved <= 1e-10 * (1.0 + np.abs(new).max(axis=1)))
+            done = still | tiny | (np.sqrt(f[ia[it]]) <= 1e-14 * scale[ia[it]])
+            stationary[ia[it[done]]] = True
+            active[ia[it[done]]] = False
+            todo[it[ok | done]] = False
+        stuck = ia[np.flatnonzero(todo)]     # eight increases of the damping without a decrease: a minimum to working accuracy
+        stationary[stuck] = True
+        active[stuck] = False
+    c, r, J = _rom_state(Ahat, bhat, G, y, theta)
+    misfit = np.sqrt(np.einsum("bm,bm->b", r, r))
+    sig = np.linalg.svd(J, compute_uv=False)[:, -1] if min(m, k) else np.zeros(B)
+    best = np.argmin(misfit.reshape(K, t), axis=1)
+    pick = np.arange(K) * t + best
+    conv = (stationary | (misfit <= 1e-14 * scale)) & (misfit <= misfit_tol * scale)
+    return PolishResult(theta[pick], misfit[pick], c[pick], conv[pick], iterations[pick], sig[pick], best)
+
+
+class ParameterLibrary:
+    """The Galerkin ROM on ``basis`` solved for the M parameters ``a_library`` (one ``rom_resid_eval`` call over all of them):
+    their coordinates COEF (M, n) in the A_1-orthonormal basis stay on the device, ``.a`` (M, k), ``.residual`` and ``.upper``
+    (the certified bound ||r|| / a_min of the ROM error of every entry) on the host.  ``observe`` fixes the sensors,
+    ``estimate`` answers measurement vectors."""
+
+    def __init__(self, sm, basis, a_library, n=None):
+        self.sm = sm
+        self.estimator = ResidualEstimator(sm, basis)
+        self.n = self.estimator.n if n is None else min(int(n), self.estimator.n)
+        ctx = sm._ctx
+        self.a = sm._a_batch(a_library)
+        self.M = M = self.a.shape[0]
+        if M < 1 or self.n < 1:
+            raise ValueError("ParameterLibrary needs at least one library parameter and one basis row")
+        D = ctx.alloc(M)
+        self.COEF = ctx.alloc(M * self.n)
+        self.estimator.handle.eval(ctx.upload(self.a), M, self.n, D, COEF=self.COEF)
+        self.residual = D.download(M)
+        self.upper = self.residual / self.a.min(axis=1)
+        self.Ahat = self.estimator.handle.download("Ahat")[:, :self.n, :self.n].copy()
+        self.bhat = self.estimator.handle.download("bhat")[:self.n].copy()
+        self._W = ctx.alloc(self.estimator.n * sm.vspace_dim)
+        self.estimator.handle.basis(self._W)
+        self.points = None
+
+    def observe(self, points, weights=None):
+        """Fix the sensors: E = l(W) (n, m); compact SVD diag(w) E^T = U S V^T truncated at sigma > 1e-12 sigma_1 (rank r);
+        the library coordinates COEF (V S) (M, r) are formed on the device.  The weighted misfit of library entry j is then
+        ||U^T (w y) - q_j||^2 + ||(I - U U^T) (w y)||^2."""
+        sm, ctx = self.sm, self.sm._ctx
+        self.points = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+        m = len(self.points)
+        self.weights = np.ones(m) if weights is None else np.asarray(weights, dtype=np.float64).reshape(m)
+        self.E = sm._fem.evaluate_points(self._W, self.n, *sm._locate(self.points))
+        U, S, Vt = np.linalg.svd(self.weights[:, None] * self.E.T, full_matrices=False)
+        self.r = r = max(1, int(np.sum(S > 1e-12 * S[0])))
+        self.U = np.ascontiguousarray(U[:, :r])
+        VS = np.ascontiguousarray(Vt[:r].T * S[:r])
+        self.Qc = ctx.alloc(self.M * r)
+        ctx.gemm_nn(self.M, r, self.n, self.COEF, 0, self.n, ctx.upload(VS), 0, r, self.Qc, 0, r)
+        return self
+
+    def search(self, measurements, t=4, mode=0):
+        """The t library rows of smallest misfit per measurement vector: (idx (K, t), misfit (K, t), info of rom_nearest)."""
+        if self.points is None:
+            raise RuntimeError("ParameterLibrary.observe(points) comes first")
+        Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
+        Yw = Y * self.weights[None, :]
+        Pq = np.ascontiguousarray(Yw @ self.U)
+        perp = Yw - Pq @ self.U.T
+        t = min(int(t), self.M)
+        ctx = self.sm._ctx
+        idx, d2, info = ctx.nearest(self.Qc, 0, self.r, self.M, ctx.upload(Pq) if len(Y) else None, 0, self.r, len(Y), self.r, t=t,
+                                    mode=mode)
+        return idx, np.sqrt(d2 + np.einsum("km,km->k", perp, perp)[:, None]), info
+
+    def estimate(self, measurements, t=4, polish=True, states=False, max_iter=30, misfit_tol=1e-3) -> ParameterEstimate:
+        """Parameters for the K measurement vectors (K, m): the search, then (``polish``) Levenberg-Marquardt in log a from
+        each of the t library entries found, inside the library's box; without the polish the nearest library entry."""
+        sm, ctx = self.sm, self.sm._ctx
+        Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
+        K = len(Y)
+        idx, start_misfit, _ = self.search(Y, t=t)
+        la = np.log(self.a)
+        starts = la[idx] if polish else la[idx[:, :1]]
+        res = polish_parameters(self.Ahat, self.bhat, self.E, Y, starts, la.min(axis=0), la.max(axis=0), weights=self.weights,
+                                max_iter=max_iter if polish else 0, misfit_tol=misfit_tol)
+        a = np.exp(res.theta) if polish else self.a[idx[:, 0]]
+        bound = self.estimator.bound(a, n=self.n)
+        S = None
+        if states:
+            dim = sm.vspace_dim
+            out = ctx.alloc(max(K * dim, 1))
+            if K:
+                ctx.gemm_nn(K, dim, self.n, ctx.upload(np.ascontiguousarray(res.coefficients)), 0, self.n, self._W, 0, dim, out, 0, dim)
+            S = DeviceArray(out, K, dim)
+        return ParameterEstimate(a.reshape((K,) + tuple(sm.blocks_geometry)), res.misfit, idx, start_misfit, res.converged,
+                                 res.iterations, res.sigma_min, res.coefficients, bound, S)

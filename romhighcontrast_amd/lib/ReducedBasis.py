@@ -429,6 +429,16 @@ class BaseReducedBasis:
         """(:80-86) linear estimate from the state-estimation coefficients."""
         return self.linear_parameter_estimator.estimate_parameter(c_values=c)
 
+    def parameter_estimation_library(self, sm: SolutionsManager, measurement_points: np.ndarray, measurements: np.ndarray,
+                                     a_library, **kw):
+        """Parameters from point measurements by a search over the Galerkin ROM's states for the parameters ``a_library``
+        (``rom_nearest``) and a Levenberg-Marquardt polish from the best entries: ``inverse.ParameterLibrary`` -- any basis,
+        no amplification by cond(E).  ``kw``: weights (of ``observe``), t, polish, states, max_iter, misfit_tol (of
+        ``estimate``).  Returns a ``ParameterEstimate``."""
+        from ..inverse import ParameterLibrary
+        lib = ParameterLibrary(sm, self.basis, a_library).observe(measurement_points, weights=kw.pop("weights", None))
+        return lib.estimate(measurements, **kw)
+
     def orthonormalize(self):
         """(:94-98) replace the basis by its contrast-sorted Euclidean-orthonormal version."""
         vectors = np.reshape(self.basis, (-1, self.ambient_space_dim))
