@@ -198,9 +198,13 @@ static int enqueue_solve(rom_fem* f, const FemDev& d, const double* am, int Mc, 
         k_extend<<<grid, 256, 0, st>>>(d, am, Mc, U, row, d.gen_blocks, 4);
       }
       if (f->n_lr_blocks > 0) {
-        ROM_PROF(ctx, "extend_lr", fl_ext * f->n_lr_blocks, 8.0 * Mc * double(f->n_lr_blocks) * nij);
+        const int mt = (Mc + 127) / 128;
+        // workgroup order of k_extend128: the system group varies fastest where the tables outgrow the caches
+        const int order = f->sw_x128_sys_fast >= 0 ? f->sw_x128_sys_fast : (f->gs_bytes >= (size_t(64) << 20) && mt >= 16 ? 1 : 0);
+        const int sys_fast = !wide ? 0 : order == 1 ? mt : order == 2 ? -mt : 0;
+        rom_prof_name(nm[0], 48, "extend_lr", "%s", sys_fast ? "_sysfast" : "");  // (the order shows under ROMHC_PROF_DETAIL only)
+        ROM_PROF(ctx, nm[0], fl_ext * f->n_lr_blocks, 8.0 * Mc * double(f->n_lr_blocks) * nij);
         if (wide) {
-          const int mt = (Mc + 127) / 128;
           const int items = (f->n1p / 64) * ((Mc + 63) / 64) * (f->nexp + 1);  // workgroups of the folded expansion
           // block descriptors travel as kernel arguments, X128_BLOCKS per launch; the folded expansion rides in the first
           for (int z0 = 0; z0 < f->n_lr_blocks; z0 += X128_BLOCKS) {
@@ -212,8 +216,6 @@ static int enqueue_solve(rom_fem* f, const FemDev& d, const double* am, int Mc, 
               xa.sides[z] = f->sides[xa.blocks[z]];
             }
             const int extra = fold_expand && z0 == 0 ? (items + mt * nz - 1) / (mt * nz) : 0;
-            const int order = f->sw_x128_sys_fast >= 0 ? f->sw_x128_sys_fast : (f->gs_bytes >= (size_t(64) << 20) && mt >= 16 ? 1 : 0);
-            const int sys_fast = order == 1 ? mt : order == 2 ? -mt : 0;
             const int wave_skip = f->sw_no_ext_wave_skip ? 0 : 1;  // every wave multiplies only the K segments its own vertices need
             const int nx = sys_fast < 0 ? (t128 + extra + 7) / 8 * 8 : t128 + extra;
             dim3 grid(sys_fast ? nx * mt : nx, sys_fast ? 1 : mt, nz);

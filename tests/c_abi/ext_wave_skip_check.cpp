@@ -1,6 +1,7 @@
 // Stand-alone check of the per-wave K-segment skipping of k_extend128 (x128_skip_counts, romhighcontrast_amd/csrc/rom_fem_plan.h:
 // the function the kernel calls), built with -fsanitize=address,undefined by tests/test_ext_wave_skip_host.py.  Plans
-// 2x2 / N = 128 (row tiles), 3x3 / N = 64 (FLAT), 3x3 / N = 171 (FLAT, n1 = 170), 2x3 / N = 128 and 4x4 / N = 256 and, for every
+// 2x2 / N = 128 (row tiles), 3x3 / N = 64 (FLAT), 3x3 / N = 171 (FLAT, n1 = 170), 2x3 / N = 128, 4x4 / N = 256 and the wide cases
+// of tests/sweep_truth.py with something to skip (2x2 / N = 171, 3x3 / N = 140: FLAT, n1 odd; 2x2 / N = 250: row tiles) and, for every
 // block the 128-vertex kernel extends, every tile, wave column and side, checks by brute force over the wave's vertices that no
 // K segment a vertex needs (FemPlan::GemmG::seg0 at the vertex's distance) lies in front of the wave's skip count, that the wave's
 // count is never below the tile's and that every geometry has a (tile, wave, side) where it is larger.  Prints per geometry
@@ -81,7 +82,8 @@ static void check_tiling(const FemPlan& p, long long* executed_tile, long long* 
 }
 
 int main() {
-  const struct { int nrb, ncb, N; } geo[] = {{2, 2, 128}, {3, 3, 64}, {3, 3, 171}, {2, 3, 128}, {4, 4, 256}};
+  const struct { int nrb, ncb, N; } geo[] = {{2, 2, 128}, {3, 3, 64}, {3, 3, 171}, {2, 3, 128}, {4, 4, 256},
+                                             {2, 2, 171}, {3, 3, 140}, {2, 2, 250}};  // (the wide cases of tests/sweep_truth.py)
   for (const auto& g : geo) {
     char name[64];
     snprintf(name, sizeof(name), "%dx%d-N%d", g.nrb, g.ncb, g.N);

@@ -143,7 +143,8 @@ static void plan_case(const char* name, int nrb, int ncb, int N, FemSwitches sw)
 int main() {
   const FemSwitches plain{false, false, false, false, false, 1e-14L};
   const struct { int nrb, ncb, N; } geo[] = {{2, 2, 2},  {2, 2, 3}, {2, 2, 16}, {2, 2, 65}, {2, 2, 66}, {2, 2, 128},
-                                             {1, 1, 8},  {1, 2, 128}, {1, 3, 7}, {2, 3, 40}, {3, 3, 24}, {5, 4, 33}};
+                                             {1, 1, 8},  {1, 2, 128}, {1, 3, 7}, {2, 3, 40}, {3, 3, 24}, {5, 4, 33},
+                                             {2, 2, 171}, {3, 3, 140}, {2, 2, 250}, {1, 2, 257}};
   for (const auto& g : geo) {
     char name[64];
     snprintf(name, sizeof(name), "%dx%d-N%d", g.nrb, g.ncb, g.N);

@@ -6,9 +6,10 @@ here, in a child process:
 Every case of sweep_truth.CASES sweeps its smallest batch and 129 systems with per-kernel profiling; the routes are read
 from the ROM_PROF labels (solve1, rhs, diag_update_jNN, ..., extend_lr; sweep_truth.routes_of_profile adds what the labels
 cannot tell -- the tiling of k_extend128, its launch count -- from the restated decision and the block counts that
-ROMHC_VERBOSE prints when the FE space is created).  Then the three product switches: more than 2048 systems, a workspace
-limit of 70 systems, a sweep of 700 after one of 256 on the same FE space (the number of chunks is the launch count of the
-first kernel).  Prints one line "ROUTES {json: id -> {want, seen, want_small, seen_small, ...}}" and a last line "OK".  TEST INFRASTRUCTURE."""
+ROMHC_VERBOSE prints when the FE space is created).  Then the four product switches: more than 2048 systems, 1921 systems
+of 3x3-N140 (k_extend128 in the system-fast workgroup order: the label extend_lr_sysfast), a workspace limit of 70 systems, a
+sweep of 700 after one of 256 on the same FE space (the number of chunks is the launch count of the first kernel).  Prints
+one line "ROUTES {json: id -> {want, seen, want_small, seen_small, ...}}" and a last line "OK".  TEST INFRASTRUCTURE."""
 import json
 import os
 import re
@@ -74,12 +75,19 @@ def main():
         expands = "expand" in p_small
         out[case.id] = {"want": sorted(case.routes), "want_small": sorted(st.narrow_routes(case.routes)), "seen": sorted(st.routes_of_profile(p_129, n1, 129, n_lr, expands)),
                         "seen_small": sorted(st.routes_of_profile(p_small, n1, small, n_lr, expands)), "small": small,
-                        "n_tiles": fem.n_tiles, "n_lr_blocks": n_lr, "profile": sorted(p_129)}
+                        "n_tiles": fem.n_tiles, "n_lr_blocks": n_lr, "profile": sorted(p_129), "profile_small": sorted(p_small)}
     # the product switches
     case = st.CASE[st.BIG_CASE]
     fem, _ = create_verbose(ctx, case)
     p = profiled_sweep(ctx, fem, case, st.BIG_M)
     out["big"] = {"seen": sorted(st.routes_of_profile(p, case.N - 1, st.BIG_M, 0, True)), "launches": first_kernel_launches(p)}
+    case = st.CASE[st.SYS_FAST_CASE]
+    fem, text = create_verbose(ctx, case)
+    m = re.search(r"128-tile kernel: (\d+), general kernel: (\d+)", text)
+    p = profiled_sweep(ctx, fem, case, st.SYS_FAST_M)
+    out["sys_fast"] = {"seen": sorted(st.routes_of_profile(p, case.N - 1, st.SYS_FAST_M, int(m.group(1)) if m else 0, True)),
+                       "profile": sorted(p), "M": st.SYS_FAST_M, "launches": first_kernel_launches(p)}
+    del fem
     for cid in st.CHUNK_CASES:
         case = st.CASE[cid]
         fem, _ = create_verbose(ctx, case)

@@ -51,14 +51,25 @@ CASES = [
     Case("1x3-N7", (1, 3), 7, (5, 129), 1, _ST, ("solve1",) + _SINE),
     Case("2x2-N3", (2, 2), 3, (5, 129), 3, _ST, ("solve1",) + _SINE),                  # two-node edges
     Case("2x2-N2", (2, 2), 2, (5, 129), 1, _ST, ("solve1",) + _SINE),                  # one-node edges, dim 9
+    # blocks wider than one 128-vertex tile (n1 >= 128): what k_extend128 does at the sizes of C4 and C5
+    Case("2x2-N171", (2, 2), 171, (5, 129, 257), 2, _ST, ("solve1",) + _FOLD_FLAT),    # C4's block: flat tiles inside one mesh row, n1 even
+    Case("3x3-N140", (3, 3), 140, (64, 129), 1, _TC, _TILE + _FOLD_FLAT),              # n1 odd: pairs straddle rows; four-sided centre block
+    Case("2x2-N250", (2, 2), 250, (3, 129, 257), 3, _ST, ("solve1",) + _FOLD_ROW),     # two column tiles, the second of 121 vertices
+    Case("1x2-N257", (1, 2), 257, (5, 129), 1, _CF, ("rhs", "coef") + _FOLD_ROW),      # two full column tiles; sides of one K chunk
 ]
 CASE = {c.id: c for c in CASES}
 FULL_CASES = ("2x2-N16", "3x3-N24", "2x3-N40")      # a single-tile and two tile Cholesky geometries (general blocks;
 #                                                     compressed blocks: k_extend128) carry FULL_MS
 CHUNK_CASES = ("2x2-N16", "3x3-N24")
-DISTINCT_CASES = ("2x2-N16", "3x3-N24", "1x2-N128")
+DISTINCT_CASES = ("2x2-N16", "3x3-N24", "1x2-N128", "2x2-N250")
+DISTINCT_MS = {"2x2-N250": 129}     # (dim 249 001: one full 128-system tile and one system more; the others carry DISTINCT_M)
 BIG_CASE = "3x3-N24"
 C2_CASE = "2x2-N128"
+WIDE_CASES = ("2x2-N171", "3x3-N140", "2x2-N250", "1x2-N257")
+SYS_FAST_CASE = "3x3-N140"
+SYS_FAST_M = 1921         # 16 system groups, the fewest that switch the workgroup order; the last group holds one system
+SYS_FAST_BYTES = 64 << 20
+SYS_FAST_GROUPS = 16
 
 ROUTES = {
     "solve1": "the whole reduced solve in k_solve1 (single tile)",
@@ -77,6 +88,7 @@ ROUTES = {
     "extend_lr_128_row": "k_extend128, 128 vertices of one mesh row",
     "extend_lr_128_flat": "k_extend128, 128 consecutive vertices of the block",
     "extend_128_multi_launch": "more than 16 compressed blocks: several k_extend128 launches",
+    "extend_128_sys_fast": "k_extend128 with the system group varying fastest (large tables, at least 16 system groups)",
     "scatter_interface": "k_scatter_interface: interface values copied by a kernel of their own",
     "diag_update_single": "more than 2048 systems: k_diag_update<1>",
     "chunked": "a workspace limit splits the sweep into chunks",
@@ -98,8 +110,10 @@ def params(case):
     return 10.0 ** rng.uniform(0, 4, size=(n_params(case), p * q))
 
 
-def distinct_params(case, M=DISTINCT_M):
-    """M parameter vectors, all different (a value-dependent mix-up that repeated vectors could mask)."""
+def distinct_params(case, M=None):
+    """M (default: DISTINCT_MS[case.id], else DISTINCT_M) parameter vectors, all different (a value-dependent mix-up that
+    repeated vectors could mask)."""
+    M = DISTINCT_MS.get(case.id, DISTINCT_M) if M is None else M
     p, q = case.blocks
     rng = np.random.default_rng([0xD157, p, q, case.N])
     a = 10.0 ** rng.uniform(0, 4, size=(M, p * q))
@@ -167,6 +181,13 @@ def extension_tiling(n1, Mc):
     return ("flat" if flat else "row") if wide else "t64"
 
 
+def system_fast_order(gs_bytes, Mc):
+    """enqueue_solve's choice of k_extend128's workgroup order (rom_fem_solve.hip, `order`), restated: the system group varies
+    fastest when the segment-major extension tables (the planner's gstotal doubles) hold at least 64 MiB and the chunk has at
+    least 16 groups of 128 systems."""
+    return gs_bytes >= SYS_FAST_BYTES and (Mc + 127) // 128 >= SYS_FAST_GROUPS
+
+
 def narrow_routes(routes):
     """The routes of a sweep of fewer than 128 systems, from those of 129: no k_extend128, hence no fold."""
     swap = {"expand_folded": "expand", "extend_lr_128_row": "extend_lr_64", "extend_lr_128_flat": "extend_lr_64",
@@ -194,12 +215,16 @@ def per_system_workspace(n_tiles, nodal_begin, stride):
 
 def routes_of_profile(prof, n1, Mc, n_lr_blocks, expands):
     """Routes of ROUTES that one sweep of chunks of Mc systems took, from its profile {name: launches} (ROM_PROF labels;
-    under ROMHC_PROF_DETAIL the per-column kernels carry a _jNN suffix), the number of compressed blocks (ROMHC_VERBOSE
+    under ROMHC_PROF_DETAIL the per-column kernels carry a _jNN suffix and a k_extend128 launch in the system-fast order is
+    extend_lr_sysfast: extend_lr for everything else), the number of compressed blocks (ROMHC_VERBOSE
     prints it) and `expands`: whether a sweep of fewer than 128 systems of the same geometry -- which never folds --
     launched k_expand (a geometry with nothing to expand launches it nowhere: that is not a fold)."""
     names = {nm.split("_j")[0] if nm[-4:-2] == "_j" else nm for nm, n in prof.items() if n > 0}
     out = set(names & {"solve1", "rhs", "diag_update", "diag_factor", "factor_panel", "backsolve", "coef", "expand", "back_pre",
                        "edge_transform", "extend", "scatter_interface"})
+    if "extend_lr_sysfast" in names:
+        names = names - {"extend_lr_sysfast"} | {"extend_lr"}
+        out.add("extend_128_sys_fast")
     if "extend_lr" in names:
         t = extension_tiling(n1, Mc)
         out.add({"t64": "extend_lr_64", "row": "extend_lr_128_row", "flat": "extend_lr_128_flat"}[t])

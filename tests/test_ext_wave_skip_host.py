@@ -1,6 +1,7 @@
 """The per-wave K-segment skipping of k_extend128 on the CPU, under AddressSanitizer and UBSan: tests/c_abi/ext_wave_skip_check.cpp
 is a stand-alone program that plans 2x2 / N = 128 (row tiles), 3x3 / N = 64 (FLAT; an interior edge with thresholds 29 / 39 / 59),
-3x3 / N = 171 (FLAT, n1 = 170), 2x3 / N = 128 and 4x4 / N = 256 and calls x128_skip_counts (rom_fem_plan.h, the function the kernel
+3x3 / N = 171 (FLAT, n1 = 170), 2x3 / N = 128, 4x4 / N = 256 and the wide cases of tests/sweep_truth.py that have something to skip
+(2x2 / N = 171, 3x3 / N = 140, 2x2 / N = 250) and calls x128_skip_counts (rom_fem_plan.h, the function the kernel
 calls) for every tile, wave column and side: no vertex of a wave needs a segment in front of the wave's skip count, the wave's count
 is at least the tile's, and every geometry has a place where it is larger.  No GPU, nothing loaded into this process.
 
@@ -20,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXECUTED_TILE = {"2x2-N128": 15456, "3x3-N171": 99000, "4x4-N256": 463664}
 NEEDED_WAVE = {"2x2-N128": 13672, "3x3-N171": 87383, "4x4-N256": 420380}
 PLANNED_NEEDED = {"2x2-N128": 13676, "3x3-N171": 87400, "4x4-N256": 420700}
-TILING = {"2x2-N128": "row", "3x3-N64": "flat", "3x3-N171": "flat", "2x3-N128": "row", "4x4-N256": "row"}
+TILING = {"2x2-N128": "row", "3x3-N64": "flat", "3x3-N171": "flat", "2x3-N128": "row", "4x4-N256": "row",
+          "2x2-N171": "flat", "3x3-N140": "flat", "2x2-N250": "row"}      # (the last three: the wide cases of tests/sweep_truth.py)
 WAVE_OVER_TILE = {"2x2-N128": 0.931, "3x3-N64": 0.977, "3x3-N171": 0.917, "2x3-N128": 0.924}
 
 

@@ -29,4 +29,4 @@ def test_planner_is_clean_under_sanitizers(tmp_path):
     out, err = r.stdout.decode(), r.stderr.decode()
     assert r.returncode == 0, out + err
     assert err == "", err                      # no sanitizer report, no violation
-    assert len(out.splitlines()) == 16, out    # twelve geometries + four switches
+    assert len(out.splitlines()) == 20, out    # sixteen geometries + four switches

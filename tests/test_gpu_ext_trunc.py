@@ -7,7 +7,8 @@ distinct parameter vectors follow the pattern of the C4 workload of bench.py: al
 10^U(0, 8); system m carries a_{idx[m]} (tests/sweep_truth.py: idx_pattern), so rows of equal idx must be equal bit for bit
 wherever they sit, and one row per d is held against a reference:
   * 2x2 / N = 40 and 3x3 / N = 24: the SuperLU oracle, relative H^1_0 <= SNAP_TOL;
-  * 2x2 / N = 64, 3x3 / N = 64, 2x2 / N = 128: the 80-bit truth of tests/referee.py, relative H^1_0 in long double <= SNAP_TOL.
+  * 2x2 / N = 64, 3x3 / N = 64, 2x2 / N = 128, 2x2 / N = 171 (flat tiles inside one mesh row), 2x2 / N = 250 (two column tiles
+    per mesh row, the second ragged): the 80-bit truth of tests/referee.py, relative H^1_0 in long double <= SNAP_TOL.
 The two builds must agree row by row to SNAP_TOL.  Both distances are rounding-level numbers (a wrong cut shows as orders of
 magnitude); they are printed, and written as JSON lines to the file ROMHC_EXT_TRUNC_JSON names, if set (profiles/ext_trunc.json
 was recorded that way)."""
@@ -25,7 +26,8 @@ pytestmark = pytest.mark.gpu
 
 M = 130
 SNAP_TOL = st.SNAP_TOL
-CASES = [((2, 2), 40, "oracle"), ((3, 3), 24, "oracle"), ((2, 2), 64, "truth"), ((3, 3), 64, "truth"), ((2, 2), 128, "truth")]
+CASES = [((2, 2), 40, "oracle"), ((3, 3), 24, "oracle"), ((2, 2), 64, "truth"), ((3, 3), 64, "truth"), ((2, 2), 128, "truth"),
+         ((2, 2), 171, "truth"), ((2, 2), 250, "truth")]
 
 
 def parameters(blocks, N):

@@ -6,7 +6,9 @@ ROMHC_NO_EXT_WAVE_SKIP (every wave follows its tile's walk, zero half included: 
 with ROMHC_NO_EXT_TRUNC (no thresholds: nothing to skip but the zero half).  The parameters follow tests/test_gpu_ext_trunc.py.
   * 2x2 / N = 128: row tiles, every block with one side its mesh rows run away from;
   * 3x3 / N = 64: FLAT tiles, the centre block with four sides;
-  * 2x3 / N = 128.
+  * 2x3 / N = 128;
+  * 2x2 / N = 171: FLAT tiles that lie inside one mesh row (n1 = 170), whole tiles skipping segments of the sides their row ends at;
+  * 2x2 / N = 250: row tiles, two column tiles per mesh row, the second of 121 vertices (its fourth wave column partly filled).
 The skipped products are exact zeros added to sums that start at +0, so the rows with and without the skipping must be equal bit
 for bit.  For 2x2 / N = 128 one row per distinct parameter is held against the 80-bit truth of tests/referee.py: relative H^1_0 in
 long double <= SNAP_TOL (the rows of the library before the skipping sat at 3e-14 there)."""
@@ -22,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 M = 130
 SNAP_TOL = st.SNAP_TOL
-CASES = [((2, 2), 128), ((3, 3), 64), ((2, 3), 128)]
+CASES = [((2, 2), 128), ((3, 3), 64), ((2, 3), 128), ((2, 2), 171), ((2, 2), 250)]
 
 
 def parameters(blocks, N):

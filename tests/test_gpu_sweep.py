@@ -13,10 +13,13 @@ tests/sweep_truth.py, proved on the CPU by tests/test_sweep_truth_host.py).
 * M = 1 ... 257 on both sides of the pair of k_diag_update<2>, the four systems of a k_solve1 workgroup, every 64- and
   128-system tile and the Mc >= 128 switch, on a single-tile geometry and two tile Cholesky ones (general blocks; compressed
   blocks through k_extend128); 129 and a size below 128 on the others.
+* Blocks wider than one 128-vertex tile (sweep_truth.WIDE_CASES, n1 = 170 / 139 / 249 / 256): flat tiles inside one mesh row
+  with n1 even and odd, row tiles with two column tiles (the second ragged, or exactly full), the longer K walks of C4 and C5.
 * Product switches the product build takes by size: 2049 systems (k_diag_update<1>), a workspace limit of 70 systems, a
-  sweep of 700 after one of 256 on the same FE space (chunks of 256 + 256 + 188).
-* 257 all-different systems: the long-double residual of EVERY row, |r|_inf / (4 a_max |u|_inf) <= 1e-11 (the bound and
-  normalisation of test_full_size_c2_properties).
+  sweep of 700 after one of 256 on the same FE space (chunks of 256 + 256 + 188), 1921 systems of 3x3-N140 (tables of
+  66 MiB and 16 system groups: k_extend128 with the system group varying fastest).
+* 257 all-different systems (129 at dim 249 001): the long-double residual of EVERY row, |r|_inf / (4 a_max |u|_inf) <= 1e-11
+  (the bound and normalisation of test_full_size_c2_properties).
 * One indefinite system, first or last of five: ROM_ERR_NOT_SPD once, then ROM_OK and the same bits as before.
 * The same bits with ROMHC_POISON_WS=1 on a fresh FE space.
 * sweep_truth.ROUTES: tests/sweep_child.py confirms the route table from profile names in a child process;
@@ -216,6 +219,49 @@ def test_more_than_2048_systems(ctx, fems):
     RAN.add("big")
 
 
+def test_system_fast_order_gives_the_same_rows(ctx, fems):
+    """1921 systems of 3x3-N140 on a fresh FE space: 16 system groups (the last holds one system) over tables of 66.0 MiB, the
+    smallest switch to k_extend128's system-fast workgroup order (tests/sweep_child.py witnesses the order).  Placement only:
+    every row equals, bit for bit, the row of the same parameters of the classic-order sweep of 129 systems.  The block is
+    2.7 GB: it is filled with the sentinel and compared on the device, in slabs of 128 rows."""
+    case = st.CASE[st.SYS_FAST_CASE]
+    M, row0 = st.SYS_FAST_M, case.row0
+    assert M > max(case.Ms) and (M + 127) // 128 == st.SYS_FAST_GROUPS and M % 128 == 1
+    t0 = time.perf_counter()
+    ref = _reference_rows(ctx, fems, case)
+    D, dim = ref.shape
+    ref_d = ctx.upload(ref)
+    a_rows, idx = _batch(case, M)
+    assert st.check_idx(idx, M, D)
+    fem = _fresh(ctx, case)
+    assert dim == fem.dim
+    U = ctx.alloc((row0 + M + 2) * dim + 3)
+    U.fill(st.SENTINEL)
+    fem.solve_batch(ctx.upload(a_rows), M, U, row0=row0)
+    what = f"{case.id} M={M}"
+    front = U.download(n=row0 * dim).view(np.uint64)
+    behind = U.download(offset=(row0 + M) * dim).view(np.uint64)
+    assert front.size == row0 * dim and (front == st.SENT_BITS).all(), f"{what}: an entry in front of row {row0} changed"
+    assert behind.size == 2 * dim + 3 and (behind == st.SENT_BITS).all(), f"{what}: an entry behind row {row0 + M - 1} changed"
+    want = ctx.alloc(128 * dim)
+    bad = []
+    for m0 in range(0, M, 128):
+        n = min(128, M - m0)
+        want.gather_rows_from(ref_d, idx[m0:m0 + n], dim)
+        if not U.same_bits_as(want, n * dim, off=(row0 + m0) * dim):
+            got = U.download(n=n * dim, offset=(row0 + m0) * dim, shape=(n, dim))
+            eq = (got.view(np.uint64) == ref[idx[m0:m0 + n]].view(np.uint64)).all(axis=1)
+            bad += (m0 + np.flatnonzero(~eq)).tolist()
+    assert not bad, f"{what}: rows {bad[:12]} (of {len(bad)}) differ from the rows of the same parameters in the classic-order " \
+                    f"sweep of {max(case.Ms)} systems"
+    t = st.truths(case)
+    last = [int(np.flatnonzero(idx == d)[-1]) for d in range(D)]
+    err = [st.rel_h10_ld(t["g"], U.download(n=dim, offset=(row0 + m) * dim), t["truth"][d]) for d, m in enumerate(last)]
+    print(f"[sweep] {what}: {time.perf_counter() - t0:.2f} s")
+    observed(f"sweep {case.id} M={M} (system-fast order): one row per parameter vector vs 80-bit truth (rel H10)", err, st.SNAP_TOL)
+    RAN.add("sys_fast")
+
+
 @pytest.mark.parametrize("cid", st.CHUNK_CASES)
 def test_later_larger_sweep_reuses_the_workspace_in_chunks(ctx, fems, cid):
     """256 systems, then 700 on the same FE space: the second runs as 256 + 256 + 188.  The bits of an unchunked sweep of the
@@ -300,7 +346,7 @@ def test_sweep_reports_an_indefinite_system_once(ctx, fems, cid):
 # =====================================================================================================================
 # 6. poisoned workspace
 # =====================================================================================================================
-@pytest.mark.parametrize("cid", ["2x2-N16", "3x3-N24", "2x3-N40", "1x2-N128"])
+@pytest.mark.parametrize("cid", ["2x2-N16", "3x3-N24", "2x3-N40", "1x2-N128", "2x2-N171"])
 def test_poisoned_workspace_gives_the_same_bits(ctx, fems, cid, monkeypatch):
     """ROMHC_POISON_WS=1 fills the factor workspace of a fresh FE space with NaN patterns before its first sweep."""
     case = st.CASE[cid]
@@ -330,6 +376,12 @@ def test_routes_confirmed_by_profile_names():
         COVERED.update(rec["seen"], rec["seen_small"])
     assert "diag_update_single" in got["big"]["seen"] and got["big"]["launches"] == 1, got["big"]
     COVERED.add("diag_update_single")
+    fast = got["sys_fast"]        # the order is read from the label extend_lr_sysfast, which only that sweep may carry
+    assert "extend_128_sys_fast" in fast["seen"] and "extend_lr_sysfast" in fast["profile"] and "extend_lr" not in fast["profile"], fast
+    assert fast["M"] == st.SYS_FAST_M and fast["launches"] == 1, fast      # (one chunk: 16 system groups)
+    assert sorted(set(fast["seen"]) - {"extend_128_sys_fast"}) == sorted(st.CASE[st.SYS_FAST_CASE].routes), fast
+    assert not any("extend_lr_sysfast" in got[c.id]["profile"] + got[c.id]["profile_small"] for c in st.CASES)
+    COVERED.add("extend_128_sys_fast")
     for cid in st.CHUNK_CASES:
         for key in ("chunked", "chunk_reuse"):
             assert got[f"{key} {cid}"]["seen"] == [key], (cid, got[f"{key} {cid}"])
@@ -340,5 +392,5 @@ def test_routes_confirmed_by_profile_names():
 def test_route_table_is_covered():
     assert "_confirmed" in COVERED, "run the whole module: the child-process confirmation did not run"
     assert set(st.ROUTES) <= COVERED, sorted(set(st.ROUTES) - COVERED)
-    want = {"rows", "two_stage", "big", "chunk_reuse", "chunked", "distinct", "status", "poison"}
+    want = {"rows", "two_stage", "big", "sys_fast", "chunk_reuse", "chunked", "distinct", "status", "poison"}
     assert want <= RAN, f"run the whole module: {sorted(want - RAN)} did not run"
