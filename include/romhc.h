@@ -493,6 +493,25 @@ int rom_tree_destroy(rom_tree* h);
 int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, int64_t M, rom_buf* P, size_t p_off, int64_t ldp, int K, int r,
                 int t, int mode, int64_t* idx_host, double* dist2_host, double* info_host);
 
+/* ---- the polish of the library-based parameter estimation (romhighcontrast_amd/inverse.py::polish_parameters) ----------------
+ * Levenberg-Marquardt in theta = log a for  min ||p - G_r c(theta)||^2 + perp2,  c(theta) = (sum_q e^theta_q Ahat_q)^-1 bhat,
+ * for K queries from t starts each: the algorithm of polish_parameters (damping, acceptance, lambda schedule, eight trials, the
+ * `still`, `tiny` and rounding-level rules, `converged`) in reduced sensor coordinates: with the compact SVD diag(w) E^T = U S V^T
+ * of rank r, P (K rows of r from an element offset with a row stride) holds p = U^T (w y), Gr (r x n) = S V^T, and AUX (K x 2)
+ * per query perp2 = ||(I - U U^T)(w y)||^2 and scale = max|w y| (NULL: 0 and max|p|).  Ahat (k, n, n) compact, bhat (n),
+ * THETA0 (K, t, k) the starts, lo_host / hi_host (k each) the box.  One workgroup per (query, start) runs the whole iteration in
+ * one launch; a second kernel keeps the start of smallest misfit per query (the lowest index among equals).
+ * OUT row of query q (ldo >= k + n + 5 doubles apart, from out_off): theta (k) | c (n) | misfit = sqrt(|p - G_r c|^2 + perp2) |
+ * sigma_min of the final Jacobian (one-sided Jacobi on its k columns) | converged (0 / 1) | iterations | start.
+ * 1 <= n <= 64, 1 <= k <= 16, 1 <= r <= 64, 1 <= t <= 8: ROM_ERR_INVALID outside; K = 0 is a no-op; max_iter = 0 only evaluates
+ * the starts.  A non-positive pivot of A(theta) in a trial rejects the trial, at a start it is ROM_ERR_NOT_SPD.  No input buffer
+ * is modified; no floating-point atomics: the same bits on a repeated call.  One host synchronisation.
+ * info8_host (8 doubles or NULL): kernel launches, host synchronisations, bytes of workspace, systems K t, LM iterations executed,
+ * n x n factorisations executed (both summed on the device in integers), 0, 0. */
+int rom_lm_polish(rom_ctx* ctx, int n, int k, int r, rom_buf* Ahat, rom_buf* bhat, rom_buf* Gr, rom_buf* P, size_t p_off, int64_t ldp,
+                  int K, int t, rom_buf* THETA0, const double* lo_host, const double* hi_host, rom_buf* AUX, int max_iter,
+                  double misfit_tol, rom_buf* OUT, size_t out_off, int64_t ldo, double* info8_host);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

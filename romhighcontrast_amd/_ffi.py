@@ -128,6 +128,8 @@ PROTOTYPES = {
     "rom_poly_destroy": (C.c_int, [_vp]),
     "rom_nearest": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, C.c_int,
                               C.c_int, _vp, _vp, _vp]),
+    "rom_lm_polish": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp,
+                                _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_tree_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "rom_tree_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
@@ -349,6 +351,33 @@ class Context:
         d = dict(group_size=int(info[0]), groups_rescored=int(info[1]), certified=int(info[2]), fallbacks=int(info[3]),
                  launches=int(info[4]), host_syncs=int(info[5]), workspace_bytes=int(info[6]), executed_flops=float(info[7]))
         return idx, dist2, d
+
+    def lm_polish(self, n, k, r, Ahat: "Buffer", bhat: "Buffer", Gr: "Buffer", P: "Buffer", p_off, ldp, K, t, THETA0: "Buffer", lo, hi,
+                  AUX: "Buffer | None" = None, max_iter=30, misfit_tol=1e-3, OUT: "Buffer | None" = None, out_off=0, ldo=None):
+        """rom_lm_polish: inverse.polish_parameters on the device in reduced sensor coordinates (P: K rows p = U^T (w y) of r
+        columns, Gr (r, n) = S V^T, AUX (K, 2) = perp2, scale or None), from the t starts THETA0 (K, t, k) per query inside the
+        box [lo, hi].  OUT (rows of ldo >= k + n + 5 from out_off) is allocated when None; the coefficients stay in it at column
+        k.  Returns (PolishResult, info dict)."""
+        from .inverse import PolishResult
+        n, k, K = int(n), int(k), int(K)
+        ldo = k + n + 5 if ldo is None else int(ldo)
+        lo = _host(np.broadcast_to(np.asarray(lo, dtype=np.float64), (k,)))
+        hi = _host(np.broadcast_to(np.asarray(hi, dtype=np.float64), (k,)))
+        if OUT is None and K > 0:
+            OUT = self.alloc(int(out_off) + K * ldo)
+        info = np.zeros(8)
+        check(self.lib.rom_lm_polish(self.h, n, k, int(r), Ahat.h, bhat.h, Gr.h, P.h if P is not None else None, int(p_off), int(ldp), K,
+                                     int(t), THETA0.h if THETA0 is not None else None, lo.ctypes.data, hi.ctypes.data,
+                                     AUX.h if AUX is not None else None, int(max_iter), float(misfit_tol),
+                                     OUT.h if OUT is not None else None, int(out_off), ldo, info.ctypes.data))
+        rows = np.zeros((K, ldo))
+        if K:   # (the last row may end with the buffer, k + n + 5 doubles in)
+            rows.reshape(-1)[:(K - 1) * ldo + k + n + 5] = OUT.download((K - 1) * ldo + k + n + 5, offset=int(out_off))
+        res = PolishResult(rows[:, :k].copy(), rows[:, k + n].copy(), rows[:, k:k + n].copy(), rows[:, k + n + 2] != 0.0,
+                           rows[:, k + n + 3].astype(np.int64), rows[:, k + n + 1].copy(), rows[:, k + n + 4].astype(np.int64))
+        d = dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), systems=int(info[3]),
+                 iterations=int(info[4]), factorisations=int(info[5]))
+        return res, d
 
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):
         check(self.lib.rom_symmetric_orthonormalize(self.h, V.h, v_row0, n, dim))

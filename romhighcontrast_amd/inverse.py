@@ -5,7 +5,7 @@ rows are snapshots, they amplify measurement noise by cond(E) and say nothing ab
 Here the parameters are SEARCHED: ``rom_resid_eval`` solves the Galerkin ROM for M library parameters in one call and leaves
 their coordinates COEF (M x n) on the device; for K measurement vectors ``rom_nearest`` finds the library states that explain
 them best (the K x M misfits never exist), and a Gauss-Newton / Levenberg-Marquardt polish on the host (n x n systems,
-batched over the queries) refines the parameters from the best library entries.  Works for any basis.
+batched over the queries; with polish="device" on the GPU, ``rom_lm_polish``) refines the best library entries.  Any basis.
 
     lib = ParameterLibrary(sm, basis, a_library).observe(points)
     est = lib.estimate(measurements)           # ParameterEstimate
@@ -133,6 +133,55 @@ def polish_parameters(Ahat, bhat, E, Y, theta0, lo, hi, weights=None, max_iter=3
     return PolishResult(theta[pick], misfit[pick], c[pick], conv[pick], iterations[pick], sig[pick], best)
 
 
+LM_LIMITS = dict(n=64, k=16, r=64, t=8)   # rom_lm_polish (csrc/rom_lm.hip)
+
+
+def _check_lm_limits(n, k, r, t):
+    for name, v in (("n", n), ("k", k), ("r", r), ("t", t)):
+        if not 1 <= v <= LM_LIMITS[name]:
+            raise ValueError(f"the device polish (rom_lm_polish) needs 1 <= {name} <= {LM_LIMITS[name]}, got {name} = {v}: "
+                             "use polish=True (the host polish)")
+
+
+def reduce_sensors(E, weights=None, rel=1e-12):
+    """The compact SVD diag(w) E^T = U S V^T truncated at sigma > rel sigma_1: (U (m, r), G_r = S V^T (r, n), V S (n, r))."""
+    E = np.asarray(E, dtype=np.float64)
+    w = np.ones(E.shape[1]) if weights is None else np.asarray(weights, dtype=np.float64)
+    U, S, Vt = np.linalg.svd(w[:, None] * E.T, full_matrices=False)
+    r = max(1, int(np.sum(S > rel * S[0])))
+    return np.ascontiguousarray(U[:, :r]), np.ascontiguousarray(S[:r, None] * Vt[:r]), np.ascontiguousarray(Vt[:r].T * S[:r])
+
+
+def reduce_measurements(U, Y, weights):
+    """p = U^T (w y) (K, r) and aux (K, 2) = (perp2 = |(I - U U^T)(w y)|^2, scale = max|w y|) of the rows of Y."""
+    Yw = Y * weights[None, :]
+    Pq = np.ascontiguousarray(Yw @ U)
+    perp = Yw - Pq @ U.T
+    scale = np.maximum(np.abs(Yw).max(axis=1), np.finfo(float).tiny) if Yw.shape[1] else np.full(len(Yw), np.finfo(float).tiny)
+    return Pq, np.ascontiguousarray(np.stack([np.einsum("km,km->k", perp, perp), scale], axis=1))
+
+
+def polish_parameters_device(ctx, Ahat, bhat, E, Y, theta0, lo, hi, weights=None, max_iter=30, misfit_tol=1e-3) -> PolishResult:
+    """``polish_parameters`` on the device of ``ctx`` (``rom_lm_polish``, one workgroup per (query, start)): the same arguments
+    and the same result.  The sensors are reduced on the host first -- diag(w) E^T = U S V^T, p = U^T (w y), G_r = S V^T -- so
+    the kernel works on r <= min(n, m) rows; the part of w y outside the range of U enters the misfit as a constant."""
+    Ahat, bhat, E = np.asarray(Ahat, dtype=np.float64), np.asarray(bhat, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+    K, m = Y.shape
+    k, n = Ahat.shape[0], Ahat.shape[1]
+    theta0 = np.asarray(theta0, dtype=np.float64).reshape(K, -1, k)
+    t = theta0.shape[1]
+    w = np.ones(m) if weights is None else np.asarray(weights, dtype=np.float64)
+    U, Gr, _ = reduce_sensors(E, w)
+    r = U.shape[1]
+    _check_lm_limits(n, k, r, t)
+    Pq, aux = reduce_measurements(U, Y, w)
+    res, _ = ctx.lm_polish(n, k, r, ctx.upload(Ahat), ctx.upload(bhat), ctx.upload(Gr), ctx.upload(Pq) if K else None, 0, r, K, t,
+                           ctx.upload(theta0) if K else None, lo, hi, AUX=ctx.upload(aux) if K else None, max_iter=max_iter,
+                           misfit_tol=misfit_tol)
+    return res
+
+
 class ParameterLibrary:
     """The Galerkin ROM on ``basis`` solved for the M parameters ``a_library`` (one ``rom_resid_eval`` call over all of them):
     their coordinates COEF (M, n) in the A_1-orthonormal basis stay on the device, ``.a`` (M, k), ``.residual`` and ``.upper``
@@ -174,10 +223,11 @@ class ParameterLibrary:
         VS = np.ascontiguousarray(Vt[:r].T * S[:r])
         self.Qc = ctx.alloc(self.M * r)
         ctx.gemm_nn(self.M, r, self.n, self.COEF, 0, self.n, ctx.upload(VS), 0, r, self.Qc, 0, r)
+        self.Gr = ctx.upload(np.ascontiguousarray(S[:r, None] * Vt[:r]))    # G_r = S V^T (r, n): the device polish
         return self
 
-    def search(self, measurements, t=4, mode=0):
-        """The t library rows of smallest misfit per measurement vector: (idx (K, t), misfit (K, t), info of rom_nearest)."""
+    def _search(self, measurements, t, mode):
+        """``search`` and what it uploaded: (idx, misfit, info, the device buffer of Pq = U^T (w y) (K, r) or None, Yw, perp2)."""
         if self.points is None:
             raise RuntimeError("ParameterLibrary.observe(points) comes first")
         Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
@@ -186,18 +236,60 @@ class ParameterLibrary:
         perp = Yw - Pq @ self.U.T
         t = min(int(t), self.M)
         ctx = self.sm._ctx
-        idx, d2, info = ctx.nearest(self.Qc, 0, self.r, self.M, ctx.upload(Pq) if len(Y) else None, 0, self.r, len(Y), self.r, t=t,
-                                    mode=mode)
-        return idx, np.sqrt(d2 + np.einsum("km,km->k", perp, perp)[:, None]), info
+        Pq_dev = ctx.upload(Pq) if len(Y) else None
+        idx, d2, info = ctx.nearest(self.Qc, 0, self.r, self.M, Pq_dev, 0, self.r, len(Y), self.r, t=t, mode=mode)
+        perp2 = np.einsum("km,km->k", perp, perp)
+        return idx, np.sqrt(d2 + perp2[:, None]), info, Pq_dev, Yw, perp2
+
+    def search(self, measurements, t=4, mode=0):
+        """The t library rows of smallest misfit per measurement vector: (idx (K, t), misfit (K, t), info of rom_nearest)."""
+        return self._search(measurements, t, mode)[:3]
+
+    def _estimate_device(self, Y, idx, Pq_dev, Yw, perp2, la, states, max_iter, misfit_tol):
+        """The device polish from the library rows idx (K, t): (PolishResult, DeviceArray of the lifted states or None).  The
+        queries Pq are the buffer the search uploaded; the coefficients are lifted from the result rows on the device."""
+        sm, ctx = self.sm, self.sm._ctx
+        K, t, k, n = len(Y), idx.shape[1], self.a.shape[1], self.n
+        _check_lm_limits(n, k, self.r, t)
+        if getattr(self, "_lm_model", None) is None:
+            self._lm_model = (ctx.upload(self.Ahat), ctx.upload(self.bhat))
+        ldo = k + n + 5
+        OUT = ctx.alloc(max(K * ldo, 1))
+        scale = np.maximum(np.abs(Yw).max(axis=1), np.finfo(float).tiny) if K else np.zeros(0)
+        res, _ = ctx.lm_polish(n, k, self.r, self._lm_model[0], self._lm_model[1], self.Gr, Pq_dev, 0, self.r, K, t,
+                               ctx.upload(la[idx]) if K else None, la.min(axis=0), la.max(axis=0),
+                               AUX=ctx.upload(np.stack([perp2, scale], axis=1)) if K else None, max_iter=max_iter,
+                               misfit_tol=misfit_tol, OUT=OUT, ldo=ldo)
+        S = None
+        if states:
+            dim = sm.vspace_dim
+            out = ctx.alloc(max(K * dim, 1))
+            if K:
+                ctx.gemm_nn(K, dim, n, OUT, k, ldo, self._W, 0, dim, out, 0, dim)
+            S = DeviceArray(out, K, dim)
+        return res, S
 
     def estimate(self, measurements, t=4, polish=True, states=False, max_iter=30, misfit_tol=1e-3) -> ParameterEstimate:
         """Parameters for the K measurement vectors (K, m): the search, then (``polish``) Levenberg-Marquardt in log a from
-        each of the t library entries found, inside the library's box; without the polish the nearest library entry."""
+        each of the t library entries found, inside the library's box; without the polish the nearest library entry.
+        ``polish="device"`` runs the polish on the GPU (``rom_lm_polish``; ValueError outside its limits n <= 64, k <= 16,
+        r <= 64, t <= 8), ``polish=True`` on the host."""
         sm, ctx = self.sm, self.sm._ctx
         Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
         K = len(Y)
-        idx, start_misfit, _ = self.search(Y, t=t)
+        if isinstance(polish, str) and polish != "device":
+            raise ValueError(f'polish = {polish!r}: True (host), False or "device"')
+        if isinstance(polish, str):
+            if self.points is None:
+                raise RuntimeError("ParameterLibrary.observe(points) comes first")
+            _check_lm_limits(self.n, self.a.shape[1], self.r, min(int(t), self.M))
+        idx, start_misfit, _, Pq_dev, Yw, perp2 = self._search(Y, t, 0)
         la = np.log(self.a)
+        if isinstance(polish, str):
+            res, S = self._estimate_device(Y, idx, Pq_dev, Yw, perp2, la, states, max_iter, misfit_tol)
+            a = np.exp(res.theta)
+            return ParameterEstimate(a.reshape((K,) + tuple(sm.blocks_geometry)), res.misfit, idx, start_misfit, res.converged,
+                                     res.iterations, res.sigma_min, res.coefficients, self.estimator.bound(a, n=self.n), S)
         starts = la[idx] if polish else la[idx[:, :1]]
         res = polish_parameters(self.Ahat, self.bhat, self.E, Y, starts, la.min(axis=0), la.max(axis=0), weights=self.weights,
                                 max_iter=max_iter if polish else 0, misfit_tol=misfit_tol)
