@@ -512,6 +512,31 @@ int rom_lm_polish(rom_ctx* ctx, int n, int k, int r, rom_buf* Ahat, rom_buf* bha
                   int K, int t, rom_buf* THETA0, const double* lo_host, const double* hi_host, rom_buf* AUX, int max_iter,
                   double misfit_tol, rom_buf* OUT, size_t out_off, int64_t ldo, double* info8_host);
 
+/* ---- sensor state estimation on the polynomial manifold (src/experiments/NonLinearROM.py:54-70, src/lib/ReducedBasis.py:65-70) ----
+ * The decoder of a fitted rom_poly map, u(z) = mean + z V_known + g(z) V_unknown (the model of src/experiments/NonLinearROM.py:54-70),
+ * fitted to point measurements instead of being given its known coordinates: the nonlinear counterpart of the linear state
+ * estimation of src/lib/ReducedBasis.py:65-70.  With t = (z - c) / h and phi(t) the P = C(m + d, d) Legendre products of the map
+ * (terms in rom_poly_terms order) the sensor image of the decoder is S phi(t); with the compact SVD diag(w) S = U Sigma V^T of
+ * rank r, P (K rows of r from an element offset with a row stride) holds p = U^T (w y), Gr (r x P row-major) = Sigma V^T, and AUX
+ * (K x 2) per query perp2 = ||(I - U U^T)(w y)||^2 and scale = max|w y| (NULL: 0 and max|p|).  Per query and start
+ *     min over lo <= t <= hi of ||p - G_r phi(t)||^2 + perp2
+ * by the Levenberg-Marquardt of rom_lm_polish (damping, acceptance, lambda schedule, eight trials, the `still`, `tiny` and
+ * rounding-level rules, `converged`) with J = -G_r d phi / d t; romhighcontrast_amd/nonlinear.py::sense_scores is the same
+ * algorithm on the host.  The residual p - G_r phi(t) and its squared norm are formed in double-double arithmetic and rounded once.  T0 (K, t, m) the starts, lo_host / hi_host (m each) the box; a coordinate with lo_j == hi_j is PINNED:
+ * it stays at its clipped start bit for bit and has no column in J^T J or in the J whose sigma_min is reported.  One workgroup
+ * per (query, start) runs the whole iteration in one launch (G_r d phi on fp64 MFMA); a second kernel keeps the start of smallest
+ * misfit per query (the lowest index among equals).
+ * OUT row of query q (ldo >= m + 5 doubles apart, from out_off): t (m) | misfit = sqrt(|p - G_r phi(t)|^2 + perp2) | sigma_min of
+ * the final Jacobian's free columns (one-sided Jacobi; 0 when every coordinate is pinned) | converged (0 / 1) | iterations | start.
+ * 1 <= m <= 16, 1 <= d <= 8, P <= 96, 1 <= r <= 96, 1 <= t <= 8: ROM_ERR_INVALID outside; K = 0 is a no-op; max_iter = 0 only
+ * evaluates the clipped starts.  NaN / Inf in Gr, P or T0: ROM_ERR_INVALID.  A non-positive pivot of the damped system rejects
+ * that trial.  No input buffer is modified; no floating-point atomics: the same bits on a repeated call.  One host synchronisation.
+ * info8_host (8 doubles or NULL): kernel launches, host synchronisations, bytes of workspace, systems K t, LM iterations executed,
+ * feature evaluations executed (both summed on the device in integers), 0, 0. */
+int rom_poly_sense(rom_ctx* ctx, int m, int d, int r, rom_buf* Gr, rom_buf* P, size_t p_off, int64_t ldp, int K, int t, rom_buf* T0,
+                   const double* lo_host, const double* hi_host, rom_buf* AUX, int max_iter, double misfit_tol, rom_buf* OUT,
+                   size_t out_off, int64_t ldo, double* info8_host);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

@@ -130,6 +130,8 @@ PROTOTYPES = {
                               C.c_int, _vp, _vp, _vp]),
     "rom_lm_polish": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp,
                                 _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
+    "rom_poly_sense": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                 C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_tree_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "rom_tree_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
@@ -378,6 +380,33 @@ class Context:
         d = dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), systems=int(info[3]),
                  iterations=int(info[4]), factorisations=int(info[5]))
         return res, d
+
+    def poly_sense(self, m, d, r, Gr: "Buffer", P: "Buffer", p_off, ldp, K, t, T0: "Buffer", lo, hi, AUX: "Buffer | None" = None,
+                   max_iter=30, misfit_tol=1e-3, OUT: "Buffer | None" = None, out_off=0, ldo=None):
+        """rom_poly_sense: nonlinear.sense_scores on the device (Gr (r, P) = Sigma V^T of the sensing matrix, the terms of
+        ``poly_terms(m, d)``; P: K rows p = U^T (w y) of r columns; AUX (K, 2) = perp2, scale or None), from the t starts T0
+        (K, t, m) per query inside the box [lo, hi]; lo_j == hi_j pins coordinate j.  OUT (rows of ldo >= m + 5 from out_off) is
+        allocated when None.  Returns (SenseResult, info dict)."""
+        from .nonlinear import SenseResult
+        m, K = int(m), int(K)
+        ldo = m + 5 if ldo is None else int(ldo)
+        lo = _host(np.broadcast_to(np.asarray(lo, dtype=np.float64), (m,)))
+        hi = _host(np.broadcast_to(np.asarray(hi, dtype=np.float64), (m,)))
+        if OUT is None and K > 0:
+            OUT = self.alloc(int(out_off) + K * ldo)
+        info = np.zeros(8)
+        check(self.lib.rom_poly_sense(self.h, m, int(d), int(r), Gr.h, P.h if P is not None else None, int(p_off), int(ldp), K, int(t),
+                                      T0.h if T0 is not None else None, lo.ctypes.data, hi.ctypes.data,
+                                      AUX.h if AUX is not None else None, int(max_iter), float(misfit_tol),
+                                      OUT.h if OUT is not None else None, int(out_off), ldo, info.ctypes.data))
+        rows = np.zeros((K, ldo))
+        if K:   # (the last row may end with the buffer, m + 5 doubles in)
+            rows.reshape(-1)[:(K - 1) * ldo + m + 5] = OUT.download((K - 1) * ldo + m + 5, offset=int(out_off))
+        res = SenseResult(rows[:, :m].copy(), rows[:, m].copy(), rows[:, m + 2] != 0.0, rows[:, m + 3].astype(np.int64),
+                          rows[:, m + 1].copy(), rows[:, m + 4].astype(np.int64))
+        d8 = dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), systems=int(info[3]),
+                  iterations=int(info[4]), evaluations=int(info[5]))
+        return res, d8
 
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):
         check(self.lib.rom_symmetric_orthonormalize(self.h, V.h, v_row0, n, dim))

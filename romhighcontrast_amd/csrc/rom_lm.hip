@@ -11,7 +11,7 @@
 // the default 64 KB of dynamic LDS, no opt-in.
 // Every control decision is taken by all threads from the same LDS values: control flow is uniform within a workgroup (every
 // __syncthreads is reached by all 256 threads) and free between workgroups.  Every loop is bounded by max_iter, LM_TRIALS, n, k,
-// r or LM_SWEEPS; nothing waits on another workgroup.  No floating-point atomics: a repeated call returns the same bits.
+// r or LMS_SWEEPS; nothing waits on another workgroup.  No floating-point atomics: a repeated call returns the same bits.
 //
 // A(theta) is factored as L D L^T without pivoting (the elimination order of k_reduced_solve, rom_ops.hip); the solves keep a
 // right-hand side in the registers of one wave, lane = row.  The factor in LDS is that of the CURRENT theta whenever an iteration
@@ -24,13 +24,13 @@
 #include <type_traits>
 
 #include "rom_basis_int.h"
+#include "rom_lm_small.h"
 
 namespace {
 
 constexpr int LM_NMAX = 64, LM_KMAX = 16, LM_RMAX = 64, LM_TMAX = 8;
 constexpr int LM_TRIALS = 8;     // py:101
-constexpr int LM_SWEEPS = 30;    // bound of the Jacobi sweeps (k <= 16 columns converge in under 10)
-constexpr int LM_THREADS = 256;
+constexpr int LM_THREADS = LMS_THREADS;
 constexpr double LM_NAN = __builtin_nan("");
 
 struct LmBox {
@@ -73,73 +73,6 @@ struct LmLds {
   }
 };
 enum { S_FN = 0, S_MOVED = 1, S_MAXNEW = 2, S_OKA = 3, S_OKH = 4 };
-
-__device__ __forceinline__ double wave_sum(double v) {   // (the butterfly leaves the same bits in every lane)
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_nan(double v) {   // NaN wins, as in numpy's max
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const double o = __shfl_xor(v, m, 64);
-    v = (o > v || o != o) ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ double group16_sum(double v) {
-  v += __shfl_xor(v, 8, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 1, 64);
-  return v;
-}
-
-// L D L^T in place on the lower triangle, all 256 threads: afterwards M[r][c] = l_rc d_c (c < r), M[j][j] = d_j, invd[j] = 1 / d_j.
-// Wave w takes the rows j + 1 + w, + 4, ..; a lane takes column j + 1 + lane (n <= 64).  *flag = 1.0 iff every pivot is > 0.
-__device__ bool lm_factor(double* M, int ld, int n, double* invd, double* flag) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int j = 0; j < n - 1; ++j) {
-    const double inv = 1.0 / M[j * ld + j];
-    const int c = j + 1 + lane;
-    if (c < n) {
-      const double lc = M[c * ld + j] * inv;
-      for (int r = j + 1 + w; r < n; r += 4)
-        if (c <= r) M[r * ld + c] -= M[r * ld + j] * lc;
-    }
-    __syncthreads();   // column j + 1 is final; step j wrote nothing that it read (it reads column j, writes columns > j)
-  }
-  if (tid < 64) {
-    bool good = true;
-    if (lane < n) {
-      const double d = M[lane * ld + lane];
-      good = d > 0.0;
-      invd[lane] = 1.0 / d;
-    }
-    const unsigned long long bad = __ballot(!good);
-    if (lane == 0) *flag = bad ? 0.0 : 1.0;
-  }
-  __syncthreads();
-  return *flag != 0.0;
-}
-
-// x = (L D L^T)^-1 b for NR right-hand sides held by one wave, lane = row
-template <int NR>
-__device__ __forceinline__ void lm_solve(const double* M, int ld, int n, const double* invd, double (&b)[NR], int lane) {
-  for (int j = 0; j < n - 1; ++j) {
-    const double l = (lane > j && lane < n) ? M[lane * ld + j] * invd[j] : 0.0;
-#pragma unroll
-    for (int u = 0; u < NR; ++u) b[u] = fma(-l, __shfl(b[u], j, 64), b[u]);
-  }
-  const double di = lane < n ? invd[lane] : 0.0;
-#pragma unroll
-  for (int u = 0; u < NR; ++u) b[u] *= di;
-  for (int j = n - 1; j > 0; --j) {
-    const double l = lane < j ? M[j * ld + lane] * invd[lane] : 0.0;
-#pragma unroll
-    for (int u = 0; u < NR; ++u) b[u] = fma(-l, __shfl(b[u], j, 64), b[u]);
-  }
-}
 
 struct LmSys {
   const LmArgs& a;
@@ -258,37 +191,8 @@ struct LmSys {
     __syncthreads();
   }
 
-  // the smallest singular value of J_r (Js is overwritten): one-sided Jacobi on its k columns, wave 0, lane = row.  Every lane
-  // holds the same alpha, beta, gamma (wave_sum), so the wave's control flow is uniform.
-  __device__ double sigma_min_wave0(int lane) {
-    const int k = a.k, r = a.r;
-    double* Js = sm + m.Js;
-    for (int sweep = 0; sweep < LM_SWEEPS; ++sweep) {
-      bool rotated = false;
-      for (int p = 0; p < k - 1; ++p)
-        for (int q = p + 1; q < k; ++q) {
-          const double x = lane < r ? Js[p * m.ldr + lane] : 0.0, y = lane < r ? Js[q * m.ldr + lane] : 0.0;
-          const double alpha = wave_sum(x * x), beta = wave_sum(y * y), gamma = wave_sum(x * y);
-          if (!(alpha > 0.0 && beta > 0.0) || !(fabs(gamma) > 2.220446049250313e-16 * sqrt(alpha) * sqrt(beta))) continue;
-          rotated = true;
-          const double zeta = (beta - alpha) / (2.0 * gamma);
-          const double tn = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double cs = 1.0 / sqrt(1.0 + tn * tn), sn = cs * tn;
-          if (lane < r) {
-            Js[p * m.ldr + lane] = cs * x - sn * y;
-            Js[q * m.ldr + lane] = sn * x + cs * y;
-          }
-        }
-      if (!rotated) break;
-    }
-    double smin = __builtin_huge_val();
-    for (int q = 0; q < k; ++q) {
-      const double x = lane < r ? Js[q * m.ldr + lane] : 0.0;
-      const double s = sqrt(wave_sum(x * x));
-      smin = (s < smin || s != s) ? s : smin;
-    }
-    return smin;
-  }
+  // the smallest singular value of J_r (Js is overwritten): one-sided Jacobi on its k columns, wave 0, lane = row
+  __device__ double sigma_min_wave0(int lane) { return lm_sigma_min_wave<1>(sm + m.Js, m.ldr, a.k, a.r, lane); }
 };
 
 __global__ __launch_bounds__(LM_THREADS) void k_lm_polish(const LmArgs a, const LmBox box) {
@@ -426,25 +330,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_lm_polish(const LmArgs a, const 
   }
 }
 
-// py:130-133: per query the start of smallest misfit (the lowest index among equals, the first NaN if there is one: numpy.argmin);
-// one wave per query copies that system's row and appends the start
-__global__ __launch_bounds__(64) void k_lm_select(const double* __restrict__ W, int ldw, int t, int mcol, double* __restrict__ OUT, long long ldo) {
-  const long long q = blockIdx.x;
-  const int lane = threadIdx.x;
-  int best = 0;
-  double bm = W[size_t(q * t) * ldw + mcol];
-  for (int s = 1; s < t; ++s) {
-    const double v = W[size_t(q * t + s) * ldw + mcol];
-    if (bm == bm && (v < bm || v != v)) {
-      bm = v;
-      best = s;
-    }
-  }
-  const double* row = W + size_t(q * t + best) * ldw;
-  double* o = OUT + q * ldo;
-  for (int e = lane; e < ldw; e += 64) o[e] = row[e];
-  if (lane == 0) o[ldw] = double(best);
-}
+// py:130-133: per query the start of smallest misfit: k_lm_select (rom_lm_small.h)
 
 }  // namespace
 

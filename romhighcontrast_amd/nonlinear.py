@@ -10,6 +10,7 @@ stay scikit-learn's.  The plots and the PerplexityLab LabPipeline driver of the 
 from __future__ import annotations
 
 from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -17,7 +18,8 @@ from .lib.ReducedBasis import pca_tall
 from .lib.SolutionsManagers import DeviceArray, SolutionsManagerFEM
 
 __all__ = ["ZERO", "Bounds", "MWhere", "draw_parameters", "vn_family_sampler", "do_pca", "get_known_unknown_indexes",
-           "learn_eigenvalues", "PolynomialMap", "TreeMap", "ForestMap", "learn_eigenvalues_device", "nonlinear_reconstruction"]
+           "learn_eigenvalues", "PolynomialMap", "TreeMap", "ForestMap", "learn_eigenvalues_device", "nonlinear_reconstruction", "SenseResult", "SensingEstimate", "legendre_table",
+           "legendre_features", "sensing_matrix", "sense_scores", "PolynomialSensing"]
 
 ZERO = 1e-15
 Bounds = namedtuple("Bounds", "lower upper")
@@ -277,3 +279,302 @@ def nonlinear_reconstruction(pca, poly, known_scores, known_start=0, unknown_sta
     ctx.gemm_nn(K, dim, q, pred, 0, q, Vd.buf, unknown_start * dim, dim, U, 0, dim, alpha=1.0, beta=1.0)
     out = DeviceArray(U, K, dim)
     return out.numpy() if download else out
+
+
+# ---- sensor state estimation on the polynomial manifold: rom_poly_sense ---------------------------------------------------
+
+
+class SenseResult(NamedTuple):
+    """``sense_scores`` / ``Context.poly_sense``: t (K, m) the scaled known coordinates, misfit (K,) = sqrt(|p - G_r phi(t)|^2 +
+    perp2), converged and iterations (K,), sigma_min (K,) of the final Jacobian's free columns, start (K,) the start that won."""
+    t: np.ndarray
+    misfit: np.ndarray
+    converged: np.ndarray
+    iterations: np.ndarray
+    sigma_min: np.ndarray
+    start: np.ndarray
+
+
+class SensingEstimate(NamedTuple):
+    """``PolynomialSensing.estimate``: known_scores (K, m) = c + h t and predicted_scores (K, q) = the map at them; misfit,
+    converged, iterations, sigma_min, start (K,) of the nonlinear least squares (``SenseResult``); linear_scores (K, m): the
+    least-squares estimate on the m known modes alone; states: DeviceArray (K, dim) of the decoded states, or None."""
+    known_scores: np.ndarray
+    predicted_scores: np.ndarray
+    misfit: np.ndarray
+    converged: np.ndarray
+    iterations: np.ndarray
+    sigma_min: np.ndarray
+    start: np.ndarray
+    linear_scores: np.ndarray
+    states: Optional[DeviceArray]
+
+
+def legendre_table(t, d):
+    """L_k(t) and L'_k(t), k = 0 .. d, of every entry of t: two arrays t.shape + (d + 1,), in t's dtype.  The recurrences of
+    rom_poly.hip and rom_sense.hip: (k + 1) L_{k+1} = (2k + 1) t L_k - k L_{k-1};  L'_{k+1} = L'_{k-1} + (2k + 1) L_k."""
+    t = np.asarray(t)
+    L, D = [np.ones_like(t), t], [np.zeros_like(t), np.ones_like(t)]
+    for k in range(1, int(d)):
+        L.append(((2 * k + 1) * t * L[k] - k * L[k - 1]) / (k + 1))
+        D.append(D[k - 1] + (2 * k + 1) * L[k])
+    return np.stack(L[:d + 1], axis=-1), np.stack(D[:d + 1], axis=-1)
+
+
+def legendre_features(t, powers, jacobian=True):
+    """phi (B, P) and d phi / d t (B, P, m) (None unless ``jacobian``) at the rows of t (B, m) for the exponent rows ``powers``
+    (P, m) (``_ffi.poly_terms``): phi_p = prod_j L_{powers[p, j]}(t_j), the factors taken in the order of j."""
+    t = np.asarray(t)
+    powers = np.asarray(powers, dtype=np.int64)
+    m = powers.shape[1]
+    d = max(int(powers.max()) if powers.size else 0, 1)
+    L, D = legendre_table(t, d)                        # (B, m, d + 1)
+    cols = np.arange(m)[None, :]
+    sel = L[:, cols, powers]                           # (B, P, m)
+    F = sel.prod(axis=-1)
+    if not jacobian:
+        return F, None
+    dsel = D[:, cols, powers]
+    dF = np.empty(sel.shape, dtype=sel.dtype)
+    for j in range(m):
+        s = sel.copy()
+        s[:, :, j] = dsel[:, :, j]
+        dF[:, :, j] = s.prod(axis=-1)
+    return F, dF
+
+
+def sensing_matrix(e0, Ek, Eu, c, h, W, powers):
+    """S (ms, P) with  l(mean + z V_known + g(z) V_unknown) = S phi(t),  z = c + h t,  g = W phi:  S = E_u W, plus e0 + E_k c on
+    the column of the constant term and h_j E_k[:, j] on the column of the term t_j.  e0 (ms,) = l(mean), Ek (ms, m) and Eu
+    (ms, q) = l(known / predicted components), c, h (m,) and W (q, P) of the fitted map, powers (P, m)."""
+    e0, Ek, Eu = np.asarray(e0, dtype=np.float64), np.asarray(Ek, dtype=np.float64), np.asarray(Eu, dtype=np.float64)
+    c, h, W = np.asarray(c, dtype=np.float64), np.asarray(h, dtype=np.float64), np.asarray(W, dtype=np.float64)
+    powers = np.asarray(powers, dtype=np.int64)
+    S = Eu @ W
+    degree = powers.sum(axis=1)
+    S[:, int(np.flatnonzero(degree == 0)[0])] += e0 + Ek @ c
+    for j in range(len(c)):
+        p = int(np.flatnonzero((degree == 1) & (powers[:, j] == 1))[0])
+        S[:, p] += h[j] * Ek[:, j]
+    return S
+
+
+SENSE_LIMITS = dict(m=16, d=8, P=96, r=96, t=8)   # rom_poly_sense (csrc/rom_sense.hip)
+_SENSE_CHUNK = 4096                                # systems of one batch of the host iteration
+
+
+def _check_sense_limits(m, d, P, r, t):
+    for name, v in (("m", m), ("d", d), ("P", P), ("r", r), ("t", t)):
+        if not 1 <= v <= SENSE_LIMITS[name]:
+            raise ValueError(f"the device estimate (rom_poly_sense) needs 1 <= {name} <= {SENSE_LIMITS[name]}, got {name} = {v}: "
+                             "use device=False (the host iteration)")
+
+
+def _residual(Gr, y, F):
+    """rho = y - F G_r^T (B, r) and f = |rho|^2 (B,), both formed in long double and rounded to fp64.  Off the manifold |rho| is a
+    few percent of |G_r phi|: in plain fp64 the rounding of G_r phi and of the sum of squares puts noise of eps |rho| |G_r phi|
+    on f, the acceptance f_new < f is decided by rounding once a step gains less than that, and the final t is reproducible to
+    1e-9 only -- correctly rounded, to a few 1e-11 (rom_sense.hip does the same in double-double arithmetic).  Where long double
+    is fp64 this is the plain fp64 residual."""
+    LD = np.longdouble
+    rho = (y.astype(LD) - F.astype(LD) @ Gr.T.astype(LD)).astype(np.float64)
+    r2 = rho.astype(LD)
+    return rho, (r2 * r2).sum(axis=1).astype(np.float64)
+
+
+def _sense_batch(Gr, powers, y, perp2, scale, T0, lo, hi, free, max_iter, misfit_tol):
+    """``sense_scores`` for one batch of queries: y (K, r), perp2, scale (K,), T0 (K, t, m)."""
+    K, t, m = T0.shape
+    B = K * t
+    kf = int(free.sum())
+    y, perp2, scale = np.repeat(y, t, axis=0), np.repeat(perp2, t), np.repeat(scale, t)
+    th = np.clip(T0.reshape(B, m), lo, hi)
+    F, _ = legendre_features(th, powers, False)
+    rho, f = _residual(Gr, y, F)
+    lam = np.full(B, 1e-3)
+    active = np.ones(B, dtype=bool)
+    stationary = np.zeros(B, dtype=bool)
+    iterations = np.zeros(B, dtype=np.int64)
+    for _ in range(int(max_iter)):
+        ia = np.flatnonzero(active)
+        if ia.size == 0:
+            break
+        iterations[ia] += 1
+        _, dF = legendre_features(th[ia], powers)
+        Ja = -np.einsum("rp,bpj->brj", Gr, dF[:, :, free])     # the free columns only: a pinned coordinate has none
+        JtJ = np.einsum("bmq,bmp->bqp", Ja, Ja)
+        g = np.einsum("bmq,bm->bq", Ja, rho[ia])
+        dJ = np.einsum("bqq->bq", JtJ)
+        todo = np.ones(ia.size, dtype=bool)
+        for _trial in range(8):
+            it = np.flatnonzero(todo)
+            if it.size == 0:
+                break
+            damp = lam[ia[it], None] * (dJ[it] + 1e-300) + 1e-30 * dJ[it].max(axis=1, keepdims=True, initial=0.0)
+            H = JtJ[it] + damp[:, :, None] * np.eye(kf)
+            step = np.zeros((it.size, m))
+            step[:, free] = -np.linalg.solve(H, g[it][..., None])[..., 0]
+            new = np.clip(th[ia[it]] + step, lo, hi)
+            moved = np.abs(new - th[ia[it]]).max(axis=1)
+            Fn, _ = legendre_features(new, powers, False)
+            rn, fn = _residual(Gr, y[ia[it]], Fn)
+            ok = fn < f[ia[it]]
+            still = moved <= 1e-13 * (1.0 + np.abs(new).max(axis=1))
+            acc = ia[it[ok]]
+            th[acc], rho[acc], f[acc] = new[ok], rn[ok], fn[ok]
+            lam[acc] = np.maximum(lam[acc] / 3.0, 1e-12)
+            lam[ia[it[~ok]]] *= 4.0
+            # a step that no longer moves t (accepted: below 1e-10 relative), or a misfit at rounding level: stationary
+            tiny = ok & (moved <= 1e-10 * (1.0 + np.abs(new).max(axis=1)))
+            done = still | tiny | (np.sqrt(f[ia[it]] + perp2[ia[it]]) <= 1e-14 * scale[ia[it]])
+            stationary[ia[it[done]]] = True
+            active[ia[it[done]]] = False
+            todo[it[ok | done]] = False
+        stuck = ia[np.flatnonzero(todo)]     # eight increases of the damping without a decrease: a minimum to working accuracy
+        stationary[stuck] = True
+        active[stuck] = False
+    misfit = np.sqrt(f + perp2)
+    sig = np.zeros(B)
+    if kf and Gr.shape[0] >= kf:             # (fewer sensor coordinates than free columns: the kf-th singular value is 0)
+        _, dF = legendre_features(th, powers)
+        J = -np.einsum("rp,bpj->brj", Gr, dF[:, :, free])
+        sig = np.linalg.svd(J, compute_uv=False)[:, -1]
+    best = np.argmin(misfit.reshape(K, t), axis=1)
+    pick = np.arange(K) * t + best
+    conv = (stationary | (misfit <= 1e-14 * scale)) & (misfit <= misfit_tol * scale)
+    return th[pick], misfit[pick], conv[pick], iterations[pick], sig[pick], best
+
+
+def sense_scores(Gr, powers, P, T0, lo, hi, aux=None, max_iter=30, misfit_tol=1e-3) -> SenseResult:
+    """Levenberg-Marquardt in t for  min over lo <= t <= hi of ||p - G_r phi(t)||^2 + perp2,  phi the Legendre products of the
+    exponent rows ``powers`` (P, m) (``legendre_features``), J = -G_r d phi / d t: ``inverse.polish_parameters`` with this model,
+    pure NumPy, batched over the queries (in batches of 4,096 systems); the specification of ``rom_poly_sense``.  Gr (r, P) and
+    the queries P (K, r) in reduced sensor coordinates (``inverse.reduce_sensors`` / ``reduce_measurements`` of the sensing
+    matrix), aux (K, 2) = (perp2, scale) or None: 0 and max|p|.  T0 (K, m) or (K, t, m): the starts -- the iteration runs from
+    each and keeps the smallest misfit, the lowest index among equals; t stays in the box [lo, hi] (scalars or (m,)).  A
+    coordinate with lo_j == hi_j is PINNED: it stays at its clipped start bit for bit, has no row or column in J^T J and no
+    column in the J whose ``sigma_min`` is reported (0 when nothing is free).  ``converged``: the iteration became stationary
+    (or the misfit reached rounding level) AND the final misfit is at most misfit_tol scale.  max_iter = 0 only evaluates the
+    clipped starts.  The residual and its squared norm are formed in long double and rounded once (``_residual``)."""
+    Gr = np.asarray(Gr, dtype=np.float64)
+    powers = np.asarray(powers, dtype=np.int64)
+    m = powers.shape[1]
+    P = np.asarray(P, dtype=np.float64).reshape(-1, Gr.shape[0])
+    K = len(P)
+    T0 = np.asarray(T0, dtype=np.float64).reshape(K, -1, m)
+    t = T0.shape[1]
+    lo, hi = np.broadcast_to(np.asarray(lo, dtype=np.float64), (m,)), np.broadcast_to(np.asarray(hi, dtype=np.float64), (m,))
+    free = lo < hi
+    tiny = np.finfo(float).tiny
+    if aux is None:
+        perp2 = np.zeros(K)
+        scale = np.maximum(np.abs(P).max(axis=1), tiny) if P.shape[1] else np.full(K, tiny)
+    else:
+        aux = np.asarray(aux, dtype=np.float64).reshape(K, 2)
+        perp2, scale = aux[:, 0], np.maximum(aux[:, 1], tiny)
+    step = max(1, _SENSE_CHUNK // max(t, 1))
+    parts = [_sense_batch(Gr, powers, P[k0:k0 + step], perp2[k0:k0 + step], scale[k0:k0 + step], T0[k0:k0 + step], lo, hi, free,
+                          max_iter, misfit_tol) for k0 in range(0, K, step)]
+    if not parts:
+        return SenseResult(np.zeros((0, m)), np.zeros(0), np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int64), np.zeros(0),
+                           np.zeros(0, dtype=np.int64))
+    return SenseResult(*(np.concatenate([p[i] for p in parts]) for i in range(6)))
+
+
+class PolynomialSensing:
+    """State estimation from point measurements on the manifold of a fitted polynomial map: the decoder u(z) = mean + z V_known +
+    g(z) V_unknown of ``nonlinear_reconstruction`` is fitted to y = l(u) -- m unknowns where a linear space of that accuracy
+    needs m + q.  ``pca``: a TallPCA; ``poly``: a fitted PolynomialMap from the m known to the q predicted score columns (a
+    TreeMap / ForestMap is not differentiable: TypeError); the known columns are the components [known_start, known_start + m)
+    and the predicted ones [unknown_start, unknown_start + q) (default: right after the known ones).
+
+        est = PolynomialSensing(sm, pca, poly).observe(points).estimate(measurements, states=True)   # SensingEstimate
+    """
+
+    def __init__(self, sm, pca, poly, known_start=0, unknown_start=None):
+        if isinstance(poly, TreeMap) or not isinstance(poly, PolynomialMap):
+            raise TypeError(f"PolynomialSensing needs a PolynomialMap: {type(poly).__name__} is not differentiable")
+        if poly.map_ is None:
+            raise ValueError("PolynomialSensing needs a fitted PolynomialMap (fit / fit_columns comes first)")
+        from . import _ffi
+        self.sm, self.pca, self.poly = sm, pca, poly
+        pm = poly.map_
+        self.m, self.q, self.degree = pm.m, pm.q, pm.degree
+        self.known_start = int(known_start)
+        self.unknown_start = self.known_start + self.m if unknown_start is None else int(unknown_start)
+        rows = pca.components_.rows if isinstance(pca.components_, DeviceArray) else np.shape(pca.components_)[0]
+        if self.known_start < 0 or self.unknown_start < 0 or max(self.known_start + self.m, self.unknown_start + self.q) > rows:
+            raise ValueError(f"PolynomialSensing: the components [{self.known_start}, {self.known_start + self.m}) and "
+                             f"[{self.unknown_start}, {self.unknown_start + self.q}) are not all among the {rows} of the PCA")
+        self.c, self.h, self.W = pm.download("c"), pm.download("h"), pm.download("W")
+        self.powers = _ffi.poly_terms(self.m, self.degree)
+        self.points = None
+
+    def observe(self, points, weights=None, extrapolate=0.5):
+        """Fix the sensors: mean and components at the points, the sensing matrix S (``sensing_matrix``), the compact SVD
+        diag(w) S = U Sigma V^T truncated at sigma > 1e-12 sigma_1 (rank r), G_r = Sigma V^T on the device, and the box
+        [-1 - extrapolate, 1 + extrapolate] of t (t in [-1, 1] over the training rows); a constant training column (h_j = 0)
+        is pinned at t_j = 0."""
+        from .inverse import reduce_sensors
+        sm, ctx, m, q = self.sm, self.sm._ctx, self.m, self.q
+        self.points = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+        ms = len(self.points)
+        self.weights = np.ones(ms) if weights is None else np.asarray(weights, dtype=np.float64).reshape(ms)
+        comps, mean = self.pca.components_, self.pca.mean_
+        comps = comps.numpy() if isinstance(comps, DeviceArray) else np.asarray(comps, dtype=np.float64)
+        mean = mean.numpy().ravel() if isinstance(mean, DeviceArray) else np.asarray(mean, dtype=np.float64).ravel()
+        rows = np.vstack([mean[None, :], comps[self.known_start:self.known_start + m], comps[self.unknown_start:self.unknown_start + q]])
+        E = np.asarray(sm.evaluate_solutions(self.points, rows))            # (1 + m + q, ms)
+        self.e0, self.Ek, self.Eu = E[0].copy(), E[1:1 + m].T.copy(), E[1 + m:].T.copy()
+        self.S = sensing_matrix(self.e0, self.Ek, self.Eu, self.c, self.h, self.W, self.powers)
+        self.U, Gr, _ = reduce_sensors(self.S.T, self.weights)
+        self.Gr_host, self.r = Gr, self.U.shape[1]
+        self.Gr = ctx.upload(Gr)
+        bound = 1.0 + float(extrapolate)
+        self.lo = np.where(self.h > 0.0, -bound, 0.0)
+        self.hi = np.where(self.h > 0.0, bound, 0.0)
+        return self
+
+    def _scaled(self, z):
+        """t = (z - c) / h, 0 for a constant column."""
+        safe = np.where(self.h > 0.0, self.h, 1.0)
+        return np.where(self.h > 0.0, (z - self.c) / safe, 0.0)
+
+    def linear_scores(self, measurements):
+        """The least-squares estimate on the m known modes alone: min ||w (y - e0 - E_k z)||_2."""
+        Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
+        w = self.weights
+        return np.linalg.lstsq(w[:, None] * self.Ek, (w[None, :] * (Y - self.e0[None, :])).T, rcond=None)[0].T
+
+    def estimate(self, measurements, starts=None, device=True, states=False, max_iter=30, misfit_tol=1e-3) -> SensingEstimate:
+        """The known scores of the K measurement vectors (K, ms) by nonlinear least squares on the manifold, from t starts per
+        vector: by default the linear least-squares estimate and the centre of the training box (t = 0); ``starts``: (K, t, m)
+        scores instead.  ``device=True`` runs ``rom_poly_sense`` (ValueError outside its limits m <= 16, d <= 8, P <= 96,
+        r <= 96, t <= 8), ``device=False`` the host iteration ``sense_scores``.  ``states``: decode the estimates
+        (``nonlinear_reconstruction``) into a DeviceArray (None when K = 0)."""
+        from .inverse import reduce_measurements
+        if self.points is None:
+            raise RuntimeError("PolynomialSensing.observe(points) comes first")
+        ctx, m = self.sm._ctx, self.m
+        Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
+        K = len(Y)
+        zl = self.linear_scores(Y) if K else np.zeros((0, m))
+        if starts is None:
+            T0 = np.stack([self._scaled(zl), np.zeros((K, m))], axis=1)
+        else:
+            T0 = self._scaled(np.asarray(starts, dtype=np.float64).reshape(K, -1, m))
+        t = T0.shape[1]
+        Pq, aux = reduce_measurements(self.U, Y, self.weights)
+        if device:
+            _check_sense_limits(m, self.degree, len(self.powers), self.r, t)
+            res, _ = ctx.poly_sense(m, self.degree, self.r, self.Gr, ctx.upload(Pq) if K else None, 0, self.r, K, t,
+                                    ctx.upload(np.ascontiguousarray(T0)) if K else None, self.lo, self.hi,
+                                    AUX=ctx.upload(aux) if K else None, max_iter=max_iter, misfit_tol=misfit_tol)
+        else:
+            res = sense_scores(self.Gr_host, self.powers, Pq, T0, self.lo, self.hi, aux=aux, max_iter=max_iter, misfit_tol=misfit_tol)
+        z = self.c + self.h * res.t
+        predicted = legendre_features(res.t, self.powers, False)[0] @ self.W.T
+        S = None
+        if states and K:
+            S = nonlinear_reconstruction(self.pca, self.poly, z, self.known_start, self.unknown_start, download=False)
+        return SensingEstimate(z, predicted, res.misfit, res.converged, res.iterations, res.sigma_min, res.start, zl, S)
