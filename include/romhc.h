@@ -441,6 +441,59 @@ int rom_poly_query(rom_poly* h, int64_t* out8);
 int rom_poly_download(rom_poly* h, int what, double* host, size_t count);
 int rom_poly_destroy(rom_poly* h);
 
+/* ---- MLP maps between columns of a tall block (src/experiments/NonLinearROM.py:54-70,138, src/lib/Estimators.py:75-97) ------
+ * The "NN" entry of the reference's model list and the regressor of EstimatorNN: a fully connected network from m input columns
+ * through 1 .. 3 hidden layers (tanh, logistic or relu; linear output) to q target columns over M rows.  Inputs are scaled as
+ * in rom_poly_fit, t_j = (x_j - c_j) / h_j (a constant column has t_j = 0); with scale_targets the targets are centred by the
+ * column mean and divided by the column standard deviation over the training rows (a constant column: its value and 1),
+ * without it mean 0 and scale 1.  Loss (scikit-learn's): L(w) = 1/(2M) sum_rows |net(t) - y_scaled|^2 + alpha/(2M) sum_l
+ * |W_l|_F^2, biases not penalised; prediction y_mean + y_scale net((x - c) / h).
+ * Limits: 1 <= m <= 64, hidden widths 1 .. 64, 1 <= q <= 128, M >= 1, and TWO rules on the padded shape (every width, m
+ * included, padded to a multiple of 16): sum_l K_l^pad N_l^pad <= 9216 doubles, and the LDS of the evaluation kernel at one
+ * workgroup per CU <= 160 KB.  That kernel keeps the padded weights (row stride K^pad + 2), the biases and one 32-row slab
+ * [A_0 | .. | A_L | Delta_1 | .. | Delta_L+1] (stride columns + 2) in LDS, + 5 KB of scalings and scratch.  The budget is
+ * 9216, not 8192, because the widest output 1 -> 64 -> 128 is 16 x 64 + 64 x 128 = 9216 (150 KB of LDS: it fits); no budget
+ * alone bounds the LDS (48 -> 32 -> 64 -> 16 -> 128 has 6656 padded weights and needs more than 160 KB, 16 -> 64 -> 64 -> 16
+ * has 6144 and needs 129 KB), hence the second rule.  rom_mlp_layout reports both numbers.  ROM_ERR_INVALID outside the limits.
+ * Optimiser: full-batch L-BFGS (two-loop recursion, gamma = s.y / y.y), first step min(1, 1/|g|_2) then 1, Armijo backtracking
+ * (c1 = 1e-4, halving, 30 trials), a pair kept when s.y > 1e-10 |s| |y|, steepest descent with cleared memory when g.d >= 0;
+ * stops at |g|_inf <= tol, at a relative loss decrease <= tol 1e-2 on two consecutive accepted iterations, at max_iter, or when
+ * the line search is exhausted.  All of it runs on the device (one director workgroup between evaluations); the host enqueues
+ * 16 (evaluation, reduction, director) sequences and reads a status word once per such batch.  No floating-point atomics: the
+ * same bits on a repeated call.  NaN / Inf among the training inputs, targets or initial weights are an error. */
+typedef struct rom_mlp rom_mlp;
+/* (src/experiments/NonLinearROM.py:54-70,138, src/lib/Estimators.py:75-97) host only, no context; the single place of the
+ * limits.  hidden: n_hidden widths.  out8: parameters P, padded weight doubles, LDS bytes of the evaluation kernel, LDS bytes
+ * of the prediction kernel, weight layers n_hidden + 1, doubles of a workgroup's partial, weights among the parameters, 0.
+ * offsets (2 (n_hidden + 1), or NULL): the offset of every W_l (row-major, outputs x inputs), then of every b_l, in the flat
+ * parameter vector -- all W in layer order, then all b. */
+int rom_mlp_layout(int m, int n_hidden, const int* hidden, int q, int64_t* out8, int64_t* offsets);
+/* (src/experiments/NonLinearROM.py:54-70,138, src/lib/Estimators.py:75-97: model.fit) X, Y as in rom_poly_fit; neither is
+ * modified.  activation: 0 tanh, 1 logistic, 2 relu.  w0_host: the P initial parameters in the layout above.  memory: L-BFGS
+ * pairs, 1 .. 64.  max_iter = 0: the handle holds w0 and the scalings of the data.  info_host (8 doubles or NULL): iterations,
+ * loss / gradient evaluations, final loss, final |g|_inf, stop reason (0 gradient tolerance, 1 loss stagnation, 2 iteration
+ * budget, 3 line search failed), kernel launches, host synchronisations, executed flops (6 M sum K^pad N^pad per evaluation). */
+int rom_mlp_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q, int64_t M,
+                int n_hidden, const int* hidden, int activation, double alpha, int scale_targets, const double* w0_host,
+                int max_iter, double tol, int memory, rom_mlp** out, double* info_host);
+/* (src/experiments/NonLinearROM.py:54-70,138, src/lib/Estimators.py:75-97) L and its gradient (P doubles, the layout above) at
+ * the handle's weights on any block of M rows, with the handle's scalings: what the optimiser evaluates.  One host
+ * synchronisation. */
+int rom_mlp_loss_grad(rom_mlp* h, rom_buf* X, size_t x_off, int64_t ldx, rom_buf* Y, size_t y_off, int64_t ldy, int64_t M,
+                      double alpha, double* loss_host, double* grad_host);
+/* (src/experiments/NonLinearROM.py:54-70,138, src/lib/Estimators.py:75-97: model.predict and the error) the contract of
+ * rom_poly_predict: OUT (may be NULL) <- prediction, or Yref - prediction; sumsq_host (q, may be NULL): column sums of squares
+ * of that, from fixed-order partials.  OUT == NULL requires sumsq_host.  OUT must not overlap X.  One host synchronisation. */
+int rom_mlp_predict(rom_mlp* h, rom_buf* X, size_t x_off, int64_t ldx, int64_t M, rom_buf* OUT, size_t o_off, int64_t ldo,
+                    rom_buf* Yref, size_t r_off, int64_t ldr, double* sumsq_host);
+/* (src/experiments/NonLinearROM.py:54-70,138, src/lib/Estimators.py:75-97) out8: m, q, hidden layers, P, M_train, iterations,
+ * kernel launches, host synchronisations so far */
+int rom_mlp_query(rom_mlp* h, int64_t* out8);
+/* (src/experiments/NonLinearROM.py:54-70,138, src/lib/Estimators.py:75-97) host copies: what = 0 w (P), 1 c (m), 2 h (m),
+ * 3 y_mean (q), 4 y_scale (q), 5 the loss after every accepted iteration (iterations + 1).  count must be the size. */
+int rom_mlp_download(rom_mlp* h, int what, double* host, size_t count);
+int rom_mlp_destroy(rom_mlp* h);
+
 /* ---- regression trees and bagged forests on columns of a tall block (src/experiments/NonLinearROM.py:54-70,136-137) ----------
  * What the reference's DecisionTreeRegressor() and RandomForestRegressor(n_estimators=10) compute: T multi-output CART trees
  * from m input columns (1 <= m <= 16) to q target columns (1 <= q <= 128) over M rows, 1 <= T <= 256, built LEVEL BY LEVEL

@@ -126,6 +126,15 @@ PROTOTYPES = {
     "rom_poly_query": (C.c_int, [_vp, _vp]),
     "rom_poly_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
     "rom_poly_destroy": (C.c_int, [_vp]),
+    "rom_mlp_layout": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "rom_mlp_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int, _vp,
+                              C.c_int, C.c_double, C.c_int, _vp, C.c_int, C.c_double, C.c_int, C.POINTER(_vp), _vp]),
+    "rom_mlp_loss_grad": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_double, _vp, _vp]),
+    "rom_mlp_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
+                                  _vp]),
+    "rom_mlp_query": (C.c_int, [_vp, _vp]),
+    "rom_mlp_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
+    "rom_mlp_destroy": (C.c_int, [_vp]),
     "rom_nearest": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, C.c_int,
                               C.c_int, _vp, _vp, _vp]),
     "rom_lm_polish": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp,
@@ -335,6 +344,13 @@ class Context:
         x_off, row stride ldx) to the q columns of Y over M rows.  Neither block is modified.  Returns the PolyMap."""
         return PolyMap(self, X, x_off, ldx, m, Y, y_off, ldy, q, M, degree, rcond)
 
+    def mlp_fit(self, X: "Buffer", x_off, ldx, m, Y: "Buffer", y_off, ldy, q, M, hidden, w0, activation="tanh", alpha=1e-4,
+                scale_targets=True, max_iter=200, tol=1e-6, memory=10) -> "MLPHandle":
+        """rom_mlp_fit: the MLP map m -> ``hidden`` -> q from the columns of X to the columns of Y over M rows (addressed as in
+        ``poly_fit``; neither block is modified), trained from the flat initial parameters ``w0`` (``mlp_layout``) by the
+        device L-BFGS.  max_iter = 0: the handle holds w0 and the scalings.  Returns the MLPHandle."""
+        return MLPHandle(self, X, x_off, ldx, m, Y, y_off, ldy, q, M, hidden, w0, activation, alpha, scale_targets, max_iter, tol, memory)
+
     def tree_fit(self, X: "Buffer", x_off, ldx, m, Y: "Buffer", y_off, ldy, q, M, T=1, counts=None, max_depth=None,
                  min_samples_split=2, min_samples_leaf=1) -> "TreeMapHandle":
         """rom_tree_fit: T regression trees (a bagged forest) from the m columns of X (from element x_off, row stride ldx) to the
@@ -464,6 +480,24 @@ def poly_terms(m: int, degree: int) -> np.ndarray:
     return powers
 
 
+MLP_ACTIVATIONS = {"tanh": 0, "logistic": 1, "sigmoid": 1, "relu": 2}
+
+
+def mlp_layout(m: int, hidden, q: int) -> dict:
+    """rom_mlp_layout (host only; the single place of the limits): P, the padded weight doubles, the LDS bytes of the two
+    kernels and the offsets of every W_l (outputs x inputs, row-major) and b_l in the flat parameter vector -- all W in
+    layer order, then all b.  ValueError outside the limits."""
+    lib = load_library()
+    hid = np.ascontiguousarray(list(hidden), dtype=np.int32)
+    out, off = np.zeros(8, dtype=np.int64), np.zeros(2 * (len(hid) + 1), dtype=np.int64)
+    if lib.rom_mlp_layout(int(m), int(len(hid)), hid.ctypes.data if len(hid) else None, int(q), out.ctypes.data, off.ctypes.data) != ROM_OK:
+        raise ValueError(last_error())
+    nl = len(hid) + 1
+    return dict(P=int(out[0]), padded_weights=int(out[1]), lds_eval=int(out[2]), lds_predict=int(out[3]), layers=nl,
+                partial=int(out[5]), n_weights=int(out[6]), w_offsets=[int(v) for v in off[:nl]],
+                b_offsets=[int(v) for v in off[nl:]], sizes=[int(m)] + [int(v) for v in hid] + [int(q)])
+
+
 def _pod_info(info) -> dict:
     """The info dict of the POD calls (rom_pod's eight doubles)."""
     keys = ("resolved_modes", "completed_modes", "gram_passes", "sketch_passes")
@@ -579,6 +613,89 @@ class PolyMap:
     def free(self):
         if getattr(self, "h", None):
             self.ctx.lib.rom_poly_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class MLPHandle:
+    """Handle of a fitted MLP map (rom_mlp_*): owns the device weights and scalings, destroyed on collection."""
+
+    _PARTS = {"w": 0, "c": 1, "h": 2, "y_mean": 3, "y_scale": 4, "loss_curve": 5}
+    _STOPS = ("gradient", "stagnation", "budget", "line_search")
+
+    def __init__(self, ctx: Context, X: Buffer, x_off, ldx, m, Y: Buffer, y_off, ldy, q, M, hidden, w0, activation="tanh", alpha=1e-4,
+                 scale_targets=True, max_iter=200, tol=1e-6, memory=10):
+        self.ctx = ctx
+        self.h = None
+        self.layout = mlp_layout(m, hidden, q)          # (ValueError outside the limits, before any device call)
+        if activation not in MLP_ACTIVATIONS:
+            raise ValueError(f"activation {activation!r}: one of {sorted(MLP_ACTIVATIONS)}")
+        w0 = _host(np.asarray(w0, dtype=np.float64).ravel())
+        if w0.size != self.layout["P"]:
+            raise ValueError(f"w0 holds {w0.size} parameters, the layout {self.layout['P']}")
+        hid = np.ascontiguousarray(list(hidden), dtype=np.int32)
+        h, info = _vp(), np.zeros(8)
+        try:
+            check(ctx.lib.rom_mlp_fit(ctx.h, X.h if X is not None else None, int(x_off), int(ldx), int(m),
+                                      Y.h if Y is not None else None, int(y_off), int(ldy), int(q), int(M), len(hid), hid.ctypes.data,
+                                      MLP_ACTIVATIONS[activation], float(alpha), 1 if scale_targets else 0, w0.ctypes.data,
+                                      int(max_iter), float(tol), int(memory), C.byref(h), info.ctypes.data))
+        except RomLibraryError as e:
+            if "NaN / Inf" in str(e):   # (scikit-learn's estimators raise ValueError on such input)
+                raise ValueError(str(e)) from None
+            raise
+        self.h = h
+        self.m, self.q, self.P = int(m), int(q), self.layout["P"]
+        self.activation, self.alpha = ("logistic" if activation == "sigmoid" else activation), float(alpha)
+        self.info = dict(iterations=int(info[0]), evaluations=int(info[1]), loss=float(info[2]), grad_inf=float(info[3]),
+                         stop_reason=self._STOPS[int(info[4])], launches=int(info[5]), host_syncs=int(info[6]),
+                         executed_flops=float(info[7]))
+
+    def query(self) -> dict:
+        out = np.zeros(8, dtype=np.int64)
+        check(self.ctx.lib.rom_mlp_query(self.h, out.ctypes.data))
+        keys = ("m", "q", "hidden_layers", "P", "M_train", "iterations", "launches", "host_syncs")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def download(self, part: str) -> np.ndarray:
+        """Host copy of "w" (P,), "c", "h" (m,), "y_mean", "y_scale" (q,) or the "loss_curve" (iterations + 1,)."""
+        n = {"w": self.P, "c": self.m, "h": self.m, "y_mean": self.q, "y_scale": self.q, "loss_curve": self.info["iterations"] + 1}[part]
+        out = np.zeros(n)
+        check(self.ctx.lib.rom_mlp_download(self.h, self._PARTS[part], out.ctypes.data, out.size))
+        return out
+
+    def weights(self):
+        """(coefs, intercepts) in scikit-learn's shapes, (fan_in, fan_out) and (fan_out,), in scaled coordinates."""
+        w, sz, lay = self.download("w"), self.layout["sizes"], self.layout
+        coefs = [w[o:o + sz[l + 1] * sz[l]].reshape(sz[l + 1], sz[l]).T.copy() for l, o in enumerate(lay["w_offsets"])]
+        return coefs, [w[o:o + sz[l + 1]].copy() for l, o in enumerate(lay["b_offsets"])]
+
+    def loss_grad(self, X: Buffer, x_off, ldx, Y: Buffer, y_off, ldy, M, alpha=None):
+        """rom_mlp_loss_grad: (L, its gradient (P,)) at the handle's weights on M rows of X and Y, the handle's scalings."""
+        loss, grad = np.zeros(1), np.zeros(self.P)
+        check(self.ctx.lib.rom_mlp_loss_grad(self.h, X.h if X is not None else None, int(x_off), int(ldx),
+                                             Y.h if Y is not None else None, int(y_off), int(ldy), int(M),
+                                             float(self.alpha if alpha is None else alpha), loss.ctypes.data, grad.ctypes.data))
+        return float(loss[0]), grad
+
+    def predict(self, X: Buffer, x_off, ldx, M, OUT: "Buffer | None" = None, o_off=0, ldo=None, Yref: "Buffer | None" = None, r_off=0,
+                ldr=None, sumsq=False):
+        """rom_mlp_predict: as ``PolyMap.predict``."""
+        ss = np.zeros(self.q) if sumsq else None
+        check(self.ctx.lib.rom_mlp_predict(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M),
+                                           OUT.h if OUT is not None else None, int(o_off), int(self.q if ldo is None else ldo),
+                                           Yref.h if Yref is not None else None, int(r_off), int(self.q if ldr is None else ldr),
+                                           ss.ctypes.data if sumsq else None))
+        return ss
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.rom_mlp_destroy(self.h)
             self.h = None
 
     def __del__(self):

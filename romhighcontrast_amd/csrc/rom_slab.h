@@ -1,6 +1,7 @@
-// Slab engine of the tall-block kernels (k_pca_tall_fused, k_poly_pass, k_poly_predict): a 512-thread workgroup (8 waves)
-// walks a chunk of 32-row slabs that it keeps in LDS and runs two products of v_mfma_f64_16x16x4_f64 on each,
+// Slab engine of the tall-block kernels (k_pca_tall_fused, k_poly_pass, k_poly_predict, k_mlp_eval, k_mlp_predict): a 512-thread
+// workgroup (8 waves) walks a chunk of 32-row slabs that it keeps in LDS and runs products of v_mfma_f64_16x16x4_f64 on each,
 //   NT:  Y (32 x 16 nct) = A (32 x K) B^T, B a table of 16 nct rows, both operands K-contiguous with the same kind of stride;
+//   NN:  Y (32 x 16 nct) = A (32 x K) B, B a table of K rows (k_mlp_eval's backward pass: the NT table of the forward pass);
 //   TN:  acc += Ys^T Ys over the 32 rows, by 16 x 16 tiles given as column offsets (ca, cb) into one slab Ys.
 // Device inline functions only: the kernels keep their own LDS carve-up, prefetch, barriers, epilogues and the list of TN
 // tiles a wave owns (w + 8 u of the workgroup's tiles, accumulators in registers over all slabs of the chunk).
@@ -52,6 +53,28 @@ __device__ __forceinline__ void slab_nt(const double* A, int lda, const double* 
     }
   } else if (ct0 < nct) {
     for (int kk = 0; kk < kpad; kk += 4) y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kk], pb0[kk], y[0], 0, 0, 0);
+  }
+}
+
+// NN product of one slab (k_mlp_eval's backward pass).  The tile ownership of slab_nt, but B is read "transposed": a table of
+// kpad rows (the contraction index) and 16 nct columns with stride ldb, so that y[jj] is tile (w & 1, ct) of A B.  Lane
+// (i, k) takes B[kk + k][16 ct + i]: the access pattern of a TN operand (rows of 16 consecutive doubles).
+__device__ __forceinline__ void slab_nn(const double* A, int lda, const double* B, int ldb, int kpad, int nct, d4_t (&y)[2]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, k = lane >> 4;
+  const int rt = w & 1, ct0 = w >> 1, ct1 = ct0 + 4;
+  y[0] = d4_t{0.0, 0.0, 0.0, 0.0};
+  y[1] = d4_t{0.0, 0.0, 0.0, 0.0};
+  const double* pa = A + (rt * 16 + i) * lda + k;
+  const double* pb0 = B + k * ldb + ct0 * 16 + i;
+  const double* pb1 = B + k * ldb + ct1 * 16 + i;
+  if (ct1 < nct) {
+    for (int kk = 0; kk < kpad; kk += 4) {
+      const double a = pa[kk];
+      y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb0[kk * ldb], y[0], 0, 0, 0);
+      y[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb1[kk * ldb], y[1], 0, 0, 0);
+    }
+  } else if (ct0 < nct) {
+    for (int kk = 0; kk < kpad; kk += 4) y[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kk], pb0[kk * ldb], y[0], 0, 0, 0);
   }
 }
 

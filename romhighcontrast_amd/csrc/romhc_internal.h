@@ -95,6 +95,7 @@ struct rom_ctx {
   bool lds_optin_reduced_solve = false, lds_optin_small_eig = false, lds_optin_pivchol = false, lds_optin_pca_tall = false;
   bool lds_optin_poly_pass = false, lds_optin_poly_predict = false;
   bool lds_optin_nn_screen = false, lds_optin_nn_exhaust = false;
+  bool lds_optin_mlp_eval = false, lds_optin_mlp_predict = false;
 };
 
 struct rom_buf {

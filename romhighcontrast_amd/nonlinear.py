@@ -4,8 +4,9 @@ the index bookkeeping of the regression experiments.  The sweep runs on the devi
 ``pca_tall`` (rom_pca_tall: 25,000 x 81 is M >> dim, the shape rom_pod was not designed for).  The polynomial regressions
 of the third stage have a device path as well (``PolynomialMap``, ``learn_eigenvalues_device``, ``nonlinear_reconstruction``:
 rom_poly_fit / rom_poly_predict), and so have the regression tree and the random forest of the model list (``TreeMap``,
-``ForestMap``: rom_tree_fit / rom_tree_predict, CART trees built level by level over all trees of a forest at once); MLPs
-stay scikit-learn's.  The plots and the PerplexityLab LabPipeline driver of the reference are out of scope.
+``ForestMap``: rom_tree_fit / rom_tree_predict, CART trees built level by level over all trees of a forest at once) and the
+"NN" entry of that list (``MLPMap``: rom_mlp_fit / rom_mlp_predict, loss and gradient in one fused MFMA kernel and a device
+L-BFGS whose specification is ``mlp_fit_host``).  The plots and the PerplexityLab LabPipeline driver of the reference are out of scope.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ from .lib.ReducedBasis import pca_tall
 from .lib.SolutionsManagers import DeviceArray, SolutionsManagerFEM
 
 __all__ = ["ZERO", "Bounds", "MWhere", "draw_parameters", "vn_family_sampler", "do_pca", "get_known_unknown_indexes",
-           "learn_eigenvalues", "PolynomialMap", "TreeMap", "ForestMap", "learn_eigenvalues_device", "nonlinear_reconstruction", "SenseResult", "SensingEstimate", "legendre_table",
+           "learn_eigenvalues", "PolynomialMap", "TreeMap", "ForestMap", "MLPMap", "mlp_loss_grad_host", "mlp_fit_host", "learn_eigenvalues_device", "nonlinear_reconstruction", "SenseResult", "SensingEstimate", "legendre_table",
            "legendre_features", "sensing_matrix", "sense_scores", "PolynomialSensing"]
 
 ZERO = 1e-15
@@ -215,6 +216,178 @@ class ForestMap(TreeMap):
     def bootstrap_counts(T, M, random_state=0):
         draw = np.random.default_rng(random_state).integers(0, M, (T, M))
         return np.stack([np.bincount(row, minlength=M) for row in draw]).astype(np.int32)
+
+
+# ---- MLP maps: rom_mlp_fit / rom_mlp_predict and their specification ------------------------------------------------------
+
+
+def _mlp_split(w, sizes):
+    """The flat parameter vector as [(W_l (outputs, inputs), b_l)]: all W in layer order (row-major), then all b."""
+    nl = len(sizes) - 1
+    Ws, at = [], 0
+    for l in range(nl):
+        Ws.append(w[at:at + sizes[l + 1] * sizes[l]].reshape(sizes[l + 1], sizes[l]))
+        at += sizes[l + 1] * sizes[l]
+    bs = []
+    for l in range(nl):
+        bs.append(w[at:at + sizes[l + 1]])
+        at += sizes[l + 1]
+    assert at == len(w), f"mlp: {len(w)} parameters for the sizes {list(sizes)}, which have {at}"
+    return list(zip(Ws, bs))
+
+
+def mlp_loss_grad_host(w, sizes, activation, T, Ys, alpha, dtype=np.float64):
+    """The loss of rom_mlp_* and its gradient in plain NumPy, all arithmetic in ``dtype``: L = 1/(2M) sum |net(T) - Ys|^2 +
+    alpha/(2M) sum_l |W_l|_F^2 for the scaled inputs T (M, m) and scaled targets Ys (M, q), ``sizes`` = [m, hidden .., q],
+    ``activation`` "tanh", "logistic" or "relu" (linear output), w flat as in ``_ffi.mlp_layout``.  The specification of
+    k_mlp_eval / k_mlp_reduce.  Returns (L, gradient (P,))."""
+    w, T, Ys = np.asarray(w, dtype=dtype), np.asarray(T, dtype=dtype), np.asarray(Ys, dtype=dtype)
+    one, half, M = w.dtype.type(1), w.dtype.type(0.5), w.dtype.type(len(T))
+    alpha = w.dtype.type(alpha)
+    layers = _mlp_split(w, sizes)
+    A = [T]
+    for l, (W, b) in enumerate(layers):
+        z = A[-1] @ W.T + b
+        if l + 1 < len(layers):
+            z = np.tanh(z) if activation == "tanh" else one / (one + np.exp(-z)) if activation == "logistic" else np.where(z > 0, z, 0 * z)
+        A.append(z)
+    delta = A[-1] - Ys
+    loss = (half * (delta * delta).sum() + half * alpha * sum((W * W).sum() for W, _ in layers)) / M
+    gW, gb = [None] * len(layers), [None] * len(layers)
+    for l in range(len(layers) - 1, -1, -1):
+        W = layers[l][0]
+        gW[l] = ((delta.T @ A[l] + alpha * W) / M).ravel()
+        gb[l] = delta.sum(axis=0) / M
+        if l > 0:
+            a = A[l]
+            d = one - a * a if activation == "tanh" else a * (one - a) if activation == "logistic" else (a > 0).astype(w.dtype)
+            delta = (delta @ W) * d
+    return loss, np.concatenate(gW + gb)
+
+
+def mlp_fit_host(w0, sizes, activation, T, Ys, alpha, max_iter, tol, memory, dtype=np.float64):
+    """The optimiser of rom_mlp_fit (k_mlp_director), step for step, in plain NumPy with all arithmetic in ``dtype``: full-batch
+    L-BFGS (two-loop recursion over at most ``memory`` pairs, gamma = s.y / y.y), first step min(1, 1/|g|_2) then 1, Armijo
+    backtracking (c1 = 1e-4, halving, at most 30 trials), a pair kept when s.y > 1e-10 |s| |y|, steepest descent with cleared
+    memory when g.d >= 0.  Stops: 0 |g|_inf <= tol, 1 relative loss decrease <= tol 1e-2 on two consecutive accepted
+    iterations, 2 max_iter, 3 line search exhausted.  Returns a dict: w, loss, grad_inf, iterations, evaluations, stop,
+    loss_curve (iterations + 1), trials (evaluations of every line search)."""
+    dt = np.dtype(dtype).type
+    w = np.array(w0, dtype=dtype)
+    f, g = mlp_loss_grad_host(w, sizes, activation, T, Ys, alpha, dtype)
+    evals, k, stag, hist, trials = 1, 0, 0, [f], []
+    S, Yp, rho, gamma = [], [], [], dt(1)
+    tol = dt(tol)
+    while True:
+        ginf = np.abs(g).max()
+        if ginf <= tol:
+            stop = 0
+            break
+        if stag >= 2:
+            stop = 1
+            break
+        if k >= max_iter:
+            stop = 2
+            break
+        q, al = g.copy(), []
+        for c in range(len(S) - 1, -1, -1):          # newest pair first
+            a = rho[c] * (S[c] @ q)
+            al.append(a)
+            q = q - a * Yp[c]
+        if S:
+            q = q * gamma
+        for c in range(len(S)):
+            b = rho[c] * (Yp[c] @ q)
+            q = q + (al[len(S) - 1 - c] - b) * S[c]
+        d = -q
+        gd, gg = g @ d, g @ g
+        if not gd < 0:                               # not a descent direction: steepest descent, the memory cleared
+            d, gd, S, Yp, rho = -g, -gg, [], [], []
+        t = min(dt(1), dt(1) / np.sqrt(gg)) if k == 0 else dt(1)
+        accepted = False
+        for trial in range(30):
+            wt = w + t * d
+            ft, gt = mlp_loss_grad_host(wt, sizes, activation, T, Ys, alpha, dtype)
+            evals += 1
+            if ft <= f + dt(1e-4) * t * gd:
+                accepted = True
+                break
+            t = t * dt(0.5)
+        trials.append(trial + 1)
+        if not accepted:
+            stop = 3
+            break
+        s, y = wt - w, gt - g
+        sy, ss, yy = s @ y, s @ s, y @ y
+        if sy > dt(1e-10) * np.sqrt(ss) * np.sqrt(yy):
+            if len(S) == memory:
+                S, Yp, rho = S[1:], Yp[1:], rho[1:]
+            S, Yp, rho, gamma = S + [s], Yp + [y], rho + [dt(1) / sy], sy / yy
+        fold, w, f, g, k = f, wt, ft, gt, k + 1
+        hist.append(f)
+        stag = stag + 1 if fold - f <= tol * dt(1e-2) * max(abs(fold), abs(f)) else 0
+    return dict(w=w, loss=f, grad_inf=ginf, iterations=k, evaluations=evals, stop=stop, loss_curve=np.array(hist, dtype=dtype),
+                trials=trials)
+
+
+class MLPMap(PolynomialMap):
+    """(:138, src/lib/Estimators.py:75-97) the reference's ``FNNModel`` / ``MLPRegressor`` as one device fit (rom_mlp_fit): m inputs
+    -> ``hidden_layer_sizes`` (1 .. 3 layers of 1 .. 64 units; "tanh", "logistic" -- alias "sigmoid", the reference's word -- or
+    "relu") -> q linear outputs, scikit-learn's loss with L2 penalty ``alpha``, full-batch L-BFGS on the device (``mlp_fit_host``
+    is its specification), inputs scaled to [-1, 1] and, with ``scale_targets``, targets standardised.  Initial weights:
+    scikit-learn's Glorot uniform draw from ``np.random.RandomState(random_state)`` (``initial_weights``).  The protocol of
+    PolynomialMap: ``fit`` / ``fit_columns`` / ``predict`` on host arrays or DeviceArrays, ``map_`` (the MLPHandle), ``info_``,
+    ``steps``; after a fit ``coefs_`` / ``intercepts_`` (scikit-learn's shapes, in scaled coordinates), ``loss_``,
+    ``loss_curve_``, ``n_iter_``.  ValueError outside the limits of ``_ffi.mlp_layout``."""
+
+    def __init__(self, hidden_layer_sizes=(20, 20), activation="tanh", alpha=1e-4, max_iter=200, tol=1e-6, random_state=0,
+                 scale_targets=True, memory=10, ctx=None):
+        from . import _ffi
+        hidden = (hidden_layer_sizes,) if np.isscalar(hidden_layer_sizes) else tuple(hidden_layer_sizes)
+        self.hidden_layer_sizes = tuple(int(v) for v in hidden)
+        if activation not in _ffi.MLP_ACTIVATIONS:
+            raise ValueError(f"MLPMap: activation {activation!r}, one of {sorted(_ffi.MLP_ACTIVATIONS)}")
+        self.activation = "logistic" if activation == "sigmoid" else activation
+        self.alpha, self.max_iter, self.tol, self.random_state = float(alpha), int(max_iter), float(tol), random_state
+        self.scale_targets, self.memory, self._ctx = bool(scale_targets), int(memory), ctx
+        self.steps = [("NN device", self)]
+        self.map_ = None
+
+    @staticmethod
+    def initial_weights(sizes, activation="tanh", random_state=0):
+        """scikit-learn's initialisation (MLPRegressor._init_coef): per layer W (fan_in, fan_out) then b (fan_out,), uniform in
+        +- sqrt(6 / (fan_in + fan_out)) (2 instead of 6 for "logistic"), from ``np.random.RandomState(random_state)``.  Returns
+        the flat parameter vector of ``_ffi.mlp_layout``: all W_l^T (outputs x inputs, row-major), then all b_l."""
+        rng = np.random.RandomState(random_state)
+        factor = 2.0 if activation in ("logistic", "sigmoid") else 6.0
+        Ws, bs = [], []
+        for fan_in, fan_out in zip(sizes[:-1], sizes[1:]):
+            bound = np.sqrt(factor / (fan_in + fan_out))
+            Ws.append(rng.uniform(-bound, bound, (fan_in, fan_out)).T.ravel())
+            bs.append(rng.uniform(-bound, bound, fan_out))
+        return np.concatenate(Ws + bs)
+
+    def _check(self, m, q):
+        from . import _ffi
+        return _ffi.mlp_layout(int(m), self.hidden_layer_sizes, int(q))   # ValueError outside the limits: no device call yet
+
+    def fit(self, X, y):
+        shape = lambda A: (A.rows, A.dim) if isinstance(A, DeviceArray) else (np.shape(A) + (1,))[:2]
+        self._check(shape(X)[1], shape(y)[1])
+        return super().fit(X, y)
+
+    def fit_columns(self, Xd, xcols, Yd, ycols, row0, rows):
+        m, q = xcols[1] - xcols[0], ycols[1] - ycols[0]
+        lay = self._check(m, q)
+        w0 = self.initial_weights(lay["sizes"], self.activation, self.random_state)
+        self.map_ = self._context().mlp_fit(Xd.buf, row0 * Xd.dim + xcols[0], Xd.dim, m, Yd.buf, row0 * Yd.dim + ycols[0], Yd.dim, q,
+                                            rows, self.hidden_layer_sizes, w0, self.activation, self.alpha, self.scale_targets,
+                                            self.max_iter, self.tol, self.memory)
+        self.info_ = self.map_.info
+        self.coefs_, self.intercepts_ = self.map_.weights()
+        self.loss_curve_ = self.map_.download("loss_curve")
+        self.loss_, self.n_iter_ = self.info_["loss"], self.info_["iterations"]
+        return self
 
 
 def learn_eigenvalues_device(degree=None, rcond=0.0, ctx=None, model=None):
@@ -492,7 +665,7 @@ class PolynomialSensing:
     """
 
     def __init__(self, sm, pca, poly, known_start=0, unknown_start=None):
-        if isinstance(poly, TreeMap) or not isinstance(poly, PolynomialMap):
+        if isinstance(poly, (TreeMap, MLPMap)) or not isinstance(poly, PolynomialMap):
             raise TypeError(f"PolynomialSensing needs a PolynomialMap: {type(poly).__name__} is not differentiable")
         if poly.map_ is None:
             raise ValueError("PolynomialSensing needs a fitted PolynomialMap (fit / fit_columns comes first)")

@@ -7,7 +7,7 @@ _root = _os.path.dirname(_os.path.dirname(_os.path.dirname(_os.path.abspath(__fi
 if _root not in _sys.path:
     _sys.path.insert(0, _root)
 
-from romhighcontrast_amd.nonlinear import (ZERO, Bounds, ForestMap, MWhere, PolynomialMap, TreeMap, do_pca, draw_parameters,  # noqa: E402,F401
+from romhighcontrast_amd.nonlinear import (ZERO, Bounds, ForestMap, MLPMap, MWhere, PolynomialMap, TreeMap, do_pca, draw_parameters,  # noqa: E402,F401
                                            get_known_unknown_indexes, learn_eigenvalues, learn_eigenvalues_device,
                                            nonlinear_reconstruction, vn_family_sampler)
 from romhighcontrast_amd.lib.ReducedBasis import TallPCA, pca_tall  # noqa: E402,F401
