@@ -16,21 +16,17 @@
 // takes the 16-row tiles w, w + 4 of G_r.  The column phi (the model value of every trial) goes by VALU, 16 lanes per row, in
 // double-double arithmetic (see SnDD below): rho and f are correctly rounded, as the host's, which forms them in long double.
 // A PINNED coordinate (lo_j == hi_j) stays at its clipped start bit for bit, has no column in d phi, J, J^T J and sigma_min.
-// Every control decision is taken by all threads from the same LDS values: control flow is uniform within a workgroup (every
-// __syncthreads is reached by all 256 threads) and free between workgroups.  Every loop is bounded by max_iter, SN_TRIALS, m, d,
-// P, r or LMS_SWEEPS; nothing waits on another workgroup.  No floating-point atomics: a repeated call returns the same bits.
+// The iteration itself is lm_drive (rom_lm_drive.h, with the contract on control flow); SnSys below is its model.
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "rom_basis_int.h"
-#include "rom_lm_small.h"
+#include "rom_lm_drive.h"
 #include "rom_mma.h"
 
 namespace {
 
 constexpr int SN_MMAX = 16, SN_DMAX = 8, SN_PMAX = 96, SN_RMAX = 96, SN_TMAX = 8;
-constexpr int SN_TRIALS = 8;
 constexpr int SN_THREADS = LMS_THREADS;
 constexpr int SN_LDD = 16;   // row stride of d phi: a row is one MFMA operand row (16 lanes read 128 contiguous bytes)
 
@@ -71,13 +67,12 @@ struct SnLds {
     Js = take(SN_MMAX * ldr), JtJ = take(SN_MMAX * ldk), Hs = take(SN_MMAX * ldk), hinv = take(SN_MMAX);
     rho = take(r), rhon = take(r), ps = take(r);
     th = take(SN_MMAX), thn = take(SN_MMAX), g = take(SN_MMAX), lo = take(SN_MMAX), hi = take(SN_MMAX);
-    scal = take(8);             // fn | moved | max |new| | flag of the H factor
+    scal = take(8);             // the slots LMS_* of rom_lm_drive.h; [7]: the number of free coordinates
     idx = take(SN_MMAX);        // 2 x 16 ints: the coordinate of free column c | the free column of coordinate j (-1: pinned)
     pw = take(2 * SN_PMAX);     // SN_PMAX x SN_MMAX bytes
     total = at;
   }
 };
-enum { S_FN = 0, S_MOVED = 1, S_MAXNEW = 2, S_OKH = 3 };
 
 __device__ __forceinline__ bool sn_finite(double v) { return fabs(v) < __builtin_huge_val(); }
 
@@ -116,6 +111,8 @@ struct SnSys {
   __device__ const unsigned char* pw() const { return reinterpret_cast<const unsigned char*>(sm + m.pw); }
   __device__ const int* free_coord() const { return reinterpret_cast<const int*>(sm + m.idx); }
   __device__ const int* free_column() const { return reinterpret_cast<const int*>(sm + m.idx) + SN_MMAX; }
+  __device__ int cols() const { return kf; }
+  __device__ unsigned long long work() const { return evaluations; }
 
   // py:legendre_table: L_k and L'_k, k = 0 .. d, of the coordinates at sm[thx ..)
   __device__ void legendre(int thx) {
@@ -135,7 +132,7 @@ struct SnSys {
     evaluations += 1;
   }
 
-  // py:`F, _ = legendre_features(new, powers, False)` .. `fn`: phi(t), rho = p - G_r phi -> rhon, |rho|^2 -> scal[S_FN]
+  // py:`F, _ = legendre_features(new, powers, False)` .. `fn`: phi(t), rho = p - G_r phi -> rhon, |rho|^2 -> scal[LMS_FN]
   __device__ void eval(int thx) {
     const int tid = threadIdx.x, lane = tid & 63, P = a.P, r = a.r, l16 = tid & 15, nm = a.m;
     legendre(thx);
@@ -167,7 +164,7 @@ struct SnSys {
       SnDD f = sn_mac(sn_mac(SnDD{0.0, 0.0}, v0, v0), v1, v1);
 #pragma unroll
       for (int x = 32; x >= 1; x >>= 1) f = sn_add(f, sn_shfl_xor(f, x));
-      if (lane == 0) sm[m.scal + S_FN] = f.hi + f.lo;
+      if (lane == 0) sm[m.scal + LMS_FN] = f.hi + f.lo;
     }
     __syncthreads();
   }
@@ -226,13 +223,53 @@ struct SnSys {
     }
     __syncthreads();
   }
+
+  // py:`step`, `new`, `moved`: lane = coordinate, the step b by free column; a pinned coordinate keeps its value
+  __device__ void step(double b, int lane) {
+    const int nm = a.m;
+    const int c = lane < nm ? free_column()[lane] : -1;
+    const double st = __shfl(b, c >= 0 ? c : 0, 64);
+    double moved = 0.0, mx = 0.0;
+    if (lane < nm) {
+      const double old = sm[m.th + lane], lo = sm[m.lo + lane], hi = sm[m.hi + lane];
+      double nw = old;
+      if (c >= 0) {
+        const double v = old - st;
+        nw = v < lo ? lo : (v > hi ? hi : v);
+      }
+      sm[m.thn + lane] = nw;
+      moved = fabs(nw - old);
+      mx = fabs(nw);
+    }
+    moved = wave_max_nan(moved);
+    mx = wave_max_nan(mx);
+    if (lane == 0) {
+      sm[m.scal + LMS_MOVED] = moved;
+      sm[m.scal + LMS_MAXNEW] = mx;
+    }
+  }
+  __device__ bool trial() {   // (every point of the box is usable)
+    eval(m.thn);
+    return true;
+  }
+  __device__ void keep() {
+    const int tid = threadIdx.x;
+    if (tid < a.m) sm[m.th + tid] = sm[m.thn + tid];
+    if (tid < a.r) sm[m.rho + tid] = sm[m.rhon + tid];
+  }
+  __device__ void refresh() {}   // (the Jacobian needs nothing that a trial overwrites)
+  __device__ int head(double* out) const {   // t
+    if (threadIdx.x < a.m) out[threadIdx.x] = sm[m.th + threadIdx.x];
+    return a.m;
+  }
+  __device__ double sigma_min(int lane) { return kf > 0 ? lm_sigma_min_wave<2>(sm + m.Js, m.ldr, kf, a.r, lane) : 0.0; }
 };
 
 __global__ __launch_bounds__(SN_THREADS) void k_sense(const SnArgs a, const SnBox box, const SnTerms terms) {
   extern __shared__ __align__(16) double sn_lds[];
   double* sm = sn_lds;
   const SnLds m(a.m, a.d, a.P, a.r);
-  const int tid = threadIdx.x, lane = tid & 63, nm = a.m, r = a.r;
+  const int tid = threadIdx.x, nm = a.m, r = a.r;
   const long long sys = blockIdx.x, query = sys / a.t;
   SnSys S(a, m, sm);
   double* out = a.W + size_t(sys) * a.ldw;
@@ -269,115 +306,12 @@ __global__ __launch_bounds__(SN_THREADS) void k_sense(const SnArgs a, const SnBo
   }
   __syncthreads();
   S.kf = int(sm[m.scal + 7]);
-  const int kf = S.kf;
-  double perp2 = 0.0, scale;
-  if (a.aux) {
-    perp2 = a.aux[2 * query];
-    scale = a.aux[2 * query + 1];
-  } else {
-    scale = 0.0;
-    for (int i = 0; i < r; ++i) scale = fmax(scale, fabs(sm[m.ps + i]));
-  }
-  scale = fmax(scale, 2.2250738585072014e-308);
+  double perp2;
+  const double scale = lm_scale(a.aux, query, sm + m.ps, r, perp2);
 
   S.eval(m.th);
   if (tid < r) sm[m.rho + tid] = sm[m.rhon + tid];
-  double f = sm[m.scal + S_FN], lam = 1e-3;
-  bool active = a.max_iter > 0, stationary = false;
-  int iterations = 0;
-  __syncthreads();
-
-  for (int it = 0; it < a.max_iter && active; ++it) {
-    iterations += 1;
-    S.jacobian();
-    double dmax = 0.0;
-    for (int q = 0; q < kf; ++q) {
-      const double d = sm[m.JtJ + q * m.ldk + q];
-      dmax = (d > dmax || d != d) ? d : dmax;
-    }
-    bool todo = true;
-    for (int trial = 0; trial < SN_TRIALS && todo; ++trial) {
-      if (tid < kf * kf) {   // py:`damp`, `H`
-        const int q = tid / kf, p = tid - q * kf;
-        double h = sm[m.JtJ + q * m.ldk + p];
-        if (p == q) h += lam * (h + 1e-300) + 1e-30 * dmax;
-        sm[m.Hs + q * m.ldk + p] = h;
-      }
-      __syncthreads();
-      const bool ok_h = lm_factor(sm + m.Hs, m.ldk, kf, sm + m.hinv, sm + m.scal + S_OKH);
-      if (!ok_h) {   // a damped system that is not positive definite has no step: a rejected trial
-        lam *= 4.0;
-        continue;
-      }
-      if (tid < 64) {   // py:`step`, `new`, `moved`: lane = coordinate; a pinned one keeps its value
-        double b[1] = {lane < kf ? sm[m.g + lane] : 0.0};
-        lm_solve<1>(sm + m.Hs, m.ldk, kf, sm + m.hinv, b, lane);
-        const int c = lane < nm ? S.free_column()[lane] : -1;
-        const double st = __shfl(b[0], c >= 0 ? c : 0, 64);
-        double moved = 0.0, mx = 0.0;
-        if (lane < nm) {
-          const double old = sm[m.th + lane], lo = sm[m.lo + lane], hi = sm[m.hi + lane];
-          double nw = old;
-          if (c >= 0) {
-            const double v = old - st;
-            nw = v < lo ? lo : (v > hi ? hi : v);
-          }
-          sm[m.thn + lane] = nw;
-          moved = fabs(nw - old);
-          mx = fabs(nw);
-        }
-        moved = wave_max_nan(moved);
-        mx = wave_max_nan(mx);
-        if (lane == 0) {
-          sm[m.scal + S_MOVED] = moved;
-          sm[m.scal + S_MAXNEW] = mx;
-        }
-      }
-      __syncthreads();
-      S.eval(m.thn);
-      const double fn = sm[m.scal + S_FN], moved = sm[m.scal + S_MOVED], mx = sm[m.scal + S_MAXNEW];
-      const bool ok = fn < f;                                // py:`ok`
-      const bool still = moved <= 1e-13 * (1.0 + mx);        // py:`still`
-      __syncthreads();   // (everyone has read the scalars before the vectors move)
-      if (ok) {
-        if (tid < nm) sm[m.th + tid] = sm[m.thn + tid];
-        if (tid < r) sm[m.rho + tid] = sm[m.rhon + tid];
-        f = fn;
-        lam = fmax(lam / 3.0, 1e-12);
-      } else {
-        lam *= 4.0;
-      }
-      const bool tiny = ok && moved <= 1e-10 * (1.0 + mx);   // py:`tiny`
-      const bool done = still || tiny || sqrt(f + perp2) <= 1e-14 * scale;
-      if (done) {
-        stationary = true;
-        active = false;
-      }
-      if (ok || done) todo = false;
-      __syncthreads();
-    }
-    if (todo) {   // py:`stuck`
-      stationary = true;
-      active = false;
-    }
-  }
-
-  // the Jacobian at the final t: rho and f are the accepted ones
-  S.jacobian();
-  const double misfit = sqrt(f + perp2);
-  if (tid < nm) out[tid] = sm[m.th + tid];
-  if (tid < 64) {
-    const double smin = kf > 0 ? lm_sigma_min_wave<2>(sm + m.Js, m.ldr, kf, r, lane) : 0.0;
-    if (lane == 0) {
-      const bool conv = (stationary || misfit <= 1e-14 * scale) && misfit <= a.misfit_tol * scale;
-      out[nm] = misfit;
-      out[nm + 1] = smin;
-      out[nm + 2] = conv ? 1.0 : 0.0;
-      out[nm + 3] = double(iterations);
-      atomicAdd(a.counters, (unsigned long long)iterations);
-      atomicAdd(a.counters + 1, S.evaluations);
-    }
-  }
+  lm_drive(S, perp2, scale, out);
 }
 
 }  // namespace
@@ -393,26 +327,10 @@ extern "C" int rom_poly_sense(rom_ctx* ctx, int m, int d, int r, rom_buf* Gr, ro
   ROM_CHECK(terms <= SN_PMAX, "rom_poly_sense: P = C(%d + %d, %d) = %lld terms, at most %d", m, d, d, terms, SN_PMAX);
   const int np = int(terms);
   ROM_CHECK(r >= 1 && r <= SN_RMAX, "rom_poly_sense: r = %d sensor coordinates, between 1 and %d", r, SN_RMAX);
-  ROM_CHECK(t >= 1 && t <= SN_TMAX, "rom_poly_sense: t = %d starts per query, between 1 and %d", t, SN_TMAX);
-  ROM_CHECK(K >= 0 && int64_t(K) * t <= (int64_t(1) << 30), "rom_poly_sense: K = %d queries (K t at most 2^30)", K);
-  ROM_CHECK(max_iter >= 0, "rom_poly_sense: max_iter = %d", max_iter);
-  ROM_CHECK(ldo >= int64_t(m) + 5, "rom_poly_sense: ldo = %lld < m + 5 = %d", (long long)ldo, m + 5);
   ROM_CHECK(Gr->n >= size_t(r) * np, "rom_poly_sense: Gr holds %zu doubles, r P = %zu needed", Gr->n, size_t(r) * np);
-  if (info8_host) std::fill(info8_host, info8_host + 8, 0.0);
-  if (K == 0) return ROM_OK;
-  ROM_CHECK(P && T0 && OUT, "rom_poly_sense: null argument (P, T0 or OUT)");
-  ROM_CHECK(ldp >= r, "rom_poly_sense: ldp = %lld < r = %d", (long long)ldp, r);
-  ROM_CHECK(p_off + size_t(K - 1) * size_t(ldp) + size_t(r) <= P->n,
-            "rom_poly_sense: P holds %zu doubles, %d rows of %d at offset %zu with stride %lld need more", P->n, K, r, p_off, (long long)ldp);
-  ROM_CHECK(T0->n >= size_t(K) * t * m, "rom_poly_sense: T0 holds %zu doubles, K t m = %zu needed", T0->n, size_t(K) * t * m);
-  ROM_CHECK(!AUX || AUX->n >= 2 * size_t(K), "rom_poly_sense: AUX holds %zu doubles, 2 K = %zu needed", AUX ? AUX->n : 0, 2 * size_t(K));
-  ROM_CHECK(out_off + size_t(K - 1) * size_t(ldo) + size_t(m + 5) <= OUT->n,
-            "rom_poly_sense: OUT holds %zu doubles, %d rows of %d at offset %zu with stride %lld need more", OUT->n, K, m + 5, out_off,
-            (long long)ldo);
   const SnLds map(m, d, np, r);
   const size_t lds = size_t(map.total) * sizeof(double);
   ROM_CHECK(lds <= 64 * 1024, "rom_poly_sense: %zu bytes of LDS", lds);   // (34.7 KB at most)
-  ROM_HIP(hipSetDevice(ctx->device));
 
   SnBox box;
   for (int j = 0; j < SN_MMAX; ++j) {
@@ -428,47 +346,16 @@ extern "C" int rom_poly_sense(rom_ctx* ctx, int m, int d, int r, rom_buf* Gr, ro
     for (int p = 0; p < np; ++p)
       for (int j = 0; j < m; ++j) tab.pw[p * SN_MMAX + j] = (unsigned char)powers[size_t(p) * m + j];
   }
-  const int B = K * t, ldw = m + 4;
-  Tmp ws;
-  const size_t ws_doubles = size_t(B) * ldw + 2;
-  ROM_TRY(ws.get(ctx, ws_doubles));
-  unsigned long long* counters = reinterpret_cast<unsigned long long*>(ws.p() + size_t(B) * ldw);
-  ROM_HIP(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
-  ROM_HIP(hipMemsetAsync(ctx->d_status, 0, sizeof(int), ctx->stream));
-  SnArgs a;
-  a.m = m, a.d = d, a.P = np, a.r = r, a.t = t, a.max_iter = max_iter;
-  a.Gr = Gr->p, a.Pq = P->p + p_off, a.ldp = ldp, a.T0 = T0->p, a.aux = AUX ? AUX->p : nullptr, a.misfit_tol = misfit_tol;
-  a.W = ws.p(), a.ldw = ldw, a.counters = counters, a.status = ctx->d_status;
-  {
+  const LmCall call = {"rom_poly_sense", r, K, t, SN_TMAX, max_iter, m, m, "T0", "m", "m", P, T0, AUX, OUT, p_off, out_off,
+                       ldp, ldo, info8_host, "poly_sense_select", "NaN / Inf in Gr, P or T0", ROM_ERR_INVALID};
+  return lm_launch(ctx, call, [&](double* W, int ldw, unsigned long long* counters) {
+    SnArgs a;
+    a.m = m, a.d = d, a.P = np, a.r = r, a.t = t, a.max_iter = max_iter;
+    a.Gr = Gr->p, a.Pq = P->p + p_off, a.ldp = ldp, a.T0 = T0->p, a.aux = AUX ? AUX->p : nullptr, a.misfit_tol = misfit_tol;
+    a.W = W, a.ldw = ldw, a.counters = counters, a.status = ctx->d_status;
     char nm[48];
     rom_prof_name(nm, sizeof nm, "poly_sense", "_m%d_d%d_r%d", m, d, r);
     ROM_PROF(ctx, nm, 0.0, 0.0);
-    k_sense<<<B, SN_THREADS, lds, ctx->stream>>>(a, box, tab);
-  }
-  ROM_HIP(hipGetLastError());
-  {
-    ROM_PROF(ctx, "poly_sense_select", 0.0, 8.0 * double(B) * ldw);
-    k_lm_select<<<K, 64, 0, ctx->stream>>>(ws.p(), ldw, t, m, OUT->p + out_off, ldo);
-  }
-  ROM_HIP(hipGetLastError());
-  unsigned long long hc[2] = {0, 0};
-  int status = 0;
-  ROM_HIP(hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, ctx->stream));
-  ROM_HIP(hipMemcpyAsync(&status, ctx->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  ROM_HIP(hipStreamSynchronize(ctx->stream));
-  if (info8_host) {
-    info8_host[0] = 2;   // launches
-    info8_host[1] = 1;   // host synchronisations
-    info8_host[2] = double(ws_doubles) * sizeof(double);
-    info8_host[3] = B;
-    info8_host[4] = double(hc[0]);
-    info8_host[5] = double(hc[1]);
-  }
-  if (status) {
-    // (reported once: the word is cleared, or the next call on this context would report this failure again)
-    ROM_HIP(hipMemsetAsync(ctx->d_status, 0, sizeof(int), ctx->stream));
-    rom_set_error("rom_poly_sense: NaN / Inf in Gr, P or T0");
-    return ROM_ERR_INVALID;
-  }
-  return ROM_OK;
+    k_sense<<<K * t, SN_THREADS, lds, ctx->stream>>>(a, box, tab);
+  });
 }

@@ -213,6 +213,33 @@ def test_noise_agrees_with_the_host(ctx):
     assert (diff <= 1e-10).sum() >= 38, np.sort(diff)[-5:]
 
 
+def test_a_start_that_is_not_positive_definite_is_reported_once(ctx):
+    """Ahat_0 negated: A(theta) is indefinite at the start, the call fails with ROM_ERR_NOT_SPD (which the binding, and only that
+    status, raises as LinAlgError) -- and leaves the context's status word clear: rom_solve_status right after it reports nothing,
+    and the same call on the sound model returns the bits it returned before."""
+    from scipy.linalg import LinAlgError
+    from romhighcontrast_amd._ffi import ROM_OK
+    model = lt.synth(4, 2, 3, 7)
+    theta_true, P = lt.exact_queries(model, 2, 7)
+    theta0 = theta_true[:, None, :] + 0.1 * np.random.default_rng(8).standard_normal((2, 1, 2))
+    up = ctx.upload
+
+    def call(Ahat):
+        OUT = up(np.full(2 * 11, np.nan))
+        ctx.lm_polish(4, 2, 3, up(Ahat), up(model["bhat"]), up(model["Gr"]), up(P), 0, 3, 2, 1, up(theta0), model["lo"], model["hi"], OUT=OUT)
+        return OUT.download()
+
+    before = call(model["Ahat"])
+    assert np.isfinite(before).all()
+    broken = model["Ahat"].copy()
+    broken[0] = -broken[0]
+    with pytest.raises(LinAlgError, match="not positive definite"):
+        call(broken)
+    assert ctx.lib.rom_solve_status(ctx.h) == ROM_OK, "the failure of rom_lm_polish is reported a second time"
+    after = call(model["Ahat"])
+    assert np.isfinite(after).all() and np.array_equal(_bits(after), _bits(before))
+
+
 def test_errors(ctx):
     from romhighcontrast_amd._ffi import RomLibraryError
     model = lt.synth(4, 2, 3, 7)
