@@ -590,6 +590,27 @@ int rom_poly_sense(rom_ctx* ctx, int m, int d, int r, rom_buf* Gr, rom_buf* P, s
                    const double* lo_host, const double* hi_host, rom_buf* AUX, int max_iter, double misfit_tol, rom_buf* OUT,
                    size_t out_off, int64_t ldo, double* info8_host);
 
+/* ---- sensor state estimation on the MLP manifold (src/experiments/NonLinearROM.py:54-70,138, src/lib/ReducedBasis.py:65-70) ----
+ * rom_poly_sense for the decoder of a fitted rom_mlp map (the "NN" model of src/experiments/NonLinearROM.py:138): m inputs ->
+ * n_hidden layers of hidden[l] units with the activation 0 tanh, 1 logistic, 2 relu -> a linear output layer.  With t = (z - c) / h
+ * and a_L(t) the activations of the last hidden layer the sensor image of the decoder is S psi(t), psi = [1; t; a_L(t)] of length
+ * 1 + m + H_L: the output layer and the scaling of the targets are part of S (romhighcontrast_amd/nonlinear.py::
+ * mlp_sensing_matrix), so only the hidden layers reach the call.  WH holds them in the flat order of rom_mlp_layout without the
+ * output layer: every W_l (outputs x inputs, row-major) in layer order, then every b_l.  Gr (r x (1 + m + H_L) row-major) = Sigma
+ * V^T of the compact SVD diag(w) S = U Sigma V^T; P, AUX, T0, lo_host / hi_host, the iteration, pinned coordinates, the second
+ * kernel and the OUT row  t (m) | misfit | sigma_min | converged | iterations | start  are those of rom_poly_sense, with
+ * J = -G_r d psi / d t, d psi / d t = [0; I; D_L], D_0 = I, D_{l+1} = diag(sigma'(a_{l+1})) W_l D_l (the products W_l D_l and
+ * G_r d psi on fp64 MFMA, psi in plain fp64, the residual and its squared norm in double-double arithmetic, rounded once);
+ * romhighcontrast_amd/nonlinear.py::mlp_sense_scores is the same algorithm on the host.
+ * 1 <= m <= 16, 1 <= n_hidden <= 3, 1 <= hidden[l] <= 64, activation in {0, 1, 2}, 1 <= r <= 96, 1 <= t <= 8: ROM_ERR_INVALID
+ * outside; K = 0 is a no-op; max_iter = 0 only evaluates the clipped starts.  NaN / Inf in WH, Gr, P or T0: ROM_ERR_INVALID.  No
+ * input buffer is modified; no floating-point atomics: the same bits on a repeated call.  Two launches, one host synchronisation.
+ * info8_host (8 doubles or NULL): kernel launches, host synchronisations, bytes of workspace, systems K t, LM iterations executed,
+ * forward passes of the hidden layers executed (both summed on the device in integers), 0, 0. */
+int rom_mlp_sense(rom_ctx* ctx, int m, int n_hidden, const int* hidden, int activation, rom_buf* WH, int r, rom_buf* Gr, rom_buf* P,
+                  size_t p_off, int64_t ldp, int K, int t, rom_buf* T0, const double* lo_host, const double* hi_host, rom_buf* AUX,
+                  int max_iter, double misfit_tol, rom_buf* OUT, size_t out_off, int64_t ldo, double* info8_host);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

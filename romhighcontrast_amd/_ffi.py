@@ -141,6 +141,8 @@ PROTOTYPES = {
                                 _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_poly_sense": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                  C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
+    "rom_mlp_sense": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp,
+                                _vp, _vp, _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_tree_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "rom_tree_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
@@ -415,6 +417,37 @@ class Context:
                                       T0.h if T0 is not None else None, lo.ctypes.data, hi.ctypes.data,
                                       AUX.h if AUX is not None else None, int(max_iter), float(misfit_tol),
                                       OUT.h if OUT is not None else None, int(out_off), ldo, info.ctypes.data))
+        rows = np.zeros((K, ldo))
+        if K:   # (the last row may end with the buffer, m + 5 doubles in)
+            rows.reshape(-1)[:(K - 1) * ldo + m + 5] = OUT.download((K - 1) * ldo + m + 5, offset=int(out_off))
+        res = SenseResult(rows[:, :m].copy(), rows[:, m].copy(), rows[:, m + 2] != 0.0, rows[:, m + 3].astype(np.int64),
+                          rows[:, m + 1].copy(), rows[:, m + 4].astype(np.int64))
+        d8 = dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), systems=int(info[3]),
+                  iterations=int(info[4]), evaluations=int(info[5]))
+        return res, d8
+
+    def mlp_sense(self, m, hidden, activation, WH: "Buffer", r, Gr: "Buffer", P: "Buffer", p_off, ldp, K, t, T0: "Buffer", lo, hi,
+                  AUX: "Buffer | None" = None, max_iter=30, misfit_tol=1e-3, OUT: "Buffer | None" = None, out_off=0, ldo=None):
+        """rom_mlp_sense: nonlinear.mlp_sense_scores on the device: ``poly_sense`` with the features [1; t; last hidden layer] of
+        the network m -> ``hidden`` with ``activation`` ("tanh", "logistic" / "sigmoid", "relu"); WH: the hidden layers' flat
+        parameters (all W_l, outputs x inputs row-major, then all b_l), Gr (r, 1 + m + hidden[-1]).  Everything else as in
+        ``poly_sense``; ``evaluations`` counts forward passes.  Returns (SenseResult, info dict)."""
+        from .nonlinear import SenseResult
+        m, K = int(m), int(K)
+        if activation not in MLP_ACTIVATIONS:
+            raise ValueError(f"activation {activation!r}: one of {sorted(MLP_ACTIVATIONS)}")
+        hid = np.ascontiguousarray([int(v) for v in hidden], dtype=np.int32)
+        ldo = m + 5 if ldo is None else int(ldo)
+        lo = _host(np.broadcast_to(np.asarray(lo, dtype=np.float64), (m,)))
+        hi = _host(np.broadcast_to(np.asarray(hi, dtype=np.float64), (m,)))
+        if OUT is None and K > 0:
+            OUT = self.alloc(int(out_off) + K * ldo)
+        info = np.zeros(8)
+        check(self.lib.rom_mlp_sense(self.h, m, len(hid), hid.ctypes.data if len(hid) else None, MLP_ACTIVATIONS[activation], WH.h, int(r),
+                                     Gr.h, P.h if P is not None else None, int(p_off), int(ldp), K, int(t),
+                                     T0.h if T0 is not None else None, lo.ctypes.data, hi.ctypes.data,
+                                     AUX.h if AUX is not None else None, int(max_iter), float(misfit_tol),
+                                     OUT.h if OUT is not None else None, int(out_off), ldo, info.ctypes.data))
         rows = np.zeros((K, ldo))
         if K:   # (the last row may end with the buffer, m + 5 doubles in)
             rows.reshape(-1)[:(K - 1) * ldo + m + 5] = OUT.download((K - 1) * ldo + m + 5, offset=int(out_off))

@@ -1,4 +1,5 @@
-// The Levenberg-Marquardt iteration of the batched kernels (rom_lm.hip: k_lm_polish, rom_sense.hip: k_sense) and the host side
+// The Levenberg-Marquardt iteration of the batched kernels (rom_lm.hip: k_lm_polish, rom_sense.hip: k_sense, rom_mlp_sense.hip:
+// k_mlp_sense, the last two through rom_sense_sys.h) and the host side
 // that their entry points share -- a port, line for line, of romhighcontrast_amd/inverse.py::polish_parameters (cited below as
 // `py:NN`, the line numbers of that file; nonlinear.py::sense_scores runs the same loop on another model).  (internal)
 //
@@ -7,7 +8,7 @@
 // workgroups.  Every loop is bounded by max_iter, LM_TRIALS, the sizes of the system or LMS_SWEEPS; nothing waits on another
 // workgroup.  No floating-point atomics: a repeated call returns the same bits.
 //
-// A system type Sys (LmSys, SnSys) supplies the model:
+// A system type Sys (LmSys, SnSys<feature policy>) supplies the model:
 //   a, m, sm          its arguments (max_iter, misfit_tol, counters), its LDS map (JtJ, Hs, ldk, hinv, g, scal) and the LDS
 //   cols()            the number of free columns of the Jacobian
 //   jacobian()        J, J^T J -> JtJ and g = J^T rho at the current point
@@ -129,7 +130,7 @@ __device__ void lm_drive(Sys& S, double perp2, double scale, double* out) {
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
-// What rom_lm_polish and rom_poly_sense pass to lm_launch after the checks of their own model.  A start is `width` doubles (named
+// What rom_lm_polish, rom_poly_sense and rom_mlp_sense pass to lm_launch after the checks of their own model.  A start is `width` doubles (named
 // width_name in the messages), an output row `lead` doubles (lead_name) | misfit | sigma_min | converged | iterations | start.
 struct LmCall {
   const char* who;

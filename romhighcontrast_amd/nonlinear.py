@@ -555,14 +555,15 @@ def _residual(Gr, y, F):
     return rho, (r2 * r2).sum(axis=1).astype(np.float64)
 
 
-def _sense_batch(Gr, powers, y, perp2, scale, T0, lo, hi, free, max_iter, misfit_tol):
-    """``sense_scores`` for one batch of queries: y (K, r), perp2, scale (K,), T0 (K, t, m)."""
+def _sense_batch(Gr, features, y, perp2, scale, T0, lo, hi, free, max_iter, misfit_tol):
+    """``sense_scores`` / ``mlp_sense_scores`` for one batch of queries: y (K, r), perp2, scale (K,), T0 (K, t, m);
+    ``features(t, jacobian)`` -> (psi (B, P), d psi / d t (B, P, m) or None), the model."""
     K, t, m = T0.shape
     B = K * t
     kf = int(free.sum())
     y, perp2, scale = np.repeat(y, t, axis=0), np.repeat(perp2, t), np.repeat(scale, t)
     th = np.clip(T0.reshape(B, m), lo, hi)
-    F, _ = legendre_features(th, powers, False)
+    F, _ = features(th, False)
     rho, f = _residual(Gr, y, F)
     lam = np.full(B, 1e-3)
     active = np.ones(B, dtype=bool)
@@ -573,7 +574,7 @@ def _sense_batch(Gr, powers, y, perp2, scale, T0, lo, hi, free, max_iter, misfit
         if ia.size == 0:
             break
         iterations[ia] += 1
-        _, dF = legendre_features(th[ia], powers)
+        _, dF = features(th[ia], True)
         Ja = -np.einsum("rp,bpj->brj", Gr, dF[:, :, free])     # the free columns only: a pinned coordinate has none
         JtJ = np.einsum("bmq,bmp->bqp", Ja, Ja)
         g = np.einsum("bmq,bm->bq", Ja, rho[ia])
@@ -589,7 +590,7 @@ def _sense_batch(Gr, powers, y, perp2, scale, T0, lo, hi, free, max_iter, misfit
             step[:, free] = -np.linalg.solve(H, g[it][..., None])[..., 0]
             new = np.clip(th[ia[it]] + step, lo, hi)
             moved = np.abs(new - th[ia[it]]).max(axis=1)
-            Fn, _ = legendre_features(new, powers, False)
+            Fn, _ = features(new, False)
             rn, fn = _residual(Gr, y[ia[it]], Fn)
             ok = fn < f[ia[it]]
             still = moved <= 1e-13 * (1.0 + np.abs(new).max(axis=1))
@@ -609,7 +610,7 @@ def _sense_batch(Gr, powers, y, perp2, scale, T0, lo, hi, free, max_iter, misfit
     misfit = np.sqrt(f + perp2)
     sig = np.zeros(B)
     if kf and Gr.shape[0] >= kf:             # (fewer sensor coordinates than free columns: the kf-th singular value is 0)
-        _, dF = legendre_features(th, powers)
+        _, dF = features(th, True)
         J = -np.einsum("rp,bpj->brj", Gr, dF[:, :, free])
         sig = np.linalg.svd(J, compute_uv=False)[:, -1]
     best = np.argmin(misfit.reshape(K, t), axis=1)
@@ -632,6 +633,12 @@ def sense_scores(Gr, powers, P, T0, lo, hi, aux=None, max_iter=30, misfit_tol=1e
     Gr = np.asarray(Gr, dtype=np.float64)
     powers = np.asarray(powers, dtype=np.int64)
     m = powers.shape[1]
+    return _sense_queries(Gr, lambda th, jacobian: legendre_features(th, powers, jacobian), m, P, T0, lo, hi, aux, max_iter, misfit_tol)
+
+
+def _sense_queries(Gr, features, m, P, T0, lo, hi, aux, max_iter, misfit_tol) -> SenseResult:
+    """The part of ``sense_scores`` / ``mlp_sense_scores`` that does not know the model (``features``, as in ``_sense_batch``):
+    the shapes, the box, perp2 and scale, the batches."""
     P = np.asarray(P, dtype=np.float64).reshape(-1, Gr.shape[0])
     K = len(P)
     T0 = np.asarray(T0, dtype=np.float64).reshape(K, -1, m)
@@ -646,7 +653,7 @@ def sense_scores(Gr, powers, P, T0, lo, hi, aux=None, max_iter=30, misfit_tol=1e
         aux = np.asarray(aux, dtype=np.float64).reshape(K, 2)
         perp2, scale = aux[:, 0], np.maximum(aux[:, 1], tiny)
     step = max(1, _SENSE_CHUNK // max(t, 1))
-    parts = [_sense_batch(Gr, powers, P[k0:k0 + step], perp2[k0:k0 + step], scale[k0:k0 + step], T0[k0:k0 + step], lo, hi, free,
+    parts = [_sense_batch(Gr, features, P[k0:k0 + step], perp2[k0:k0 + step], scale[k0:k0 + step], T0[k0:k0 + step], lo, hi, free,
                           max_iter, misfit_tol) for k0 in range(0, K, step)]
     if not parts:
         return SenseResult(np.zeros((0, m)), np.zeros(0), np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int64), np.zeros(0),
@@ -751,3 +758,165 @@ class PolynomialSensing:
         if states and K:
             S = nonlinear_reconstruction(self.pca, self.poly, z, self.known_start, self.unknown_start, download=False)
         return SensingEstimate(z, predicted, res.misfit, res.converged, res.iterations, res.sigma_min, res.start, zl, S)
+
+
+# ---- sensor state estimation on the MLP manifold: rom_mlp_sense -----------------------------------------------------------
+
+MLP_SENSE_LIMITS = dict(m=16, layers=3, width=64, r=96, t=8)   # rom_mlp_sense (csrc/rom_mlp_sense.hip)
+
+
+def _check_mlp_sense_limits(m, hidden, r, t):
+    hidden = tuple(int(v) for v in hidden)
+    checks = [("m", m, "m"), ("layers", len(hidden), "layers")] + [("width", v, "width") for v in hidden] + [("r", r, "r"), ("t", t, "t")]
+    for name, v, key in checks:
+        if not 1 <= v <= MLP_SENSE_LIMITS[key]:
+            raise ValueError(f"the device estimate (rom_mlp_sense) needs 1 <= {name} <= {MLP_SENSE_LIMITS[key]}, got {name} = {v} "
+                             f"(hidden layers {hidden}): use device=False (the host iteration)")
+
+
+def mlp_hidden_features(t, layers, activation, jacobian=True):
+    """psi (B, P) = [1, t, a_L(t)] and d psi / d t (B, P, m) = [0; I; D_L] (None unless ``jacobian``) at the rows of t (B, m), in
+    t's dtype, P = 1 + m + H_L: the hidden layers ``layers`` = [(W_l (outputs, inputs), b_l)] with ``activation`` "tanh",
+    "logistic" or "relu", a_0 = t, a_{l+1} = sigma(W_l a_l + b_l), and in forward mode D_0 = I, D_{l+1} = diag(sigma'(a_{l+1})) W_l
+    D_l with sigma' = 1 - a^2, a (1 - a), [a > 0] (as in ``mlp_loss_grad_host``)."""
+    t = np.asarray(t)
+    B, m = t.shape
+    one = t.dtype.type(1)
+    a = t
+    D = np.broadcast_to(np.eye(m, dtype=t.dtype), (B, m, m)) if jacobian else None
+    for W, b in layers:
+        W, b = np.asarray(W, dtype=t.dtype), np.asarray(b, dtype=t.dtype)
+        z = a @ W.T + b
+        a = np.tanh(z) if activation == "tanh" else one / (one + np.exp(-z)) if activation == "logistic" else np.where(z > 0, z, 0 * z)
+        if jacobian:
+            d = one - a * a if activation == "tanh" else a * (one - a) if activation == "logistic" else (a > 0).astype(t.dtype)
+            D = d[:, :, None] * np.matmul(W, D)
+    psi = np.concatenate([np.ones((B, 1), dtype=t.dtype), t, a], axis=1)
+    if not jacobian:
+        return psi, None
+    eye = np.broadcast_to(np.eye(m, dtype=t.dtype), (B, m, m))
+    return psi, np.concatenate([np.zeros((B, 1, m), dtype=t.dtype), eye, D], axis=1)
+
+
+def mlp_sensing_matrix(e0, Ek, Eu, c, h, y_mean, y_scale, W_out, b_out):
+    """S (ms, 1 + m + H_L) with  l(mean + z V_known + g(z) V_unknown) = S psi(t),  z = c + h t,  g = y_mean + y_scale (W_out a_L(t) +
+    b_out),  psi = [1; t; a_L(t)] (``mlp_hidden_features``):  S = [e0 + E_k c + E_u (y_mean + y_scale b_out) | E_k diag(h) | E_u
+    diag(y_scale) W_out].  e0 (ms,) = l(mean), Ek (ms, m) and Eu (ms, q) = l(known / predicted components); c, h (m,), y_mean,
+    y_scale (q,), W_out (q, H_L) and b_out (q,) of the fitted map."""
+    f = lambda A: np.asarray(A, dtype=np.float64)   # noqa: E731
+    e0, Ek, Eu, c, h, y_mean, y_scale, W_out, b_out = map(f, (e0, Ek, Eu, c, h, y_mean, y_scale, W_out, b_out))
+    s0 = e0 + Ek @ c + Eu @ (y_mean + y_scale * b_out)
+    return np.concatenate([s0[:, None], Ek * h[None, :], Eu @ (y_scale[:, None] * W_out)], axis=1)
+
+
+def mlp_sense_scores(Gr, sizes, activation, WH, P, T0, lo, hi, aux=None, max_iter=30, misfit_tol=1e-3) -> SenseResult:
+    """``sense_scores`` with the features psi = [1; t; last hidden layer] of the network ``sizes`` = [m, hidden ..] with
+    ``activation``, WH its hidden layers' flat parameters (``_mlp_split(WH, sizes)``: all W_l, outputs x inputs row-major, then
+    all b_l):  min over lo <= t <= hi of ||p - G_r psi(t)||^2 + perp2,  Gr (r, 1 + m + sizes[-1]) the reduced
+    ``mlp_sensing_matrix``.  The same iteration (``_sense_batch``), arguments and result; the specification of ``rom_mlp_sense``."""
+    Gr = np.asarray(Gr, dtype=np.float64)
+    sizes = [int(v) for v in sizes]
+    activation = "logistic" if activation == "sigmoid" else activation
+    if activation not in ("tanh", "logistic", "relu"):
+        raise ValueError(f"mlp_sense_scores: activation {activation!r}, one of 'tanh', 'logistic' ('sigmoid'), 'relu'")
+    layers = _mlp_split(np.asarray(WH, dtype=np.float64).ravel(), sizes)
+    assert Gr.shape[1] == 1 + sizes[0] + sizes[-1], f"mlp_sense_scores: Gr has {Gr.shape[1]} columns, 1 + m + H_L = {1 + sizes[0] + sizes[-1]}"
+    return _sense_queries(Gr, lambda th, jacobian: mlp_hidden_features(th, layers, activation, jacobian), sizes[0], P, T0, lo, hi, aux,
+                          max_iter, misfit_tol)
+
+
+class MLPSensing(PolynomialSensing):
+    """``PolynomialSensing`` for the decoder of a fitted ``MLPMap`` (the reference's "NN" model): the same protocol --
+
+        est = MLPSensing(sm, pca, mlp).observe(points).estimate(measurements, states=True)   # SensingEstimate
+
+    -- with the features psi(t) = [1; t; last hidden layer] in place of the Legendre products: the output layer and the target
+    scaling are part of the sensing matrix (``mlp_sensing_matrix``), the device estimate is ``rom_mlp_sense``, the host one
+    ``mlp_sense_scores``.  TypeError for anything that is not an MLPMap, ValueError for an unfitted map or components out of range."""
+
+    def __init__(self, sm, pca, mlp, known_start=0, unknown_start=None):
+        if not isinstance(mlp, MLPMap):
+            raise TypeError(f"MLPSensing needs an MLPMap, not {type(mlp).__name__} (PolynomialSensing takes a PolynomialMap)")
+        if mlp.map_ is None:
+            raise ValueError("MLPSensing needs a fitted MLPMap (fit / fit_columns comes first)")
+        self.sm, self.pca, self.poly = sm, pca, mlp
+        pm = mlp.map_
+        self.m, self.q, self.activation = pm.m, pm.q, pm.activation
+        self.hidden = tuple(pm.layout["sizes"][1:-1])
+        self.known_start = int(known_start)
+        self.unknown_start = self.known_start + self.m if unknown_start is None else int(unknown_start)
+        rows = pca.components_.rows if isinstance(pca.components_, DeviceArray) else np.shape(pca.components_)[0]
+        if self.known_start < 0 or self.unknown_start < 0 or max(self.known_start + self.m, self.unknown_start + self.q) > rows:
+            raise ValueError(f"MLPSensing: the components [{self.known_start}, {self.known_start + self.m}) and "
+                             f"[{self.unknown_start}, {self.unknown_start + self.q}) are not all among the {rows} of the PCA")
+        self.c, self.h, self.y_mean, self.y_scale = (pm.download(part) for part in ("c", "h", "y_mean", "y_scale"))
+        w, lay = pm.download("w"), pm.layout
+        nl, sizes = lay["layers"], lay["sizes"]
+        self.W_out = w[lay["w_offsets"][-1]:lay["w_offsets"][-1] + sizes[-1] * sizes[-2]].reshape(sizes[-1], sizes[-2]).copy()
+        self.b_out = w[lay["b_offsets"][-1]:lay["b_offsets"][-1] + sizes[-1]].copy()
+        # the hidden layers alone, in the flat order of _mlp_split(., [m, *hidden])
+        self.WH = np.concatenate([w[lay["w_offsets"][l]:lay["w_offsets"][l] + sizes[l + 1] * sizes[l]] for l in range(nl - 1)] +
+                                 [w[lay["b_offsets"][l]:lay["b_offsets"][l] + sizes[l + 1]] for l in range(nl - 1)])
+        self.sizes = [self.m, *self.hidden]
+        self.layers = _mlp_split(self.WH, self.sizes)
+        self.points = None
+
+    def _sensing_matrix(self):
+        return mlp_sensing_matrix(self.e0, self.Ek, self.Eu, self.c, self.h, self.y_mean, self.y_scale, self.W_out, self.b_out)
+
+    def observe(self, points, weights=None, extrapolate=0.5):
+        """As ``PolynomialSensing.observe``, with the sensing matrix ``mlp_sensing_matrix``; the hidden weights go to the device."""
+        from .inverse import reduce_sensors
+        sm, ctx, m, q = self.sm, self.sm._ctx, self.m, self.q
+        self.points = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+        ms = len(self.points)
+        self.weights = np.ones(ms) if weights is None else np.asarray(weights, dtype=np.float64).reshape(ms)
+        comps, mean = self.pca.components_, self.pca.mean_
+        comps = comps.numpy() if isinstance(comps, DeviceArray) else np.asarray(comps, dtype=np.float64)
+        mean = mean.numpy().ravel() if isinstance(mean, DeviceArray) else np.asarray(mean, dtype=np.float64).ravel()
+        rows = np.vstack([mean[None, :], comps[self.known_start:self.known_start + m], comps[self.unknown_start:self.unknown_start + q]])
+        E = np.asarray(sm.evaluate_solutions(self.points, rows))            # (1 + m + q, ms)
+        self.e0, self.Ek, self.Eu = E[0].copy(), E[1:1 + m].T.copy(), E[1 + m:].T.copy()
+        self.S = self._sensing_matrix()
+        self.U, Gr, _ = reduce_sensors(self.S.T, self.weights)
+        self.Gr_host, self.r = Gr, self.U.shape[1]
+        self.Gr, self.WH_dev = ctx.upload(Gr), ctx.upload(self.WH)
+        bound = 1.0 + float(extrapolate)
+        self.lo = np.where(self.h > 0.0, -bound, 0.0)
+        self.hi = np.where(self.h > 0.0, bound, 0.0)
+        return self
+
+    def predict_scores(self, t):
+        """y_mean + y_scale net(t): the predicted scores at the scaled coordinates t (K, m)."""
+        a = mlp_hidden_features(np.asarray(t, dtype=np.float64).reshape(-1, self.m), self.layers, self.activation, False)[0][:, 1 + self.m:]
+        return self.y_mean + self.y_scale * (a @ self.W_out.T + self.b_out)
+
+    def estimate(self, measurements, starts=None, device=True, states=False, max_iter=30, misfit_tol=1e-3) -> SensingEstimate:
+        """As ``PolynomialSensing.estimate``: ``device=True`` runs ``rom_mlp_sense`` (ValueError outside ``MLP_SENSE_LIMITS``),
+        ``device=False`` the host iteration ``mlp_sense_scores``; predicted_scores = y_mean + y_scale net(t)."""
+        from .inverse import reduce_measurements
+        if self.points is None:
+            raise RuntimeError("MLPSensing.observe(points) comes first")
+        ctx, m = self.sm._ctx, self.m
+        Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
+        K = len(Y)
+        zl = self.linear_scores(Y) if K else np.zeros((0, m))
+        if starts is None:
+            T0 = np.stack([self._scaled(zl), np.zeros((K, m))], axis=1)
+        else:
+            T0 = self._scaled(np.asarray(starts, dtype=np.float64).reshape(K, -1, m))
+        t = T0.shape[1]
+        Pq, aux = reduce_measurements(self.U, Y, self.weights)
+        if device:
+            _check_mlp_sense_limits(m, self.hidden, self.r, t)
+            res, _ = ctx.mlp_sense(m, self.hidden, self.activation, self.WH_dev, self.r, self.Gr, ctx.upload(Pq) if K else None, 0,
+                                   self.r, K, t, ctx.upload(np.ascontiguousarray(T0)) if K else None, self.lo, self.hi,
+                                   AUX=ctx.upload(aux) if K else None, max_iter=max_iter, misfit_tol=misfit_tol)
+        else:
+            res = mlp_sense_scores(self.Gr_host, self.sizes, self.activation, self.WH, Pq, T0, self.lo, self.hi, aux=aux,
+                                   max_iter=max_iter, misfit_tol=misfit_tol)
+        z = self.c + self.h * res.t
+        S = None
+        if states and K:
+            S = nonlinear_reconstruction(self.pca, self.poly, z, self.known_start, self.unknown_start, download=False)
+        return SensingEstimate(z, self.predict_scores(res.t), res.misfit, res.converged, res.iterations, res.sigma_min, res.start, zl, S)
