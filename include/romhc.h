@@ -611,6 +611,35 @@ int rom_mlp_sense(rom_ctx* ctx, int m, int n_hidden, const int* hidden, int acti
                   size_t p_off, int64_t ldp, int K, int t, rom_buf* T0, const double* lo_host, const double* hi_host, rom_buf* AUX,
                   int max_iter, double misfit_tol, rom_buf* OUT, size_t out_off, int64_t ldo, double* info8_host);
 
+/* ---- box-constrained least squares: linear state estimation that survives noise (src/lib/ReducedBasis.py:65-70) ----
+ * The linear state estimation of src/lib/ReducedBasis.py:65-70 with the coefficients kept inside a box (constrained
+ * stabilisation: the box the training snapshots' coefficients span).  For each of the K rows p of P (r columns from an element
+ * offset with a row stride)
+ *     min over lo <= c <= hi of ||p - G_r c||^2 + perp2
+ * with Gr (r x n row-major, full column rank) shared by all rows and AUX (K x 2) per row perp2 and scale (NULL: 0; the scale is
+ * not used) -- in reduced sensor coordinates Gr = Sigma V^T and p = U^T (w y) of the compact SVD diag(w) E^T = U Sigma V^T.
+ * Stark-Parker bounded-variable least squares with every decision fixed; romhighcontrast_amd/inverse.py::bvls_host is the same
+ * algorithm on the host.  Start: the unconstrained solution clipped to the box, what lands on a bound starts bound.  A pass
+ * solves the least squares on the free columns with the bound ones moved to the right-hand side (L D L^T of the free block of
+ * G^T G, one refinement step with the residual formed on the columns of Gr).  Feasible: it is taken, and with g = Gr^T (Gr c - p)
+ * the bound variable of largest |g_j| / ||G_j|| among those whose multiplier has the wrong sign (g_j < 0 at lo, g_j > 0 at hi) is
+ * freed, the lowest index among equals; none: the Karush-Kuhn-Tucker conditions hold, converged.  Infeasible: c moves along the
+ * segment to the solution up to the first bound hit, and what hits it is bound.  A variable freed in one pass that leaves through
+ * the same bound in the next is bound again and barred until another variable changes state.  At most max_iter passes
+ * (max_iter = 0 returns the clipped start).  lo_host / hi_host (n each): lo_j == hi_j PINS c_j bit for bit; lo_j = -inf and
+ * hi_j = +inf are allowed; lo_j > hi_j or NaN: ROM_ERR_INVALID.  One workgroup per row runs the whole iteration in one launch,
+ * after one kernel that forms G^T G.
+ * OUT row of p (ldo >= n + 4 doubles apart, from out_off): c (n) | misfit = sqrt(|p - G_r c|^2 + perp2) | number of bound
+ * variables | converged (0 / 1) | passes.  BOUND (K x n doubles, or NULL): -1 at lo, +1 at hi, 0 free; a pinned coordinate -1.
+ * 1 <= n <= 64, n <= r <= 96: ROM_ERR_INVALID outside, OUT unwritten; K = 0 is a no-op.  NaN / Inf in Gr or P, or a Gr without
+ * full column rank: ROM_ERR_INVALID, reported once.  No input buffer is modified; no floating-point atomics: the same bits on a
+ * repeated call.  Two launches, one host synchronisation.
+ * info8_host (8 doubles or NULL): kernel launches, host synchronisations, bytes of workspace, systems K, passes executed,
+ * factorisations executed (both summed on the device in integers), 0, 0. */
+int rom_bvls(rom_ctx* ctx, int n, int r, rom_buf* Gr, rom_buf* P, size_t p_off, int64_t ldp, int K, const double* lo_host,
+             const double* hi_host, rom_buf* AUX, int max_iter, rom_buf* OUT, size_t out_off, int64_t ldo, rom_buf* BOUND,
+             double* info8_host);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

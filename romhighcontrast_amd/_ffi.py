@@ -143,6 +143,8 @@ PROTOTYPES = {
                                  C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_mlp_sense": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp,
                                 _vp, _vp, _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
+    "rom_bvls": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_size_t,
+                           C.c_int64, _vp, _vp]),
     "rom_tree_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "rom_tree_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
@@ -455,6 +457,37 @@ class Context:
                           rows[:, m + 1].copy(), rows[:, m + 4].astype(np.int64))
         d8 = dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), systems=int(info[3]),
                   iterations=int(info[4]), evaluations=int(info[5]))
+        return res, d8
+
+    def bvls(self, n, r, Gr: "Buffer", P: "Buffer", p_off, ldp, K, lo, hi, AUX: "Buffer | None" = None, max_iter=None,
+             OUT: "Buffer | None" = None, out_off=0, ldo=None, bound=True):
+        """rom_bvls: inverse.bvls_host on the device -- for the K rows p of P (r columns from p_off with stride ldp)
+        min over lo <= c <= hi of ||p - Gr c||^2 with Gr (r, n) shared; AUX (K, 2) = perp2, scale or None; max_iter None: 5 n + 10.
+        lo_j == hi_j pins coordinate j, infinite bounds are allowed.  OUT (rows of ldo >= n + 4 from out_off: c | misfit | bound
+        variables | converged | passes) is allocated when None; ``bound`` False leaves BOUND out (the result's bound is then
+        None).  Returns (BvlsResult, info dict)."""
+        from .inverse import BvlsResult
+        n, K = int(n), int(K)
+        ldo = n + 4 if ldo is None else int(ldo)
+        max_iter = 5 * n + 10 if max_iter is None else int(max_iter)
+        lo = _host(np.broadcast_to(np.asarray(lo, dtype=np.float64), (n,)))
+        hi = _host(np.broadcast_to(np.asarray(hi, dtype=np.float64), (n,)))
+        if OUT is None and K > 0:
+            OUT = self.alloc(int(out_off) + K * ldo)
+        BOUND = self.alloc(K * n) if bound and K > 0 else None
+        info = np.zeros(8)
+        check(self.lib.rom_bvls(self.h, n, int(r), Gr.h, P.h if P is not None else None, int(p_off), int(ldp), K, lo.ctypes.data,
+                                hi.ctypes.data, AUX.h if AUX is not None else None, max_iter, OUT.h if OUT is not None else None,
+                                int(out_off), ldo, BOUND.h if BOUND is not None else None, info.ctypes.data))
+        rows = np.zeros((K, ldo))
+        if K:   # (the last row may end with the buffer, n + 4 doubles in)
+            rows.reshape(-1)[:(K - 1) * ldo + n + 4] = OUT.download((K - 1) * ldo + n + 4, offset=int(out_off))
+        st = None
+        if bound:
+            st = (BOUND.download(K * n).reshape(K, n) if K else np.zeros((0, n))).astype(np.int64)
+        res = BvlsResult(rows[:, :n].copy(), rows[:, n].copy(), st, rows[:, n + 2] != 0.0, rows[:, n + 3].astype(np.int64))
+        d8 = dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), systems=int(info[3]),
+                  passes=int(info[4]), factorisations=int(info[5]), bound_variables=rows[:, n + 1].astype(np.int64))
         return res, d8
 
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):

@@ -304,3 +304,171 @@ class ParameterLibrary:
             S = DeviceArray(out, K, dim)
         return ParameterEstimate(a.reshape((K,) + tuple(sm.blocks_geometry)), res.misfit, idx, start_misfit, res.converged,
                                  res.iterations, res.sigma_min, res.coefficients, bound, S)
+
+
+# ---- box-constrained least squares (Stark-Parker BVLS): the noise-robust linear state estimate ----------------------------------
+class BvlsResult(NamedTuple):
+    """``bvls_host`` / ``Context.bvls`` / ``bounded_lstsq``: c (K, n) inside the box; misfit (K,) = sqrt(||p - G c||^2 + perp2);
+    bound (K, n): -1 at lo, +1 at hi, 0 free (a pinned coordinate, lo_j == hi_j, reads -1); converged (K,): the Karush-Kuhn-Tucker
+    conditions were reached; iterations (K,): the passes made."""
+    c: np.ndarray
+    misfit: np.ndarray
+    bound: np.ndarray
+    converged: np.ndarray
+    iterations: np.ndarray
+
+
+BVLS_LIMITS = dict(n=64, r=96)   # rom_bvls (csrc/rom_bvls.hip): 1 <= n <= 64, n <= r <= 96
+
+
+def _check_bvls_limits(n, r):
+    if not (1 <= n <= BVLS_LIMITS["n"] and n <= r <= BVLS_LIMITS["r"]):
+        raise ValueError(f"the device solve (rom_bvls) needs 1 <= n <= {BVLS_LIMITS['n']} and n <= r <= {BVLS_LIMITS['r']}, got "
+                         f"n = {n}, r = {r}: use device=False (bvls_host)")
+
+
+def _bvls_box(lo, hi, n):
+    lo = np.array(np.broadcast_to(np.asarray(lo, dtype=np.float64), (n,)))
+    hi = np.array(np.broadcast_to(np.asarray(hi, dtype=np.float64), (n,)))
+    if np.isnan(lo).any() or np.isnan(hi).any() or (lo > hi).any() or np.isposinf(lo).any() or np.isneginf(hi).any():
+        raise ValueError("bvls: the box needs lo <= hi without NaN (lo may be -inf, hi +inf)")
+    return lo, hi
+
+
+def _bvls_solve(G, gram, free, rhs):
+    """z (B, n): the least squares of the rows of rhs (B, r) on the free columns of G (zero elsewhere): a Cholesky of the free
+    block of gram = G^T G, then one refinement step with the residual formed on the columns of G themselves."""
+    both = free[:, :, None] & free[:, None, :]
+    H = np.where(both, gram[None, :, :], 0.0) + (~free)[:, :, None] * np.eye(gram.shape[0])
+    L = np.linalg.cholesky(H)
+    Lt = np.ascontiguousarray(L.transpose(0, 2, 1))
+
+    def solve(b):
+        return np.linalg.solve(Lt, np.linalg.solve(L, b[..., None]))[..., 0]
+
+    z = solve(np.where(free, rhs @ G, 0.0))
+    return z + solve(np.where(free, (rhs - z @ G.T) @ G, 0.0))
+
+
+def bvls_host(G, P, lo, hi, aux=None, max_iter=None) -> BvlsResult:
+    """For each row p of P (K, r):  min over lo <= c <= hi of ||p - G c||^2  with G (r, n) of full column rank shared by all rows
+    -- Stark-Parker bounded-variable least squares, every decision fixed (``rom_bvls`` is its port); pure NumPy, batched over
+    the rows.
+
+    Start: the unconstrained solution clipped to the box; what lands on a bound starts bound, the rest free.  A PASS solves the
+    least squares on the free columns with the bound ones moved to the right-hand side (``_bvls_solve``).  Feasible: it is
+    taken, g = G^T (G c - p), and the bound variable whose multiplier has the wrong sign (g_j < 0 at lo, g_j > 0 at hi) with the
+    largest |g_j| / ||G_j|| is freed, the lowest index among equals; none: the Karush-Kuhn-Tucker conditions hold, ``converged``.
+    Infeasible: c moves along the segment to the solution up to the first bound hit, and the variables that hit it are bound.
+    A variable freed in one pass that leaves through the same bound in the next is bound again and BARRED from being freed
+    until some other variable changes state (a variable that stays free after being freed, or another one bound).  At most
+    max_iter passes (default 5 n + 10; 0 returns the clipped start).  lo_j == hi_j PINS c_j bit for bit (never freed, bound -1);
+    -inf / +inf bounds are never active.  aux (K, 2) = (perp2, scale) as in ``sense_scores``: misfit = sqrt(||p - G c||^2 + perp2).
+    ValueError: lo_j > hi_j or NaN in the box, NaN / Inf in G or P, or G without full column rank."""
+    G = np.asarray(G, dtype=np.float64)
+    r, n = G.shape
+    P = np.asarray(P, dtype=np.float64).reshape(-1, r)
+    K = len(P)
+    lo, hi = _bvls_box(lo, hi, n)
+    max_iter = 5 * n + 10 if max_iter is None else int(max_iter)
+    if not (np.isfinite(G).all() and np.isfinite(P).all()):
+        raise ValueError("bvls: NaN / Inf in G or P")
+    gram = G.T @ G
+    gn = np.sqrt(np.diag(gram))
+    try:
+        if r < n or not (gn > 0).all():
+            raise np.linalg.LinAlgError
+        np.linalg.cholesky(gram)
+    except np.linalg.LinAlgError:
+        raise ValueError(f"bvls: G ({r} x {n}) has no full column rank") from None
+    perp2 = np.zeros(K) if aux is None else np.asarray(aux, dtype=np.float64).reshape(K, 2)[:, 0]
+    pinned = lo == hi
+    rows = np.arange
+    with np.errstate(invalid="ignore", divide="ignore"):
+        start = _bvls_solve(G, gram, np.ones((K, n), dtype=bool), P)
+        c = np.minimum(np.maximum(start, lo), hi)
+        st = np.where(pinned | (start <= lo), -1, np.where(start >= hi, 1, 0))
+        barred = np.zeros((K, n), dtype=bool)
+        freed, side = np.full(K, -1), np.zeros(K, dtype=np.int64)
+        active, conv, passes = np.full(K, max_iter > 0), np.zeros(K, dtype=bool), np.zeros(K, dtype=np.int64)
+        for _ in range(max_iter):
+            ia = np.flatnonzero(active)
+            if ia.size == 0:
+                break
+            passes[ia] += 1
+            F = st[ia] == 0
+            z = np.where(F, _bvls_solve(G, gram, F, P[ia] - np.where(F, 0.0, c[ia]) @ G.T), c[ia])
+            below, above = F & (z < lo), F & (z > hi)
+            infeasible = (below | above).any(axis=1)
+            f = np.flatnonzero(~infeasible)
+            if f.size:   # the solution is taken; free the worst multiplier, or stop
+                i, zf = ia[f], z[f]
+                s = np.where(F[f] & (zf == lo), -1, np.where(F[f] & (zf == hi), 1, st[i]))   # (exactly on a bound: bound)
+                c[i] = zf
+                g = -((P[i] - zf @ G.T) @ G)
+                barred[i[freed[i] >= 0]] = False   # the variable freed in the last pass has stayed free
+                viol = np.where(s < 0, -g, g) / gn
+                cand = (s != 0) & ~pinned & ~barred[i] & (viol > 0)
+                viol = np.where(cand, viol, 0.0)
+                j = np.argmax(viol, axis=1)        # (the lowest index among equals)
+                go = cand.any(axis=1)
+                conv[i[~go]] = True
+                active[i[~go]] = False
+                freed[i] = np.where(go, j, -1)
+                side[i[go]] = s[go, j[go]]
+                s[go, j[go]] = 0
+                st[i] = s
+            f = np.flatnonzero(infeasible)
+            if f.size:   # to the first bound on the segment; what hits it is bound
+                i, zf, cf, Ff = ia[f], z[f], c[ia[f]], F[f]
+                ratio = np.where(below[f], (cf - lo) / (cf - zf), np.where(above[f], (hi - cf) / (zf - cf), np.inf))
+                alpha = ratio.min(axis=1, keepdims=True)
+                cn = np.minimum(np.maximum(cf + alpha * (zf - cf), lo), hi)
+                cn = np.where(ratio == alpha, np.where(below[f], lo, hi), cn)
+                cn = np.where(Ff, cn, cf)
+                s = np.where(Ff & (cn == lo), -1, np.where(Ff & (cn == hi), 1, st[i]))
+                changed = s != st[i]
+                fr = np.maximum(freed[i], 0)
+                same = (freed[i] >= 0) & changed[rows(len(i)), fr] & (s[rows(len(i)), fr] == side[i])
+                others = changed.sum(axis=1) > same
+                barred[i[others]] = False
+                barred[i[same], fr[same]] = True
+                freed[i] = -1
+                c[i], st[i] = cn, s
+        res = P - c @ G.T
+    misfit = np.sqrt(np.einsum("kr,kr->k", res, res) + perp2)
+    return BvlsResult(c, misfit, st.astype(np.int64), conv, passes)
+
+
+def coefficient_box(C, inflate=0.1):
+    """(lo, hi) (n each): min / max over the rows of a training coefficient matrix C (M, n), widened on both sides by
+    ``inflate`` times the range."""
+    C = np.asarray(C, dtype=np.float64)
+    C = C.reshape(-1, C.shape[-1])
+    lo, hi = C.min(axis=0), C.max(axis=0)
+    pad = float(inflate) * (hi - lo)
+    return lo - pad, hi + pad
+
+
+def bounded_lstsq(ctx, E, Y, lo, hi, weights=None, device=True) -> BvlsResult:
+    """min over lo <= c <= hi of ||w (y - E^T c)||_2 for the K rows y of Y (K, m): E (n, m) the basis at the sensors, as in
+    ``polish_parameters``.  The sensors are reduced first -- diag(w) E^T = U S V^T, p = U^T (w y), G_r = S V^T (``reduce_sensors``
+    / ``reduce_measurements``) -- so the solve works on r = n rows and the part of w y outside the range of U enters the misfit
+    as a constant; ValueError when the rank is below n.  ``device``: ``rom_bvls`` on ``ctx`` (ValueError outside
+    ``BVLS_LIMITS``), else ``bvls_host`` (``ctx`` may be None).  c is in the coordinates of E's rows."""
+    E = np.asarray(E, dtype=np.float64)
+    n, m = E.shape
+    Y = np.asarray(Y, dtype=np.float64).reshape(-1, m)
+    K = len(Y)
+    lo, hi = _bvls_box(lo, hi, n)
+    w = np.ones(m) if weights is None else np.asarray(weights, dtype=np.float64).reshape(m)
+    U, Gr, _ = reduce_sensors(E, w)
+    r = U.shape[1]
+    if r < n:
+        raise ValueError(f"bounded_lstsq: the {m} weighted sensors determine {r} of the {n} coefficients (rank of diag(w) E^T below n)")
+    Pq, aux = reduce_measurements(U, Y, w)
+    if not device:
+        return bvls_host(Gr, Pq, lo, hi, aux=aux)
+    _check_bvls_limits(n, r)
+    res, _ = ctx.bvls(n, r, ctx.upload(Gr), ctx.upload(Pq) if K else None, 0, r, K, lo, hi, AUX=ctx.upload(aux) if K else None)
+    return res

@@ -106,7 +106,7 @@ def _pbdw_bad_points(G):
     return sorted(bad)
 
 
-def pbdw_solve(G, L, Y, A_V=None):
+def pbdw_solve(G, L, Y, A_V=None, bounds=None, solver=None):
     """PBDW coefficients on the host.  G (m, m): H^1_0 Gram matrix of the sensors' Riesz representers; L (m, n):
     L[i, j] = l_i(C_j) (``evaluate_solutions(points, basis).T``); Y (K, m): measurements of K states; A_V (n, n), optional:
     H^1_0 Gram matrix of the basis rows.
@@ -114,6 +114,10 @@ def pbdw_solve(G, L, Y, A_V=None):
     G = R^T R (Cholesky), B = R^-T L, y~ = R^-T Y^T; c = argmin ||y~ - B c|| (QR), d = R^-1 (y~ - B c).  With
     A_V = K K^T, beta[n' - 1] = sigma_min((B K^-T)[:, :n']) for n' = 1 .. n: the inf-sup constant of V_n' against the
     sensor space (the Cholesky factors nest, so every prefix is the constant of the first n' rows).
+
+    bounds = (lo, hi) (n each, or scalars): the c-step becomes  argmin over lo <= c <= hi of ||y~ - B c||  (``inverse.bvls_host``,
+    or ``solver(B, y~^T, lo, hi)`` returning a ``BvlsResult``); d = R^-1 (y~ - B c) as before, so the estimate still interpolates
+    the measurements.  None: the unconstrained c.
 
     Returns (c (n, K), d (m, K), beta (n,) or None without A_V).  Raises ValueError if n > m, G is not numerically SPD
     (coincident points, or a point on the boundary: named), B is rank-deficient, or A_V is not SPD."""
@@ -145,8 +149,13 @@ def pbdw_solve(G, L, Y, A_V=None):
         if not sv[-1] > _PBDW_RANK_TOL * sv[0]:
             raise ValueError(f"the basis is not determined by the measurements: B = R^-T L is rank-deficient "
                              f"(sigma_min / sigma_max = {sv[-1] / sv[0] if sv[0] > 0 else 0.0:.2e})")
-        Q, RB = np.linalg.qr(B)
-        c = sla.solve_triangular(RB, Q.T @ yt, lower=False)
+        if bounds is None:
+            Q, RB = np.linalg.qr(B)
+            c = sla.solve_triangular(RB, Q.T @ yt, lower=False)
+        else:
+            if solver is None:
+                from ..inverse import bvls_host as solver
+            c = np.ascontiguousarray(solver(B, np.ascontiguousarray(yt.T), bounds[0], bounds[1]).c.T)
         res = yt - B @ c
     else:
         c = np.zeros((0, Y.shape[0]))
@@ -195,17 +204,22 @@ def _pbdw_operators(sm: SolutionsManager, basis, measurement_points, representer
     return C, Om, G, L, A_V
 
 
-def pbdw_state_estimation(sm: SolutionsManager, basis, measurement_points, measurements, device=False) -> PBDWResult:
+def pbdw_state_estimation(sm: SolutionsManager, basis, measurement_points, measurements, device=False, bounds=None) -> PBDWResult:
     """PBDW estimates of the K states measured at the m points (measurements (K, m), one row per state) with the
     background space spanned by the n rows of ``basis`` (ndarray or DeviceArray; n = 0 gives the minimum-norm interpolant
     Omega^T G^-1 y).  G, Omega, L and A_V are formed on the device, the (m + n)-sized problem is solved on the host
     (``pbdw_solve``), and the estimates are lifted on the device as c^T C + d^T Omega (two MFMA products into one buffer).
-    ``estimates`` is a DeviceArray if ``device``, else an ndarray."""
+    ``estimates`` is a DeviceArray if ``device``, else an ndarray.  bounds = (lo, hi): the coefficients c stay inside that box
+    (``pbdw_solve``; the bounded c-step runs on the device, ``rom_bvls``)."""
     ctx, dim = sm._ctx, sm.vspace_dim
     C, Om, G, L, A_V = _pbdw_operators(sm, basis, measurement_points)
     m, n = G.shape[0], L.shape[1]
     Y = np.asarray(measurements, dtype=np.float64).reshape(-1, m) if m else np.asarray(measurements).reshape(-1, 0)
-    c, d, beta = pbdw_solve(G, L, Y, A_V)
+    solver = None
+    if bounds is not None and n:
+        from ..inverse import bounded_lstsq
+        solver = lambda B, Yt, lo, hi: bounded_lstsq(ctx, B.T, Yt, lo, hi)
+    c, d, beta = pbdw_solve(G, L, Y, A_V, bounds=bounds, solver=solver)
     K = Y.shape[0]
     est = ctx.alloc(max(K * dim, 1))
     if K and n:
@@ -381,21 +395,45 @@ class BaseReducedBasis:
         """(:62-63) H^1_0-orthogonal projections of ``true_solutions``."""
         return sm.project_solutions(true_solutions, self.basis)
 
+    def coefficient_bounds(self, sm: SolutionsManager, training_solutions, inflate=0.1):
+        """(lo, hi) (dim each): the box that the coefficients of the H^1_0 projections of ``training_solutions`` on the basis
+        rows span, widened by ``inflate`` times its range (``inverse.coefficient_box``) -- the ``bounds`` of ``state_estimation``
+        and ``state_estimation_pbdw``.  The Gram matrix C A_1 C^T and the moments U A_1 C^T are formed on the device."""
+        from ..inverse import coefficient_box
+        ctx, dim, n = sm._ctx, sm.vspace_dim, self.dim
+        C, U = _as_device(ctx, self.basis, dim), _as_device(ctx, training_solutions, dim)
+        AC, AV, R = ctx.alloc(n * dim), ctx.alloc(n * n), ctx.alloc(U.rows * n)
+        sm._fem.stencil_apply(C.buf, n, AC)
+        ctx.gemm_nt(n, n, dim, AC, 0, dim, C.buf, 0, dim, AV, 0, n)
+        ctx.gemm_nt(U.rows, n, dim, U.buf, 0, dim, AC, 0, dim, R, 0, n)
+        A_V = AV.download(n * n, shape=(n, n))
+        coef = np.linalg.solve(0.5 * (A_V + A_V.T), R.download(U.rows * n, shape=(U.rows, n)).T).T
+        return coefficient_box(coef, inflate)
+
     def state_estimation(self, sm: SolutionsManager, measurement_points: np.ndarray, measurements: np.ndarray,
-                         return_coefs=False):
+                         return_coefs=False, bounds=None, device=True):
         """(:65-70) fit the basis coefficients to point measurements: the basis is evaluated at the
-        measurement points on the device, the (points x n) least-squares problem is solved on the host."""
+        measurement points on the device, the (points x n) least-squares problem is solved on the host.
+        bounds = (lo, hi) (``coefficient_bounds``): the coefficients stay inside that box -- ``inverse.bounded_lstsq``, on the
+        device (``rom_bvls``) or with ``device=False`` on the host; on noisy measurements the unconstrained fit amplifies the
+        noise by 1 / sigma_min(E)."""
         E = sm.evaluate_solutions(measurement_points, self.basis)          # (n, points)
+        if bounds is not None:
+            from ..inverse import bounded_lstsq
+            c = np.ascontiguousarray(bounded_lstsq(sm._ctx, E, np.asarray(measurements, dtype=np.float64).reshape(-1, E.shape[1]),
+                                                   bounds[0], bounds[1], device=device).c.T)
+            estimates = c.T @ np.array(self.basis)
+            return (c, estimates) if return_coefs else estimates
         c, *_ = np.linalg.lstsq(E.T, measurements.T, rcond=-1)              # (n, n_measured_states)
         estimates = c.T @ np.array(self.basis)
         return (c, estimates) if return_coefs else estimates
 
     def state_estimation_pbdw(self, sm: SolutionsManager, measurement_points: np.ndarray, measurements: np.ndarray,
-                              return_coefs=False):
+                              return_coefs=False, bounds=None):
         """PBDW state estimation (``pbdw_state_estimation``): the estimates interpolate the measurements and differ from
         the basis span by an H^1_0-orthogonal correction in the span of the sensors' Riesz representers.  c (n, K) as in
-        ``state_estimation``, so the parameter estimators accept it unchanged."""
-        r = pbdw_state_estimation(sm, self.basis, measurement_points, measurements)
+        ``state_estimation``, so the parameter estimators accept it unchanged.  bounds = (lo, hi): c stays inside that box."""
+        r = pbdw_state_estimation(sm, self.basis, measurement_points, measurements, bounds=bounds)
         return (r.c, r.estimates) if return_coefs else r.estimates
 
     def pbdw_stability(self, sm: SolutionsManager, measurement_points: np.ndarray):

@@ -533,6 +533,7 @@ def sensing_matrix(e0, Ek, Eu, c, h, W, powers):
 
 
 SENSE_LIMITS = dict(m=16, d=8, P=96, r=96, t=8)   # rom_poly_sense (csrc/rom_sense.hip)
+from .inverse import BVLS_LIMITS  # noqa: E402,F401  rom_bvls (csrc/rom_bvls.hip), the linear estimators' limits: defined in inverse.py
 _SENSE_CHUNK = 4096                                # systems of one batch of the host iteration
 
 
