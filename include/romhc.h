@@ -154,7 +154,8 @@ int rom_h10norm(rom_fem* fem, rom_buf* U, int64_t u_row0, rom_buf* V, int64_t v_
 int rom_l2norm(rom_ctx* ctx, rom_buf* U, int64_t row0, int K, int64_t dim, double* out_host);
 
 /* ---- dense fp64 contractions on MFMA (v_mfma_f64_16x16x4_f64) --------------------------- */
-/* C[m,n] = alpha * sum_k A[m,k] B[n,k] + beta*C   (row-major, "NT": Gram / C A U^T) */
+/* C[m,n] = alpha * sum_k A[m,k] B[n,k] + beta*C   (row-major, "NT": Gram / C A U^T).  rom_gemm_nt and rom_gemm_nn run a
+ * product of more than 65535 * 64 rows in row blocks of that many (their 64-row tiles are one grid dimension). */
 int rom_gemm_nt(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alpha, rom_buf* A, size_t a_off,
                 int64_t lda, rom_buf* B, size_t b_off, int64_t ldb, double beta, rom_buf* C, size_t c_off,
                 int64_t ldc);
@@ -319,7 +320,8 @@ int rom_h10norm_factored(rom_fem* fem, rom_buf* Yc, int64_t c_row0, int M, doubl
 /* rom_greedy on compact interface vectors (M x Kc); a: M x nrb*ncb parameters (mode 1) */
 int rom_greedy_factored(rom_fem* fem, rom_buf* Yc, int64_t c_row0, int M, rom_buf* a, const double* h1norm_host, int mode,
                         int n, int64_t* picks_out, double* max_err_out);
-/* rom_pod on compact interface vectors (M x Kc, not modified): V[v_row0 ...] receives the n modes as ROWS (n x dim) */
+/* rom_pod on compact interface vectors (M x Kc, not modified): V[v_row0 ...] receives the n modes as ROWS (n x dim);
+ * n <= 65535 (here and in rom_pod_h10_factored): ROM_ERR_INVALID beyond */
 int rom_pod_factored(rom_fem* fem, rom_buf* Yc, int64_t c_row0, int M, int n, int center, rom_buf* V, int64_t v_row0,
                      double* sigma_host, double* info_host);
 /* ---- the H^1_0 inner product in spectral form: POD in the energy norm -----------------------------------------------------
@@ -538,9 +540,10 @@ int rom_tree_destroy(rom_tree* h);
  * point atomics: the same bits on a repeated call.
  * mode 0: screened search -- scores |q~|^2 - 2 p~ . q~ on operands shifted by the library's column means, one MFMA kernel that
  * writes only the minimum of every group of G = 32 rows and query (K x ceil(M / 32) doubles, the queries in passes when that
- * would exceed the workspace limit); per query the T' = t + 4 groups of smallest minima are rescored exactly, and a certificate
- * with a proven bound on the screen's error decides whether the rows not rescored can be excluded; the queries it does not
- * certify go to the exhaustive kernel.  mode 1 (test hook): the exhaustive kernel for every query.
+ * would exceed the workspace limit or 65535 tables (128 queries per table, 64 when r > 64)); per query the T' = t + 4 groups
+ * of smallest minima are rescored exactly, and a certificate with a proven bound on the screen's error decides whether the
+ * rows not rescored can be excluded; the queries it does not certify go to the exhaustive kernel.  mode 1 (test hook): the
+ * exhaustive kernel for every query.
  * info_host (8 doubles or NULL): G, T', queries certified by the screen, queries sent to the exhaustive kernel, kernel launches,
  * host synchronisations, bytes of workspace, executed flops. */
 int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, int64_t M, rom_buf* P, size_t p_off, int64_t ldp, int K, int r,

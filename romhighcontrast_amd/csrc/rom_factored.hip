@@ -727,6 +727,7 @@ int pod_factored(rom_fem* f, bool h10, const char* who, rom_buf* Yc, int64_t c_r
                  int64_t v_row0, double* sigma_host, double* info_host) {
   ROM_CHECK(f && Yc && V && (sigma_host || n == 0), "%s: null argument", who);
   ROM_CHECK(M >= 1 && n >= 0 && c_row0 >= 0 && v_row0 >= 0, "%s: bad sizes", who);
+  ROM_CHECK(n <= 65535, "%s: n = %d modes, at most 65535 (kf_scatter_pivots takes them in one grid dimension)", who, n);
   const int64_t dim = f->dim;
   ROM_CHECK(n <= std::min<int64_t>(M, dim), "%s: %d modes requested from a %d x %lld block", who, n, M, (long long)dim);
   ROM_CHECK(size_t(v_row0 + n) * dim <= V->n, "%s: mode buffer too small", who);

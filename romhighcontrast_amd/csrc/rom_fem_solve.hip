@@ -257,6 +257,9 @@ static int solve_batch_impl(rom_fem* f, rom_buf* a, int M, rom_buf* U, int64_t r
   // chunk the sweep so that the factor workspace respects the budget
   size_t per_sys = (size_t(f->nslots) * 4096 + size_t(f->T) * 4096 + 2 * size_t(f->nGp)) * sizeof(double);
   int Mc_max = int(std::max<size_t>(1, std::min<size_t>(size_t(M), ctx->ws_limit / std::max<size_t>(per_sys, 1))));
+  // ... and so that the systems of a chunk fit one grid dimension (k_scatter_interface takes them one by one in grid.y, the
+  // expansion and extension kernels by 64)
+  Mc_max = std::min(Mc_max, 65535);
   if (f->ws_M > 0 && f->ws_M < Mc_max && f->ws_M >= 256) Mc_max = f->ws_M;  // reuse what we have
   ROM_TRY(ensure_workspace(f, Mc_max));
   const size_t lds_back = size_t(std::max(f->nGa, 1)) * sizeof(double);

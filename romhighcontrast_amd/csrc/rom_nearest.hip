@@ -346,18 +346,18 @@ __global__ __launch_bounds__(256) void k_nn_select(const double* __restrict__ Q,
 }
 
 // ---- the exhaustive scan ----------------------------------------------------------------------------------------------------
-// grid (row chunks, blocks of NN_QB listed queries), 256 threads.  Library tiles of 64 rows go through LDS (a lane per row, odd
-// stride); wave w scores its four queries against the tile with nn_dist2 and offers the results to its running top-t lists.
+// grid (row chunks, blocks of NN_QB listed queries from block qb0 on), 256 threads.  Library tiles of 64 rows go through LDS (a
+// lane per row, odd stride); wave w scores its four queries against the tile with nn_dist2 and offers the results to its running top-t lists.
 // part[(query slot, chunk)][t] receives the chunk's list.
 __global__ __launch_bounds__(256) void k_nn_exhaust(const double* __restrict__ Q, long long ldq, long long M, const double* __restrict__ P,
-                                                    long long ldp, const int* __restrict__ list, int nlist, int r, int t,
+                                                    long long ldp, const int* __restrict__ list, int nlist, int qb0, int r, int t,
                                                     long long rows_per_chunk, double* __restrict__ part_d, long long* __restrict__ part_j) {
   extern __shared__ double nn_lds[];
   const int LQ = r | 1;
   double* Ps = nn_lds;            // NN_QB x r
   double* Qs = Ps + NN_QB * r;    // NN_TILE x LQ
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int qb = blockIdx.y * NN_QB;
+  const int qb = (qb0 + int(blockIdx.y)) * NN_QB;
   for (int e = tid; e < NN_QB * r; e += 256) {
     const int n = e / r, c = e - n * r;
     Ps[e] = P[(long long)list[min(qb + n, nlist - 1)] * ldp + c];
@@ -483,7 +483,8 @@ extern "C" int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, 
   const long long k_fit = (long long)(ctx->ws_limit / (size_t(ngs) * sizeof(double))) / nq_tab * nq_tab;
   const bool screened = mode == 0 && k_fit >= nq_tab;
   if (screened) {
-    const int kc = int(std::min<long long>(k_fit, (K + nq_tab - 1) / nq_tab * nq_tab));
+    // (and at most 65535 tables per pass: they are the workgroups of grid.y)
+    const int kc = int(std::min<long long>({k_fit, (K + nq_tab - 1) / nq_tab * nq_tab, 65535LL * nq_tab}));
     const SlabPlan sp = rom_slab_plan(ctx, M, r);
     const long long per = (sp.per_chunk + NN_SLOTS - 1) / NN_SLOTS * NN_SLOTS;
     const int chunks = int((nslabs + per - 1) / per);
@@ -545,7 +546,11 @@ extern "C" int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, 
     if (lds > 64 * 1024) ROM_TRY(rom_lds_optin(ctx->lds_optin_nn_exhaust, reinterpret_cast<const void*>(k_nn_exhaust), 96 * 1024));
     {
       ROM_PROF(ctx, "nn_exhaust", 3.0 * double(nqb) * NN_QB * double(M) * r, 8.0 * double(nqb) * double(M) * r);
-      k_nn_exhaust<<<dim3(chunks, nqb), 256, lds, ctx->stream>>>(q, ldq, M, p, ldp, d_list, nlist, r, t, rows_per, part_d, part_j);
+      for (int b0 = 0; b0 < nqb; b0 += 65535) {  // grid.y holds at most 65535 query blocks per launch
+        k_nn_exhaust<<<dim3(chunks, std::min(65535, nqb - b0)), 256, lds, ctx->stream>>>(q, ldq, M, p, ldp, d_list, nlist, b0, r, t, rows_per,
+                                                                                        part_d, part_j);
+        launches += 1;
+      }
     }
     ROM_HIP(hipGetLastError());
     {
@@ -553,7 +558,7 @@ extern "C" int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, 
       k_nn_merge<<<nlist, 64, 0, ctx->stream>>>(part_d, part_j, chunks, d_list, t, res_d, res_j);
     }
     ROM_HIP(hipGetLastError());
-    launches += 2;
+    launches += 1;
     executed += 3.0 * double(nlist) * double(M) * r;
   }
   if (!screened) ROM_HIP(hipMemcpyAsync(hstat.data(), stat.p() + NN_RMAX, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -505,6 +505,8 @@ static void dispatch_mi(int64_t rows, Launch launch) {
   }
 }
 
+constexpr int64_t GEMM_MAX_ROWS = int64_t(65535) * 64;  // rows of C per launch of the 64 x 64 engines (row tiles in grid.y)
+
 // A/B switch (read once): the 64 x 64 register-staged engine for the thin shapes too
 static bool no_thin_gemm() {
   static const bool off = getenv("ROMHC_NO_THIN_GEMM") != nullptr;
@@ -552,6 +554,12 @@ int rom_launch_gemm_nt_ex(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double 
       size_t(lda) * 8 * 128 < (size_t(1) << 32) && !no_thin_gemm())  // thin B: the transposed product on the same kernel
     return launch_gemm_nt_thin(ctx, n, m, k, alpha, B, ldb, A, lda, beta, C, ldc, prof_name, 1);
   const long long nt = (m + 63) / 64;
+  if (!lower_only && nt > 65535) {  // grid.y holds at most 65535 row tiles per launch: row blocks, each a product of its own
+    for (int64_t m0 = 0; m0 < m; m0 += GEMM_MAX_ROWS)
+      ROM_TRY(rom_launch_gemm_nt_ex(ctx, std::min(GEMM_MAX_ROWS, m - m0), n, k, alpha, A + m0 * lda, lda, B, ldb, beta, C + m0 * ldc, ldc,
+                                    prof_name, 0));
+    return ROM_OK;
+  }
   const long long tiles = lower_only ? nt * (nt + 1) / 2 : nt * ((n + 63) / 64);  // tiles that do work
   long long want = 1;
   if (k >= 1024 && tiles < 512) {
@@ -813,6 +821,12 @@ int rom_launch_gemm_nn(rom_ctx* ctx, int64_t m, int64_t n, int64_t k, double alp
       k_gemm_nn_thin<decltype(mi)::value><<<grid, 256, 0, ctx->stream>>>(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
     });
     ROM_HIP(hipGetLastError());
+    return ROM_OK;
+  }
+  if (m > GEMM_MAX_ROWS) {  // grid.y holds at most 65535 row tiles per launch: row blocks, each a product of its own
+    for (int64_t m0 = 0; m0 < m; m0 += GEMM_MAX_ROWS)
+      ROM_TRY(rom_launch_gemm_nn(ctx, std::min(GEMM_MAX_ROWS, m - m0), n, k, alpha, A + m0 * lda, lda, B, ldb, beta, C + m0 * ldc, ldc,
+                                 part_ws, prof_name));
     return ROM_OK;
   }
   dim3 grid(unsigned((n + 63) / 64), unsigned((m + 63) / 64));
@@ -1376,8 +1390,11 @@ __global__ void k_rows_scale(double* __restrict__ X, long long dim, const double
 }
 
 int rom_launch_rows_scale(rom_ctx* ctx, double* X, int rows, int64_t dim, const double* d_fac) {
-  if (rows <= 0) return ROM_OK;
-  k_rows_scale<<<dim3(unsigned(std::min<int64_t>((dim + 255) / 256, 64)), rows), 256, 0, ctx->stream>>>(X, dim, d_fac);
+  const unsigned gx = unsigned(std::min<int64_t>((dim + 255) / 256, 64));
+  for (int r0 = 0; r0 < rows; r0 += 65535) {  // grid.y holds at most 65535 rows per launch
+    const int take = std::min(65535, rows - r0);
+    k_rows_scale<<<dim3(gx, unsigned(take)), 256, 0, ctx->stream>>>(X + size_t(r0) * dim, dim, d_fac + r0);
+  }
   ROM_HIP(hipGetLastError());
   return ROM_OK;
 }
@@ -1451,15 +1468,22 @@ __global__ void k_rows_sign_pivots(const double* __restrict__ X, long long dim, 
 
 int rom_launch_rows_sign_flip(rom_ctx* ctx, double* X, int rows, int64_t dim) {
   if (rows <= 0) return ROM_OK;
+  // grid.y holds at most 65535 rows per launch: the candidates of one launch's rows live in the scratch block, and the next
+  // launch's (stream order) take their place
+  const int cap = std::min(rows, 65535);
   double* ws = nullptr;
-  ROM_TRY(rom_ctx_scratch(ctx, size_t(3) * rows * SIGN_SEGS, &ws));
+  ROM_TRY(rom_ctx_scratch(ctx, size_t(3) * cap * SIGN_SEGS, &ws));
   double* pv = ws;
-  long long* pi = reinterpret_cast<long long*>(ws + size_t(rows) * SIGN_SEGS);
-  double* piv = ws + size_t(2) * rows * SIGN_SEGS;
-  const dim3 grid(SIGN_SEGS, unsigned(rows));
-  k_rows_sign_partial<<<grid, 256, 0, ctx->stream>>>(X, dim, pv, pi);
-  k_rows_sign_pivots<<<unsigned((rows * SIGN_SEGS + 255) / 256), 256, 0, ctx->stream>>>(X, dim, pi, piv, rows * SIGN_SEGS);
-  k_rows_sign_apply<<<grid, 256, 0, ctx->stream>>>(X, dim, pv, pi, piv);
+  long long* pi = reinterpret_cast<long long*>(ws + size_t(cap) * SIGN_SEGS);
+  double* piv = ws + size_t(2) * cap * SIGN_SEGS;
+  for (int r0 = 0; r0 < rows; r0 += cap) {
+    const int take = std::min(cap, rows - r0);
+    double* Xr = X + size_t(r0) * dim;
+    const dim3 grid(SIGN_SEGS, unsigned(take));
+    k_rows_sign_partial<<<grid, 256, 0, ctx->stream>>>(Xr, dim, pv, pi);
+    k_rows_sign_pivots<<<unsigned((take * SIGN_SEGS + 255) / 256), 256, 0, ctx->stream>>>(Xr, dim, pi, piv, take * SIGN_SEGS);
+    k_rows_sign_apply<<<grid, 256, 0, ctx->stream>>>(Xr, dim, pv, pi, piv);
+  }
   ROM_HIP(hipGetLastError());
   return ROM_OK;
 }
