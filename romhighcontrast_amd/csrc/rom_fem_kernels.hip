@@ -762,18 +762,28 @@ __device__ inline double rsqrt_newton(double d) {
 __device__ __host__ constexpr int s1_lrow(int r) { return 8 * (r >> 2) * ((r >> 2) + 1) + (r & 3) * 4 * ((r >> 2) + 1); }
 
 // One 64 x 4 panel of the blocked Cholesky of k_solve1 / k_diag_factor, in row-per-lane form (row r of the panel at
-// Pn[4 r]; c0 = its first column): on return v = row `lane` of L in these columns, y / myrs carry the forward substitution.
+// Pn[4 r]; c0 = its first column): on return v = row `lane` of L in these columns, y carries the forward substitution, rs =
+// the panel's four 1 / L_jj (the same numbers in every lane).
 // Round 4: every lane factorises the 4 x 4 diagonal block for itself (LDS broadcast reads of rows c0 .. c0 + 3, fetched
 // beside its own row) instead of receiving pivots and multipliers through v_readlane one column at a time -- 14
 // cross-lane broadcasts per panel, each at the end of a dependent chain (31 k of a wave's 82 k cycles), become straight
 // VALU code.  Same operations on the same numbers in the same order as the broadcast form: same bits.
+// The callers park rs in LDS panel by panel (chol_park_rs) and read 1 / L_jj of column `lane` back behind the factorisation:
+// a per-lane copy selected column by column (`if (lane == c) myrs = rs`) is 64 selects whose result nothing needs before
+// the end -- the compiler moved them all there, and kept 64 pivots in registers and 64 lane masks spilled into lanes of a
+// VGPR (v_writelane in every panel, v_readlane + select 64 times between factorisation and back substitution).
 // A non-positive (or NaN) pivot shows in its 1 / sqrt: lane j's myrs = 1 / L_jj is then not a finite positive number, and
 // every later one is NaN.  (Tested once, behind the factorisation: an or-chain over the 64 pivots kept them all alive.)
+// (every lane stores the same numbers to the same place: no branch, which would end the scheduler's region inside the panel)
+__device__ inline void chol_park_rs(double* dst, const double (&rs)[4]) {  // dst: 16-byte aligned LDS, 4 doubles
+  *reinterpret_cast<double2*>(dst) = double2{rs[0], rs[1]};
+  *reinterpret_cast<double2*>(dst + 2) = double2{rs[2], rs[3]};
+}
 __device__ inline bool chol_pivots_bad(double myrs) {
   return __builtin_amdgcn_ballot_w64(!(myrs > 0.0 && myrs < 1.0e300)) != 0;
 }
 // (the arithmetic; a00 .. a33: the lower triangle of the panel's 4 x 4 diagonal block, the same numbers in every lane)
-__device__ inline void chol_panel_core(int lane, int c0, double (&v)[4], double& y, double& myrs, double a00, double a10,
+__device__ inline void chol_panel_core(int lane, int c0, double (&v)[4], double& y, double (&rs)[4], double a00, double a10,
                                        double a11, double a20, double a21, double a22, double a30, double a31, double a32, double a33) {
   const double y0 = readlane_f64(y, c0);
   double y1 = readlane_f64(y, c0 + 1), y2 = readlane_f64(y, c0 + 2), y3 = readlane_f64(y, c0 + 3);
@@ -787,12 +797,8 @@ __device__ inline void chol_panel_core(int lane, int c0, double (&v)[4], double&
   {
     const double l = lane >= c0 ? v[0] * rs0 : 0.0;  // L[lane][c0]
     v[0] = l;
-    if (lane == c0) {
-      y = yd0;
-      myrs = rs0;
-    } else if (lane > c0) {
-      y -= l * yd0;
-    }
+    const double yu = __builtin_fma(-l, yd0, y);
+    y = lane == c0 ? yd0 : (lane > c0 ? yu : y);
     v[1] -= l * l10; v[2] -= l * l20; v[3] -= l * l30;
   }
   // column c0 + 1
@@ -804,12 +810,8 @@ __device__ inline void chol_panel_core(int lane, int c0, double (&v)[4], double&
   {
     const double l = lane >= c0 + 1 ? v[1] * rs1 : 0.0;
     v[1] = l;
-    if (lane == c0 + 1) {
-      y = yd1;
-      myrs = rs1;
-    } else if (lane > c0 + 1) {
-      y -= l * yd1;
-    }
+    const double yu = __builtin_fma(-l, yd1, y);
+    y = lane == c0 + 1 ? yd1 : (lane > c0 + 1 ? yu : y);
     v[2] -= l * l21; v[3] -= l * l31;
   }
   // column c0 + 2
@@ -821,12 +823,8 @@ __device__ inline void chol_panel_core(int lane, int c0, double (&v)[4], double&
   {
     const double l = lane >= c0 + 2 ? v[2] * rs2 : 0.0;
     v[2] = l;
-    if (lane == c0 + 2) {
-      y = yd2;
-      myrs = rs2;
-    } else if (lane > c0 + 2) {
-      y -= l * yd2;
-    }
+    const double yu = __builtin_fma(-l, yd2, y);
+    y = lane == c0 + 2 ? yd2 : (lane > c0 + 2 ? yu : y);
     v[3] -= l * l32;
   }
   // column c0 + 3
@@ -835,15 +833,12 @@ __device__ inline void chol_panel_core(int lane, int c0, double (&v)[4], double&
   {
     const double l = lane >= c0 + 3 ? v[3] * rs3 : 0.0;
     v[3] = l;
-    if (lane == c0 + 3) {
-      y = yd3;
-      myrs = rs3;
-    } else if (lane > c0 + 3) {
-      y -= l * yd3;
-    }
+    const double yu = __builtin_fma(-l, yd3, y);
+    y = lane == c0 + 3 ? yd3 : (lane > c0 + 3 ? yu : y);
   }
+  rs[0] = rs0; rs[1] = rs1; rs[2] = rs2; rs[3] = rs3;
 }
-__device__ inline void chol_panel_rows(const double* Pn, int lane, int c0, double (&v)[4], double& y, double& myrs) {
+__device__ inline void chol_panel_rows(const double* Pn, int lane, int c0, double (&v)[4], double& y, double (&rs)[4]) {
   {
     const double2 v01 = *reinterpret_cast<const double2*>(&Pn[lane * 4]);
     const double2 v23 = *reinterpret_cast<const double2*>(&Pn[lane * 4 + 2]);
@@ -855,11 +850,11 @@ __device__ inline void chol_panel_rows(const double* Pn, int lane, int c0, doubl
   const double a22 = Pn[(c0 + 2) * 4 + 2];
   const double2 r3a = *reinterpret_cast<const double2*>(&Pn[(c0 + 3) * 4]);
   const double2 r3b = *reinterpret_cast<const double2*>(&Pn[(c0 + 3) * 4 + 2]);
-  chol_panel_core(lane, c0, v, y, myrs, a00, r1.x, r1.y, r2.x, r2.y, a22, r3a.x, r3a.y, r3b.x, r3b.y);
+  chol_panel_core(lane, c0, v, y, rs, a00, r1.x, r1.y, r2.x, r2.y, a22, r3a.x, r3a.y, r3b.x, r3b.y);
 }
 // the same with the panel already in registers (v: row `lane`); the diagonal block comes from its four lanes
-__device__ inline void chol_panel_regs(int lane, int c0, double (&v)[4], double& y, double& myrs) {
-  chol_panel_core(lane, c0, v, y, myrs, readlane_f64(v[0], c0), readlane_f64(v[0], c0 + 1), readlane_f64(v[1], c0 + 1),
+__device__ inline void chol_panel_regs(int lane, int c0, double (&v)[4], double& y, double (&rs)[4]) {
+  chol_panel_core(lane, c0, v, y, rs, readlane_f64(v[0], c0), readlane_f64(v[0], c0 + 1), readlane_f64(v[1], c0 + 1),
                   readlane_f64(v[0], c0 + 2), readlane_f64(v[1], c0 + 2), readlane_f64(v[2], c0 + 2), readlane_f64(v[0], c0 + 3),
                   readlane_f64(v[1], c0 + 3), readlane_f64(v[2], c0 + 3), readlane_f64(v[3], c0 + 3));
 }
@@ -910,7 +905,6 @@ __device__ inline void diag_factor_body(const FemDev& f, int m, int slot, int j,
         C[ib][jb][g] = Lt[max(R, Cc) * 64 + min(R, Cc)];
       }
   double y = f.y[size_t(m) * f.nGp + j * 64 + lane];
-  double myrs = 0.0;
 #ifdef ROMHC_DIAGF_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -925,8 +919,9 @@ __device__ inline void diag_factor_body(const FemDev& f, int m, int slot, int j,
         for (int g = 0; g < 4; ++g) Pn[(16 * ib + 4 * g + l4) * 4 + (l16 - co)] = C[ib][jb][g];
     }
     __builtin_amdgcn_wave_barrier();
-    double v[4];
-    chol_panel_rows(Pn, lane, c0, v, y, myrs);
+    double v[4], rs[4];
+    chol_panel_rows(Pn, lane, c0, v, y, rs);
+    chol_park_rs(rinv + c0, rs);  // 1 / L_jj of the panel's columns
     __builtin_amdgcn_wave_barrier();
     *reinterpret_cast<double2*>(&Pn[lane * 4]) = double2{v[0], v[1]};
     *reinterpret_cast<double2*>(&Pn[lane * 4 + 2]) = double2{v[2], v[3]};
@@ -946,9 +941,8 @@ __device__ inline void diag_factor_body(const FemDev& f, int m, int slot, int j,
     __builtin_amdgcn_wave_barrier();
   }
   DF_STAMP(2);
-  if (chol_pivots_bad(myrs) && lane == 0) atomicOr(f.status, 1);
+  if (chol_pivots_bad(rinv[lane]) && lane == 0) atomicOr(f.status, 1);  // (rinv[lane] = 1 / L[lane][lane])
   f.y[size_t(m) * f.nGp + j * 64 + lane] = y;
-  rinv[lane] = myrs;  // 1 / L[lane][lane]
   __builtin_amdgcn_wave_barrier();
   // L (lower, zero above the diagonal) to HBM, coalesced
   tile_rows_to_global(Lt, Ls, lane);
@@ -1407,7 +1401,8 @@ __global__ __launch_bounds__(512) void k_solve1(FemDev f, const double* __restri
   // current one left them (`base`) -- this wave applies the current panel's update to them itself, on the vector pipe,
   // k in the order of the matrix instruction (same bits as the all-MFMA form).  One barrier per panel: factorised panel
   // and base are in LDS.
-  double myrs = 0.0;
+  // The panel's four 1 / L_jj go to zs (free between the rhs, read above, and the solution): the back substitution and the
+  // pivot test read them there.
 #ifdef ROMHC_SOLVE1_PANEL_STAMPS
   unsigned long long fwait = 0;
 #endif
@@ -1415,7 +1410,9 @@ __global__ __launch_bounds__(512) void k_solve1(FemDev f, const double* __restri
 #pragma unroll
   for (int p = 0; p < 16; ++p) {
     const int c0 = 4 * p;
-    chol_panel_regs(lane, c0, nv, y, myrs);
+    double rs[4];
+    chol_panel_regs(lane, c0, nv, y, rs);
+    chol_park_rs(zs + c0, rs);
     {  // the factorised panel: operand array of the update wave's MFMAs ...
       double* Pp = (p & 1) ? Pn1 : Pn;
       *reinterpret_cast<double2*>(&Pp[lane * 4]) = double2{nv[0], nv[1]};
@@ -1443,25 +1440,54 @@ __global__ __launch_bounds__(512) void k_solve1(FemDev f, const double* __restri
       for (int kk = 0; kk < 4; ++kk) nv[kk] = nn[kk];
     }
   }
-  if (chol_pivots_bad(myrs) && live && lane == 0) atomicOr(f.status, 1);
   S1_WAVE_SYNC();
+  if (chol_pivots_bad(zs[lane]) && live && lane == 0) atomicOr(f.status, 1);
   S1_STAMP(5);
-  // back substitution x = L^-T y.  Column `lane` of L is fetched from LDS in batches (conflict free), then the
-  // chain x_j = y_j / L_jj ; y_i -= L_ji x_j (i < j) runs on registers and readlane broadcasts only.
+  // back substitution x = L^-T y:  x_j = y_j / L_jj ; y_i -= L_ji x_j (i < j), j downwards, in blocks of four columns,
+  // every lane for itself: one batch of broadcasts brings the block's four y; its 4 x 4 triangle of L and its 1 / L_jj
+  // (in zs since the factorisation) come by LDS broadcast reads, and the lane's own four entries L[j][lane] with them,
+  // all asked for a block ahead (two and three ahead measured slower); each lane solves the triangle and applies the
+  // four updates to its own entry.  The same products in the same order as one column at a time (same bits), where every
+  // column paid two readlane pairs and two selects on the chain, and the chain stood still for each half's 32 loads of L.
+  {
+    double tri[16][10];  // per block: l10 l20 l21 l30 l31 l32, then the four 1 / L_jj (the same numbers in every lane)
+    double lc[16][4];    // per block: L[4 q + i][lane] for lane <= 4 q + i (beyond: padding or another row's entry, never used)
+    auto fetch_block = [&](int q) {
+      const int b = 4 * q;
+      const double2 r1 = *reinterpret_cast<const double2*>(&Ls[s1_lrow(b + 1) + b]);
+      const double2 r2 = *reinterpret_cast<const double2*>(&Ls[s1_lrow(b + 2) + b]);
+      const double2 r3 = *reinterpret_cast<const double2*>(&Ls[s1_lrow(b + 3) + b]);
+      const double l32 = Ls[s1_lrow(b + 3) + b + 2];
+      const double2 s01 = *reinterpret_cast<const double2*>(&zs[b]), s23 = *reinterpret_cast<const double2*>(&zs[b + 2]);
+      double (&t)[10] = tri[q];
+      t[0] = r1.x; t[1] = r2.x; t[2] = r2.y; t[3] = r3.x; t[4] = r3.y; t[5] = l32;
+      t[6] = s01.x; t[7] = s01.y; t[8] = s23.x; t[9] = s23.y;
 #pragma unroll
-  for (int h = 1; h >= 0; --h) {  // (in two halves: 64 registers of L at a time)
-    double lcol[32];
+      for (int i = 0; i < 4; ++i) lc[q][i] = Ls[s1_lrow(b + i) + lane];
+    };
+    fetch_block(15);
+    const bool odd = lane & 1, upper = lane & 2;
+    double u = y;    // the running entry: lanes below the current block
+    double x = 0.0;  // the finished entry: lanes of the blocks done
 #pragma unroll
-    for (int j = 0; j < 32; ++j) lcol[j] = Ls[s1_lrow(32 * h + j) + lane];  // L[j][lane] for lane <= j (beyond: padding or another row's entry, never used)
-#pragma unroll
-    for (int j = 31; j >= 0; --j) {
-      const int jj = 32 * h + j;
-      const double xj = readlane_f64(y, jj) * readlane_f64(myrs, jj);
-      if (lane == jj) y = xj;
-      else if (lane < jj) y -= lcol[j] * xj;
+    for (int q = 15; q >= 0; --q) {
+      if (q >= 1) fetch_block(q - 1);
+      const double (&t)[10] = tri[q];
+      const double y0 = readlane_f64(u, 4 * q), y1 = readlane_f64(u, 4 * q + 1), y2 = readlane_f64(u, 4 * q + 2), y3 = readlane_f64(u, 4 * q + 3);
+      const double x3 = y3 * t[9];
+      u = __builtin_fma(-lc[q][3], x3, u);
+      const double x2 = __builtin_fma(-t[5], x3, y2) * t[8];
+      u = __builtin_fma(-lc[q][2], x2, u);
+      const double x1 = __builtin_fma(-t[2], x2, __builtin_fma(-t[4], x3, y1)) * t[7];
+      u = __builtin_fma(-lc[q][1], x1, u);
+      const double x0 = __builtin_fma(-t[0], x1, __builtin_fma(-t[1], x2, __builtin_fma(-t[3], x3, y0))) * t[6];
+      u = __builtin_fma(-lc[q][0], x0, u);
+      const double xhi = odd ? x3 : x2, xlo = odd ? x1 : x0;
+      const double xs = upper ? xhi : xlo;
+      x = (lane >> 2) == q ? xs : x;
     }
+    zs[lane] = x;
   }
-  zs[lane] = y;
   S1_STAMP(6);
 #ifdef ROMHC_SOLVE1_STAMPS
 #pragma unroll
