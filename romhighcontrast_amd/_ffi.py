@@ -634,9 +634,52 @@ class Buffer:
             pass
 
 
-class PolyMap:
+class _MapHandle:
+    """What the handles of the fitted maps share.  A subclass names the prefix of its symbols (``<prefix>_predict``, ``_query``,
+    ``_destroy``) and the keys of its eight query words; its constructor sets ``ctx``, ``h`` (None until the fit has returned)
+    and ``q``."""
+
+    _PREFIX = ""
+    _QUERY_KEYS = ()
+    h = None
+
+    def _fn(self, name):
+        return getattr(self.ctx.lib, f"{self._PREFIX}_{name}")
+
+    def query(self) -> dict:
+        out = np.zeros(8, dtype=np.int64)
+        check(self._fn("query")(self.h, out.ctypes.data))
+        return {k: int(v) for k, v in zip(self._QUERY_KEYS, out)}
+
+    def predict(self, X: Buffer, x_off, ldx, M, OUT: "Buffer | None" = None, o_off=0, ldo=None, Yref: "Buffer | None" = None, r_off=0,
+                ldr=None, sumsq=False):
+        """rom_poly_predict / rom_mlp_predict / rom_tree_predict: OUT <- the prediction for the M rows of X, or Yref -
+        prediction; with ``sumsq`` returns the q column sums of squares of that (OUT may then be None: nothing of size M x q is
+        written)."""
+        ss = np.zeros(self.q) if sumsq else None
+        check(self._fn("predict")(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M),
+                                  OUT.h if OUT is not None else None, int(o_off), int(self.q if ldo is None else ldo),
+                                  Yref.h if Yref is not None else None, int(r_off), int(self.q if ldr is None else ldr),
+                                  ss.ctypes.data if sumsq else None))
+        return ss
+
+    def free(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PolyMap(_MapHandle):
     """Handle of a fitted polynomial map (rom_poly_*): owns the device coefficients, destroyed on collection."""
 
+    _PREFIX = "rom_poly"
+    _QUERY_KEYS = ("m", "d", "P", "q", "rank", "M_train", "passes", "host_syncs")
     _PARTS = {"c": 0, "h": 1, "W": 2, "dropped": 3}
 
     def __init__(self, ctx: Context, X: Buffer, x_off, ldx, m, Y: Buffer, y_off, ldy, q, M, degree, rcond=0.0):
@@ -652,12 +695,6 @@ class PolyMap:
                          pivot_ratio=float(info[4]), executed_flops=float(info[5]), host_syncs=int(info[6]),
                          stop_reason=("full_rank", "terms_dropped", "budget")[int(info[7])])
 
-    def query(self) -> dict:
-        out = np.zeros(8, dtype=np.int64)
-        check(self.ctx.lib.rom_poly_query(self.h, out.ctypes.data))
-        keys = ("m", "d", "P", "q", "rank", "M_train", "passes", "host_syncs")
-        return {k: int(v) for k, v in zip(keys, out)}
-
     def download(self, part: str) -> np.ndarray:
         """Host copy of "c" (m,), "h" (m,), "W" (q, P) or the "dropped" flags (P,)."""
         P = self.info["P"]
@@ -665,32 +702,12 @@ class PolyMap:
         check(self.ctx.lib.rom_poly_download(self.h, self._PARTS[part], out.ctypes.data, out.size))
         return out
 
-    def predict(self, X: Buffer, x_off, ldx, M, OUT: "Buffer | None" = None, o_off=0, ldo=None, Yref: "Buffer | None" = None, r_off=0,
-                ldr=None, sumsq=False):
-        """rom_poly_predict: OUT <- the prediction for the M rows of X, or Yref - prediction; with ``sumsq`` returns the q
-        column sums of squares of that (OUT may then be None: nothing of size M x q is written)."""
-        ss = np.zeros(self.q) if sumsq else None
-        check(self.ctx.lib.rom_poly_predict(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M),
-                                            OUT.h if OUT is not None else None, int(o_off), int(self.q if ldo is None else ldo),
-                                            Yref.h if Yref is not None else None, int(r_off), int(self.q if ldr is None else ldr),
-                                            ss.ctypes.data if sumsq else None))
-        return ss
 
-    def free(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.rom_poly_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class MLPHandle:
+class MLPHandle(_MapHandle):
     """Handle of a fitted MLP map (rom_mlp_*): owns the device weights and scalings, destroyed on collection."""
 
+    _PREFIX = "rom_mlp"
+    _QUERY_KEYS = ("m", "q", "hidden_layers", "P", "M_train", "iterations", "launches", "host_syncs")
     _PARTS = {"w": 0, "c": 1, "h": 2, "y_mean": 3, "y_scale": 4, "loss_curve": 5}
     _STOPS = ("gradient", "stagnation", "budget", "line_search")
 
@@ -722,12 +739,6 @@ class MLPHandle:
                          stop_reason=self._STOPS[int(info[4])], launches=int(info[5]), host_syncs=int(info[6]),
                          executed_flops=float(info[7]))
 
-    def query(self) -> dict:
-        out = np.zeros(8, dtype=np.int64)
-        check(self.ctx.lib.rom_mlp_query(self.h, out.ctypes.data))
-        keys = ("m", "q", "hidden_layers", "P", "M_train", "iterations", "launches", "host_syncs")
-        return {k: int(v) for k, v in zip(keys, out)}
-
     def download(self, part: str) -> np.ndarray:
         """Host copy of "w" (P,), "c", "h" (m,), "y_mean", "y_scale" (q,) or the "loss_curve" (iterations + 1,)."""
         n = {"w": self.P, "c": self.m, "h": self.m, "y_mean": self.q, "y_scale": self.q, "loss_curve": self.info["iterations"] + 1}[part]
@@ -749,31 +760,12 @@ class MLPHandle:
                                              float(self.alpha if alpha is None else alpha), loss.ctypes.data, grad.ctypes.data))
         return float(loss[0]), grad
 
-    def predict(self, X: Buffer, x_off, ldx, M, OUT: "Buffer | None" = None, o_off=0, ldo=None, Yref: "Buffer | None" = None, r_off=0,
-                ldr=None, sumsq=False):
-        """rom_mlp_predict: as ``PolyMap.predict``."""
-        ss = np.zeros(self.q) if sumsq else None
-        check(self.ctx.lib.rom_mlp_predict(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M),
-                                           OUT.h if OUT is not None else None, int(o_off), int(self.q if ldo is None else ldo),
-                                           Yref.h if Yref is not None else None, int(r_off), int(self.q if ldr is None else ldr),
-                                           ss.ctypes.data if sumsq else None))
-        return ss
 
-    def free(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.rom_mlp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class TreeMapHandle:
+class TreeMapHandle(_MapHandle):
     """Handle of a fitted tree / forest (rom_tree_*): owns the device node arrays, destroyed on collection."""
 
+    _PREFIX = "rom_tree"
+    _QUERY_KEYS = ("m", "q", "T", "M_train", "nodes", "deepest_level", "launches", "host_syncs")
     _PARTS = ("first", "feature", "threshold", "left", "count", "value")
 
     def __init__(self, ctx: Context, X: Buffer, x_off, ldx, m, Y: Buffer, y_off, ldy, q, M, T=1, counts=None, max_depth=None,
@@ -794,12 +786,6 @@ class TreeMapHandle:
         self.info = dict(nodes=int(info[0]), leaves=int(info[1]), deepest_level=int(info[2]), levels=int(info[3]),
                          launches=int(info[4]), host_syncs=int(info[5]), workspace_bytes=int(info[6]))
 
-    def query(self) -> dict:
-        out = np.zeros(8, dtype=np.int64)
-        check(self.ctx.lib.rom_tree_query(self.h, out.ctypes.data))
-        keys = ("m", "q", "T", "M_train", "nodes", "deepest_level", "launches", "host_syncs")
-        return {k: int(v) for k, v in zip(keys, out)}
-
     def nodes(self) -> dict:
         """Host copies of the node arrays, the trees one after the other (tree t: nodes first[t] .. first[t + 1] - 1, breadth
         first): "first" (T + 1,), "feature" (-1 at a leaf), "threshold", "left" (the right child is left + 1; -1 at a leaf),
@@ -811,28 +797,6 @@ class TreeMapHandle:
             check(self.ctx.lib.rom_tree_download(self.h, what, a.ctypes.data, a.size))
             out[part] = a.reshape(n, self.q) if what == 5 else a if what in (2, 4) else a.astype(np.int64)
         return out
-
-    def predict(self, X: Buffer, x_off, ldx, M, OUT: "Buffer | None" = None, o_off=0, ldo=None, Yref: "Buffer | None" = None, r_off=0,
-                ldr=None, sumsq=False):
-        """rom_tree_predict: as PolyMap.predict -- OUT <- the prediction for the M rows of X, or Yref - prediction; with
-        ``sumsq`` returns the q column sums of squares of that (OUT may then be None)."""
-        ss = np.zeros(self.q) if sumsq else None
-        check(self.ctx.lib.rom_tree_predict(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M),
-                                            OUT.h if OUT is not None else None, int(o_off), int(self.q if ldo is None else ldo),
-                                            Yref.h if Yref is not None else None, int(r_off), int(self.q if ldr is None else ldr),
-                                            ss.ctypes.data if sumsq else None))
-        return ss
-
-    def free(self):
-        if getattr(self, "h", None):
-            self.ctx.lib.rom_tree_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 _contexts = {}

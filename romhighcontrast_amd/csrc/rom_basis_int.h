@@ -50,6 +50,20 @@ int download(rom_ctx* ctx, const double* d, double* h, size_t n) {
   return ROM_OK;
 }
 
+// destroys a half-built handle on every way out of its *_fit but the one that releases it
+template <class H, int (*Destroy)(H*)>
+struct HandleGuard {
+  H* h;
+  ~HandleGuard() {
+    if (h) Destroy(h);
+  }
+  H* release() {
+    H* r = h;
+    h = nullptr;
+    return r;
+  }
+};
+
 // the points on the device: [ix | iy] as ints, then [tx | ty] (the host arrays are free after the next synchronisation)
 struct DevPoints {
   Tmp buf;
@@ -89,6 +103,29 @@ __global__ void kb_ints_to_doubles(const int* __restrict__ src, double* __restri
 __global__ void kb_partials_reduce(const double* __restrict__ Part, int chunks, int ppad, int ldp, int P, int qg,
                                    double* __restrict__ G, double* __restrict__ B, int q, int c0);
 __global__ void kb_partials_colsum(const double* __restrict__ part, int chunks, int n, double divisor, double* __restrict__ out);
+
+namespace {
+// The tail of the *_predict entry points.  With sums of squares wanted: get() before the launch, whose kernel writes one row of q
+// partials per chunk to partials(); finish() adds them in chunk order and copies the q sums to the host.  finish() ends the call
+// either way: it waits for the stream.  (The callers count their own launches and synchronisations.)
+struct SumsqTail {
+  Tmp SS, sums;
+  int get(rom_ctx* ctx, int chunks, int q) {
+    ROM_TRY(SS.get(ctx, size_t(chunks) * q));
+    return sums.get(ctx, q);
+  }
+  double* partials() const { return SS.b ? SS.p() : nullptr; }
+  int finish(rom_ctx* ctx, int chunks, int q, double* sumsq_host) {
+    if (SS.b) {
+      kb_partials_colsum<<<blocks_for(q), 256, 0, ctx->stream>>>(SS, chunks, q, 1.0, sums);
+      ROM_HIP(hipGetLastError());
+      ROM_HIP(hipMemcpyAsync(sumsq_host, sums.p(), size_t(q) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ROM_HIP(hipStreamSynchronize(ctx->stream));
+    return ROM_OK;
+  }
+};
+}  // namespace
 // (rom_pod.hip) out[0] = bits of the largest |x| among the finite entries, out[1] = number of entries that are not finite
 __global__ void kp_block_amax(const double* __restrict__ X, size_t count, unsigned long long* __restrict__ out);
 

@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "rom_basis_int.h"
+#include "rom_block.h"
 #include "rom_lm_small.h"
 
 namespace {
@@ -278,12 +279,9 @@ extern "C" int rom_bvls(rom_ctx* ctx, int n, int r, rom_buf* Gr, rom_buf* P, siz
   if (info8_host) std::fill(info8_host, info8_host + 8, 0.0);
   if (K == 0) return ROM_OK;
   ROM_CHECK(P && OUT, "rom_bvls: null argument (P or OUT)");
-  ROM_CHECK(ldp >= r, "rom_bvls: ldp = %lld < r = %d", (long long)ldp, r);
-  ROM_CHECK(p_off + size_t(K - 1) * size_t(ldp) + size_t(r) <= P->n, "rom_bvls: P holds %zu doubles, %d rows of %d at offset %zu with stride %lld need more",
-            P->n, K, r, p_off, (long long)ldp);
+  ROM_TRY(rom_check_block("rom_bvls", {"P", "ldp", "r"}, P->n, p_off, ldp, r, K));
   ROM_CHECK(!AUX || AUX->n >= 2 * size_t(K), "rom_bvls: AUX holds %zu doubles, 2 K = %zu needed", AUX ? AUX->n : 0, 2 * size_t(K));
-  ROM_CHECK(out_off + size_t(K - 1) * size_t(ldo) + size_t(n) + 4 <= OUT->n,
-            "rom_bvls: OUT holds %zu doubles, %d rows of %d at offset %zu with stride %lld need more", OUT->n, K, n + 4, out_off, (long long)ldo);
+  ROM_TRY(rom_check_block("rom_bvls", {"OUT", "ldo", "n + 4"}, OUT->n, out_off, ldo, n + 4, K));   // (ldo >= n + 4: checked above)
   ROM_CHECK(!BOUND || BOUND->n >= size_t(K) * n, "rom_bvls: BOUND holds %zu doubles, K n = %zu needed", BOUND ? BOUND->n : 0, size_t(K) * n);
   ROM_HIP(hipSetDevice(ctx->device));
 

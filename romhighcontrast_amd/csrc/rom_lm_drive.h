@@ -22,6 +22,7 @@
 //   work()            its work counter
 #pragma once
 #include "rom_basis_int.h"
+#include "rom_block.h"
 #include "rom_lm_small.h"
 
 namespace {
@@ -157,15 +158,11 @@ int lm_launch(rom_ctx* ctx, const LmCall& c, Launch&& launch) {
   if (c.info8_host) std::fill(c.info8_host, c.info8_host + 8, 0.0);
   if (K == 0) return ROM_OK;
   ROM_CHECK(c.P && c.STARTS && c.OUT, "%s: null argument (P, %s or OUT)", c.who, c.starts_name);
-  ROM_CHECK(c.ldp >= r, "%s: ldp = %lld < r = %d", c.who, (long long)c.ldp, r);
-  ROM_CHECK(c.p_off + size_t(K - 1) * size_t(c.ldp) + size_t(r) <= c.P->n,
-            "%s: P holds %zu doubles, %d rows of %d at offset %zu with stride %lld need more", c.who, c.P->n, K, r, c.p_off, (long long)c.ldp);
+  ROM_TRY(rom_check_block(c.who, {"P", "ldp", "r"}, c.P->n, c.p_off, c.ldp, r, K));
   ROM_CHECK(c.STARTS->n >= size_t(K) * t * c.width, "%s: %s holds %zu doubles, K t %s = %zu needed", c.who, c.starts_name, c.STARTS->n,
             c.width_name, size_t(K) * t * c.width);
   ROM_CHECK(!c.AUX || c.AUX->n >= 2 * size_t(K), "%s: AUX holds %zu doubles, 2 K = %zu needed", c.who, c.AUX ? c.AUX->n : 0, 2 * size_t(K));
-  ROM_CHECK(c.out_off + size_t(K - 1) * size_t(c.ldo) + size_t(row) <= c.OUT->n,
-            "%s: OUT holds %zu doubles, %d rows of %d at offset %zu with stride %lld need more", c.who, c.OUT->n, K, row, c.out_off,
-            (long long)c.ldo);
+  ROM_TRY(rom_check_block(c.who, {"OUT", "ldo", "its row"}, c.OUT->n, c.out_off, c.ldo, row, K));   // (ldo >= row: checked above)
   ROM_HIP(hipSetDevice(ctx->device));
 
   const int B = K * t, ldw = c.lead + 4;

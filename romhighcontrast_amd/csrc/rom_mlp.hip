@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "rom_basis_int.h"
+#include "rom_block.h"
 #include "rom_slab.h"
 
 namespace {
@@ -705,8 +706,6 @@ __global__ __launch_bounds__(ML_DIR_THREADS) void k_mlp_director(int P, int mem,
   }
 }
 
-bool ranges_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
-
 }  // namespace
 
 struct rom_mlp {
@@ -777,13 +776,6 @@ int mlp_enqueue_eval(rom_mlp* h, const double* x, int64_t ldx, const double* y, 
   return ROM_OK;
 }
 
-int mlp_check_block(const char* who, const char* name, rom_buf* B, size_t off, int64_t ld, int cols, int64_t M) {
-  ROM_CHECK(ld >= cols, "%s: the row stride of %s = %lld < its %d columns", who, name, (long long)ld, cols);
-  ROM_CHECK(off + size_t(M - 1) * size_t(ld) + size_t(cols) <= B->n, "%s: %s holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more",
-            who, name, B->n, (long long)M, cols, off, (long long)ld);
-  return ROM_OK;
-}
-
 }  // namespace
 
 extern "C" int rom_mlp_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q,
@@ -795,13 +787,13 @@ extern "C" int rom_mlp_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, 
   const char* why = "";
   ROM_CHECK(mlp_plan(m, n_hidden, hidden, q, &D, &le, &lp, &why), "rom_mlp_fit: m = %d, %d hidden layers, q = %d: %s", m, n_hidden, q, why);
   ROM_CHECK(activation >= 0 && activation <= 2, "rom_mlp_fit: activation = %d, one of 0 (tanh), 1 (logistic), 2 (relu)", activation);
-  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 40), "rom_mlp_fit: M = %lld rows, at least 1", (long long)M);
+  ROM_TRY(rom_check_rows("rom_mlp_fit", M));
   ROM_CHECK(alpha >= 0.0 && alpha <= ML_DBL_MAX, "rom_mlp_fit: alpha = %g, a finite number >= 0", alpha);
   ROM_CHECK(max_iter >= 0 && max_iter <= (1 << 20), "rom_mlp_fit: max_iter = %d, between 0 and 2^20", max_iter);
   ROM_CHECK(tol >= 0.0, "rom_mlp_fit: tol = %g, at least 0", tol);
   ROM_CHECK(memory >= 1 && memory <= ML_MEMMAX, "rom_mlp_fit: memory = %d pairs, between 1 and %d", memory, ML_MEMMAX);
-  ROM_TRY(mlp_check_block("rom_mlp_fit", "X", X, x_off, ldx, m, M));
-  ROM_TRY(mlp_check_block("rom_mlp_fit", "Y", Y, y_off, ldy, q, M));
+  ROM_TRY(rom_check_block("rom_mlp_fit", {"X", "ldx", "m"}, X->n, x_off, ldx, m, M));
+  ROM_TRY(rom_check_block("rom_mlp_fit", {"Y", "ldy", "q"}, Y->n, y_off, ldy, q, M));
   D.act = activation;
   const int P = D.P;
   for (int p = 0; p < P; ++p)
@@ -811,10 +803,7 @@ extern "C" int rom_mlp_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, 
   const double* y = Y->p + y_off;
 
   rom_mlp* h = new rom_mlp;
-  struct Guard {
-    rom_mlp* h;
-    ~Guard() { if (h) rom_mlp_destroy(h); }
-  } guard{h};
+  HandleGuard<rom_mlp, rom_mlp_destroy> guard{h};
   h->ctx = ctx;
   h->D = D;
   h->lds_eval = le;
@@ -924,8 +913,7 @@ extern "C" int rom_mlp_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, 
     info_host[6] = double(h->syncs);
     info_host[7] = 6.0 * double(M) * D.wpad * his[IS_EVALS];
   }
-  guard.h = nullptr;
-  *out = h;
+  *out = guard.release();
   return ROM_OK;
 }
 
@@ -934,10 +922,10 @@ extern "C" int rom_mlp_loss_grad(rom_mlp* h, rom_buf* X, size_t x_off, int64_t l
   ROM_CHECK(h && X && Y && loss_host && grad_host, "rom_mlp_loss_grad: null argument");
   rom_ctx* ctx = h->ctx;
   const MlpDesc& D = h->D;
-  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 40), "rom_mlp_loss_grad: M = %lld rows, at least 1", (long long)M);
+  ROM_TRY(rom_check_rows("rom_mlp_loss_grad", M));
   ROM_CHECK(alpha >= 0.0 && alpha <= ML_DBL_MAX, "rom_mlp_loss_grad: alpha = %g, a finite number >= 0", alpha);
-  ROM_TRY(mlp_check_block("rom_mlp_loss_grad", "X", X, x_off, ldx, D.n[0], M));
-  ROM_TRY(mlp_check_block("rom_mlp_loss_grad", "Y", Y, y_off, ldy, D.n[D.nl], M));
+  ROM_TRY(rom_check_block("rom_mlp_loss_grad", {"X", "ldx", "m"}, X->n, x_off, ldx, D.n[0], M));
+  ROM_TRY(rom_check_block("rom_mlp_loss_grad", {"Y", "ldy", "q"}, Y->n, y_off, ldy, D.n[D.nl], M));
   ROM_HIP(hipSetDevice(ctx->device));
   const SlabPlan plan = rom_slab_plan(ctx, M, 16);
   Tmp Part, ev;
@@ -959,38 +947,23 @@ extern "C" int rom_mlp_predict(rom_mlp* h, rom_buf* X, size_t x_off, int64_t ldx
   rom_ctx* ctx = h->ctx;
   const MlpDesc& D = h->D;
   const int m = D.n[0], q = D.n[D.nl];
-  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 40), "rom_mlp_predict: M = %lld rows, at least 1", (long long)M);
-  ROM_TRY(mlp_check_block("rom_mlp_predict", "X", X, x_off, ldx, m, M));
-  if (OUT) {
-    ROM_TRY(mlp_check_block("rom_mlp_predict", "OUT", OUT, o_off, ldo, q, M));
-    ROM_CHECK(!ranges_overlap(X->p + x_off, size_t(M - 1) * size_t(ldx) + m, OUT->p + o_off, size_t(M - 1) * size_t(ldo) + q),
-              "rom_mlp_predict: OUT overlaps X (the inputs are read while the predictions are written)");
-  }
-  if (Yref) ROM_TRY(mlp_check_block("rom_mlp_predict", "Yref", Yref, r_off, ldr, q, M));
+  ROM_TRY(rom_check_predict_blocks("rom_mlp_predict", M, X, x_off, ldx, m, q, OUT, o_off, ldo, Yref, r_off, ldr));
   ROM_HIP(hipSetDevice(ctx->device));
   const SlabPlan plan = rom_slab_plan(ctx, M, 16);
   if (h->lds_predict > 64 * 1024)
     ROM_TRY(rom_lds_optin(ctx->lds_optin_mlp_predict, reinterpret_cast<const void*>(k_mlp_predict), ML_LDS_MAX - ML_STATIC_LDS));
-  Tmp SS, sums;
-  if (sumsq_host) {
-    ROM_TRY(SS.get(ctx, size_t(plan.chunks) * q));
-    ROM_TRY(sums.get(ctx, q));
-  }
+  SumsqTail tail;
+  if (sumsq_host) ROM_TRY(tail.get(ctx, plan.chunks, q));
   {
     ROM_PROF(ctx, "mlp_predict", 2.0 * double(M) * D.wpad, 8.0 * double(M) * (m + q * (Yref ? 2.0 : 1.0)));
     k_mlp_predict<<<plan.chunks, SLAB_THREADS, h->lds_predict, ctx->stream>>>(D, X->p + x_off, ldx, M, plan.per_chunk, h->dev->p,
                                                                              h->dev->p + ML_SC_SIZE, OUT ? OUT->p + o_off : nullptr, ldo,
                                                                              Yref ? Yref->p + r_off : nullptr, ldr,
-                                                                             sumsq_host ? SS.p() : nullptr);
+                                                                             tail.partials());
   }
   ROM_HIP(hipGetLastError());
-  h->launches += 1;
-  if (sumsq_host) {
-    kb_partials_colsum<<<blocks_for(q), 256, 0, ctx->stream>>>(SS, plan.chunks, q, 1.0, sums);
-    ROM_HIP(hipGetLastError());
-    ROM_HIP(hipMemcpyAsync(sumsq_host, sums.p(), size_t(q) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  ROM_HIP(hipStreamSynchronize(ctx->stream));
+  h->launches += 1;   // (the column sums of the tail are not counted here)
+  ROM_TRY(tail.finish(ctx, plan.chunks, q, sumsq_host));
   h->syncs += 1;
   return ROM_OK;
 }

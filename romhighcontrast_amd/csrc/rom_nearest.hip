@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "rom_basis_int.h"
+#include "rom_block.h"
 #include "rom_slab.h"
 
 namespace {
@@ -427,16 +428,11 @@ extern "C" int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, 
   ROM_CHECK(M >= t && M <= (int64_t(1) << 40), "rom_nearest: M = %lld library rows, at least t = %d", (long long)M, t);
   ROM_CHECK(K >= 0, "rom_nearest: K = %d queries", K);
   ROM_CHECK(mode == 0 || mode == 1, "rom_nearest: mode = %d, 0 (screened search) or 1 (exhaustive scan)", mode);
-  ROM_CHECK(ldq >= r, "rom_nearest: ldq = %lld < r = %d", (long long)ldq, r);
-  ROM_CHECK(q_off + size_t(M - 1) * size_t(ldq) + size_t(r) <= Q->n,
-            "rom_nearest: Q holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", Q->n, (long long)M, r, q_off,
-            (long long)ldq);
+  ROM_TRY(rom_check_block("rom_nearest", {"Q", "ldq", "r"}, Q->n, q_off, ldq, r, M));
   if (info_host) std::fill(info_host, info_host + 8, 0.0);
   if (K == 0) return ROM_OK;
   ROM_CHECK(P && idx_host && dist2_host, "rom_nearest: null argument (P, idx_host or dist2_host)");
-  ROM_CHECK(ldp >= r, "rom_nearest: ldp = %lld < r = %d", (long long)ldp, r);
-  ROM_CHECK(p_off + size_t(K - 1) * size_t(ldp) + size_t(r) <= P->n,
-            "rom_nearest: P holds %zu doubles, %d rows of %d at offset %zu with stride %lld need more", P->n, K, r, p_off, (long long)ldp);
+  ROM_TRY(rom_check_block("rom_nearest", {"P", "ldp", "r"}, P->n, p_off, ldp, r, K));
   ROM_HIP(hipSetDevice(ctx->device));
   const double* q = Q->p + q_off;
   const double* p = P->p + p_off;

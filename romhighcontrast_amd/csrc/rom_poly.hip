@@ -22,18 +22,17 @@
 #include <cstring>
 
 #include "rom_basis_int.h"
+#include "rom_block.h"
+#include "rom_poly_host.h"   // PL_MAX, PL_MMAX, PL_DMAX, PL_NOFAC and the host arithmetic of the fit
 #include "rom_slab.h"
 
 namespace {
 
-constexpr int PL_MAX = 96;       // largest P (T + the slabs in 160 KB of LDS)
 constexpr int PL_QG = 96;        // target columns of one launch
 constexpr int PL_QMAX = 1024;
-constexpr int PL_MMAX = 16, PL_DMAX = 8;
 constexpr int PL_YREG = SLAB_ROWS * PL_QG / SLAB_THREADS;   // target values of a slab per thread
 constexpr int PL_TILES = 8;      // 16 x 16 tiles of Psi^T [Psi | Y] per wave: 21 lower Gram tiles + 36 of B <= 64
 constexpr int PL_PASS_CAP = 4;
-constexpr int PL_NOFAC = 255;
 constexpr double PL_EPS = 1.1102230246251565e-16;   // 2^-53
 // A pass is accepted when P |delta|_max <= 1/3: |delta|_2 <= P |delta|_max, so cond(G) <= (1 + 1/3) / (1 - 1/3) = 2 -- the
 // solve G^-1 B loses at most one bit against an exactly orthonormal Psi, and a further pass could not gain more than that.
@@ -343,56 +342,13 @@ __global__ __launch_bounds__(SLAB_THREADS) void k_poly_predict(const double* __r
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// the exponent rows of PolynomialFeatures(d).powers_: graded, combinations_with_replacement(range(m), k) in lexicographic order
-long long poly_count(int m, int d) {
-  long long p = 1;
-  for (int k = 1; k <= d; ++k) p = p * (m + k) / k;   // C(m + k, k): exact at every step
-  return p;
-}
-
-void poly_powers(int m, int d, std::vector<int>& powers) {
-  powers.clear();
-  std::vector<int> comb;
-  for (int deg = 0; deg <= d; ++deg) {
-    comb.assign(deg, 0);
-    for (;;) {
-      const size_t at = powers.size();
-      powers.resize(at + m, 0);
-      for (int v : comb) powers[at + v] += 1;
-      int pos = deg - 1;
-      while (pos >= 0 && comb[pos] == m - 1) --pos;
-      if (pos < 0) break;
-      const int v = comb[pos] + 1;
-      for (int r = pos; r < deg; ++r) comb[r] = v;
-    }
-  }
-}
-
+// (the terms, the factor table and the dense steps between the passes: rom_poly_host.h)
 size_t pass_lds(int ppad, int qpad, int m, int d) {
   return (size_t(ppad + SLAB_ROWS) * slab_ld_nt(ppad) + size_t(SLAB_ROWS) * slab_ld_tn(ppad + qpad) + size_t(SLAB_ROWS) * pl_ld_leg(m, d)) *
          sizeof(double);
 }
 size_t predict_lds(int ppad, int qpad, int m, int d) {
   return (size_t(qpad + SLAB_ROWS) * slab_ld_nt(ppad) + size_t(SLAB_ROWS) * pl_ld_leg(m, d)) * sizeof(double);
-}
-
-bool ranges_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
-
-// L L^T = A (r x r, row-major with stride ld, lower triangle read) in extended precision; false if a pivot is not positive
-bool host_cholesky(std::vector<long double>& L, const double* A, int ld, int r) {
-  L.assign(size_t(r) * r, 0.0L);
-  for (int i = 0; i < r; ++i)
-    for (int j = 0; j <= i; ++j) {
-      long double s = A[size_t(i) * ld + j];
-      for (int q = 0; q < j; ++q) s -= L[size_t(i) * r + q] * L[size_t(j) * r + q];
-      if (i == j) {
-        if (!(s > 0.0L)) return false;
-        L[size_t(i) * r + i] = sqrtl(s);
-      } else {
-        L[size_t(i) * r + j] = s / L[size_t(j) * r + j];
-      }
-    }
-  return true;
 }
 
 }  // namespace
@@ -427,89 +383,73 @@ extern "C" int rom_poly_destroy(rom_poly* h) {
   return ROM_OK;
 }
 
-extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q,
-                            int64_t M, int d, double rcond, rom_poly** out, double* info_host) {
-  ROM_CHECK(ctx && X && Y && out, "rom_poly_fit: null argument (context, X, Y or the handle's address)");
-  ROM_CHECK(m >= 1 && m <= PL_MMAX, "rom_poly_fit: m = %d inputs, between 1 and %d", m, PL_MMAX);
-  ROM_CHECK(d >= 1 && d <= PL_DMAX, "rom_poly_fit: degree d = %d, between 1 and %d", d, PL_DMAX);
-  const long long Pl = poly_count(m, d);
-  ROM_CHECK(Pl <= PL_MAX, "rom_poly_fit: P = C(%d + %d, %d) = %lld terms, at most %d", m, d, d, Pl, PL_MAX);
-  ROM_CHECK(q >= 1 && q <= PL_QMAX, "rom_poly_fit: q = %d target columns, between 1 and %d", q, PL_QMAX);
-  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 40), "rom_poly_fit: M = %lld rows, at least 1", (long long)M);
-  ROM_CHECK(ldx >= m, "rom_poly_fit: ldx = %lld < m = %d", (long long)ldx, m);
-  ROM_CHECK(ldy >= q, "rom_poly_fit: ldy = %lld < q = %d", (long long)ldy, q);
-  ROM_CHECK(x_off + size_t(M - 1) * size_t(ldx) + size_t(m) <= X->n,
-            "rom_poly_fit: X holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", X->n, (long long)M, m, x_off,
-            (long long)ldx);
-  ROM_CHECK(y_off + size_t(M - 1) * size_t(ldy) + size_t(q) <= Y->n,
-            "rom_poly_fit: Y holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", Y->n, (long long)M, q, y_off,
-            (long long)ldy);
-  ROM_HIP(hipSetDevice(ctx->device));
-  const int P = int(Pl);
-  const double* x = X->p + x_off;
-  const double* y = Y->p + y_off;
-  // A Cholesky factorisation of a Gram matrix sees the SQUARE of the condition number: a squared pivot of the column-
-  // normalised G_1 at or below about P eps of the largest is rounding noise of the P-term sums behind it, so the default
-  // drops a term there: rcond^2 = P eps, rcond = sqrt(P eps) (1e-7 at P = 96).
-  const double rc = rcond > 0.0 ? rcond : std::sqrt(double(P) * PL_EPS);
-  const SlabPlan plan = rom_slab_plan(ctx, M, P);
-  const int ppad = plan.pad, ngroups = (q + PL_QG - 1) / PL_QG;
-  const unsigned long long helper_syncs0 = ctx->host_syncs;
-  int syncs = 0;
-  double executed = 0.0;
+namespace {
 
-  rom_poly* h = new rom_poly;
-  struct Guard {
-    rom_poly* h;
-    ~Guard() { if (h) rom_poly_destroy(h); }
-  } guard{h};
-  h->ctx = ctx;
-  h->m = m;
-  h->d = d;
-  h->P = P;
-  h->q = q;
-  h->M_train = M;
-  h->dropped.assign(P, 0.0);
-  ROM_TRY(rom_buf_alloc(ctx, PL_OFF_W + size_t(q) * P, &h->dev));
-  double* dev = h->dev->p;
-  unsigned char* d_tab = reinterpret_cast<unsigned char*>(dev + PL_OFF_TAB);
+// One fit between its steps: setup, first_pass, pass_loop, finish.  h is the handle under construction (m, d, P, q, M_train set).
+struct PolyFit {
+  rom_ctx* ctx;
+  rom_poly* h;
+  const double *x, *y;   // the blocks at their offsets
+  int64_t ldx, ldy;
+  double rc;
+  int m, d, P, q;
+  int64_t M;
+  SlabPlan plan;
+  size_t pp;             // P^2
+  unsigned long long helper_syncs0;
+  std::vector<unsigned char> tab;
+  Tmp mm_part, Gh, lam, Td, That, GB, Part;   // lam: lam | D; GB: G | B, one download per pass
+  std::vector<double> hT, hGB, hsmall, hW, tnew;
+  std::vector<long double> L, z;
+  int syncs = 0, passes = 0, rank = 0, stop = 0;
+  double executed = 0.0, delta = 0.0, piv_ratio = 0.0;
+  bool solved = false;
 
-  // factor table of the terms
-  std::vector<int> powers;
-  poly_powers(m, d, powers);
-  std::vector<unsigned char> tab(size_t(PL_MAX) * PL_DMAX, (unsigned char)PL_NOFAC);
-  for (int p = 0; p < P; ++p) {
-    int nf = 0;
-    for (int j = 0; j < m; ++j)
-      if (powers[size_t(p) * m + j] > 0) tab[size_t(p) * PL_DMAX + nf++] = (unsigned char)(j * d + powers[size_t(p) * m + j] - 1);
+  PolyFit(rom_poly* h_, const double* x_, int64_t ldx_, const double* y_, int64_t ldy_, double rc_)
+      : ctx(h_->ctx), h(h_), x(x_), y(y_), ldx(ldx_), ldy(ldy_), rc(rc_), m(h_->m), d(h_->d), P(h_->P), q(h_->q), M(h_->M_train),
+        plan(rom_slab_plan(ctx, M, P)), pp(size_t(P) * P), helper_syncs0(ctx->host_syncs) {}
+
+  double* dev() const { return h->dev->p; }
+  double* d_G() const { return GB; }
+  double* d_B() const { return GB.p() + pp; }
+
+  // the handle's device block with the factor table, c and h of the input columns, the scratch of the passes
+  int setup() {
+    ROM_TRY(rom_buf_alloc(ctx, PL_OFF_W + size_t(q) * P, &h->dev));
+    std::vector<int> powers;
+    poly_powers(m, d, powers);
+    tab = poly_factor_table(powers, m, d, P);
+    ROM_HIP(hipMemcpyAsync(dev() + PL_OFF_TAB, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream));
+    {
+      const int chunks = int(std::min<int64_t>(1024, (M + 63) / 64));
+      const long long per = (M + chunks - 1) / chunks;
+      ROM_TRY(mm_part.get(ctx, size_t(chunks) * 48));
+      ROM_PROF(ctx, "poly_minmax", 2.0 * M * m, 8.0 * M * m);
+      k_poly_minmax_partial<<<chunks, 256, 0, ctx->stream>>>(x, ldx, m, M, per, mm_part);
+      k_poly_minmax_finish<<<1, 64, 0, ctx->stream>>>(mm_part, chunks, m, dev());
+      ROM_HIP(hipGetLastError());
+    }
+    ROM_TRY(GB.get(ctx, pp + size_t(P) * q));
+    ROM_TRY(Gh.get(ctx, pp));
+    ROM_TRY(lam.get(ctx, 2 * size_t(P)));
+    ROM_TRY(Td.get(ctx, pp));
+    ROM_TRY(That.get(ctx, pp));
+    ROM_TRY(Part.get(ctx, size_t(plan.chunks) * plan.pad * (plan.pad + PL_QG)));
+    if (pass_lds(plan.pad, PL_QG, m, d) > 64 * 1024)
+      ROM_TRY(rom_lds_optin(ctx->lds_optin_poly_pass, reinterpret_cast<const void*>(k_poly_pass), 159 * 1024));
+    hT.assign(pp, 0.0);
+    hGB.resize(pp + size_t(P) * q);
+    hsmall.resize(2 * size_t(P) + pp);
+    hW.assign(size_t(q) * P, 0.0);
+    tnew.resize(pp);
+    z.resize(P);
+    return ROM_OK;
   }
-  ROM_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream));
-
-  Tmp mm_part, G, Gh, lam, Td, That, GB, Part;
-  const size_t pp = size_t(P) * P;
-  {
-    const int chunks = int(std::min<int64_t>(1024, (M + 63) / 64));
-    const long long per = (M + chunks - 1) / chunks;
-    ROM_TRY(mm_part.get(ctx, size_t(chunks) * 48));
-    ROM_PROF(ctx, "poly_minmax", 2.0 * M * m, 8.0 * M * m);
-    k_poly_minmax_partial<<<chunks, 256, 0, ctx->stream>>>(x, ldx, m, M, per, mm_part);
-    k_poly_minmax_finish<<<1, 64, 0, ctx->stream>>>(mm_part, chunks, m, dev);
-    ROM_HIP(hipGetLastError());
-  }
-  ROM_TRY(GB.get(ctx, pp + size_t(P) * q));   // G | B: one download per pass
-  ROM_TRY(Gh.get(ctx, pp));
-  ROM_TRY(lam.get(ctx, 2 * size_t(P)));       // lam | D
-  ROM_TRY(Td.get(ctx, pp));
-  ROM_TRY(That.get(ctx, pp));
-  ROM_TRY(Part.get(ctx, size_t(plan.chunks) * ppad * (ppad + PL_QG)));
-  double* d_G = GB;
-  double* d_B = GB.p() + pp;
-
-  if (pass_lds(ppad, PL_QG, m, d) > 64 * 1024)
-    ROM_TRY(rom_lds_optin(ctx->lds_optin_poly_pass, reinterpret_cast<const void*>(k_poly_pass), 159 * 1024));
 
   // one pass: every target group through the kernel (the Gram tiles with the first), G and B reduced in chunk order
-  auto pass = [&](const double* T) -> int {
+  int pass(const double* T) {
+    const int ppad = plan.pad, ngroups = (q + PL_QG - 1) / PL_QG;
+    const unsigned char* d_tab = reinterpret_cast<const unsigned char*>(dev() + PL_OFF_TAB);
     for (int g = 0; g < ngroups; ++g) {
       const int c0 = g * PL_QG, qg = std::min(PL_QG, q - c0), qpad = (qg + 15) / 16 * 16;
       const int ntile = (g == 0 ? (ppad / 16) * (ppad / 16 + 1) / 2 : 0) + (ppad / 16) * (qpad / 16);
@@ -518,7 +458,7 @@ extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx,
         char nm[48];
         rom_prof_name(nm, sizeof nm, "poly_pass", "_P%d_q%d", P, qg);
         ROM_PROF(ctx, nm, fl, 8.0 * M * (m + qg));
-        k_poly_pass<<<plan.chunks, SLAB_THREADS, pass_lds(ppad, qpad, m, d), ctx->stream>>>(x, ldx, m, d, dev, d_tab, P, ppad, T, y + c0, ldy,
+        k_poly_pass<<<plan.chunks, SLAB_THREADS, pass_lds(ppad, qpad, m, d), ctx->stream>>>(x, ldx, m, d, dev(), d_tab, P, ppad, T, y + c0, ldy,
                                                                                        qg, qpad, M, plan.per_chunk, g == 0, Part);
       }
       ROM_HIP(hipGetLastError());
@@ -526,53 +466,35 @@ extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx,
       {
         ROM_PROF(ctx, "poly_reduce", double(plan.chunks) * (pp + P * qg), 8.0 * plan.chunks * (pp + P * qg));
         kb_partials_reduce<<<blocks_for((g == 0 ? pp : 0) + size_t(P) * qg), 256, 0, ctx->stream>>>(Part, plan.chunks, ppad, ppad + qpad, P,
-                                                                                                    qg, g == 0 ? d_G : nullptr, d_B, q, c0);
+                                                                                                    qg, g == 0 ? d_G() : nullptr, d_B(), q, c0);
       }
       ROM_HIP(hipGetLastError());
     }
     return ROM_OK;
-  };
-
-  std::vector<double> hT(pp, 0.0), hGB(pp + size_t(P) * q), hsmall(2 * size_t(P) + pp), hW(size_t(q) * P, 0.0);
-  std::vector<double> tnew(pp);
-  std::vector<long double> L, z(P);
-  int passes = 0, rank = 0, stop = 0;
-  double delta = 0.0, piv_ratio = 0.0;
-  bool solved = false;
+  }
 
   // pass 1: T = I, the column-normalised Gram matrix and its rank-revealing whitening transform
-  ROM_TRY(pass(nullptr));
-  passes = 1;
-  k_poly_normalise<<<blocks_for(pp), 256, 0, ctx->stream>>>(d_G, P, Gh, lam.p() + P);
-  ROM_HIP(hipGetLastError());
-  ROM_TRY(romb_pivchol_whiten(ctx, P, Gh, P, lam, That, P, rc * rc));
-  executed += double(P) * P * P;
-  {
+  int first_pass() {
+    ROM_TRY(pass(nullptr));
+    passes = 1;
+    k_poly_normalise<<<blocks_for(pp), 256, 0, ctx->stream>>>(d_G(), P, Gh, lam.p() + P);
+    ROM_HIP(hipGetLastError());
+    ROM_TRY(romb_pivchol_whiten(ctx, P, Gh, P, lam, That, P, rc * rc));
+    executed += double(P) * P * P;
     double bad = 0.0;
-    ROM_HIP(hipMemcpyAsync(&bad, dev + PL_OFF_BAD, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ROM_HIP(hipMemcpyAsync(&bad, dev() + PL_OFF_BAD, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ROM_HIP(hipMemcpyAsync(hsmall.data(), lam.p(), 2 * size_t(P) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ROM_TRY(download(ctx, That, hsmall.data() + 2 * P, pp));
     syncs += 1;
     ROM_CHECK(bad == 0.0, "rom_poly_fit: the inputs contain %.0f NaN / Inf entries", bad);
-  }
-  {
     const double* hl = hsmall.data();
-    const double* hD = hl + P;
-    const double* hTh = hD + P;
-    for (int i = 0; i < P; ++i) rank += hl[i] > 0.0 ? 1 : 0;
+    rank = poly_first_transform(P, hl, hl + P, hl + 2 * P, hT.data(), &piv_ratio, h->dropped.data());
     ROM_CHECK(rank >= 1, "rom_poly_fit: no term of the feature space has a finite positive norm (NaN / Inf in the features?)");
-    piv_ratio = hl[rank - 1] / hl[0];
-    for (int i = 0; i < P; ++i)
-      for (int c = 0; c < P; ++c) hT[size_t(i) * P + c] = hTh[size_t(i) * P + c] * hD[c];
-    // a term is dropped when its column of T^ is zero: it never became a pivot
-    for (int c = 0; c < P; ++c) {
-      bool used = false;
-      for (int i = 0; i < rank && !used; ++i) used = hTh[size_t(i) * P + c] != 0.0;
-      h->dropped[c] = used ? 0.0 : 1.0;
-    }
+    return ROM_OK;
   }
 
-  for (int p = 2; p <= PL_PASS_CAP; ++p) {
+  // pass p >= 2 with the current T: G (I + delta on the leading rank x rank block) and B on the host, |delta|_max
+  int gram_of_pass(int p) {
     ROM_HIP(hipMemcpyAsync(Td, hT.data(), pp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     ROM_TRY(pass(Td));
     passes = p;
@@ -581,79 +503,103 @@ extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx,
     bool finite = true;
     for (double v : hGB) finite = finite && std::fabs(v) <= 1.7976931348623157e308;
     ROM_CHECK(finite, "rom_poly_fit: the targets contain NaN / Inf entries (or products with them leave the range of fp64)");
-    const double* hG = hGB.data();
-    const double* hB = hG + pp;
     delta = 0.0;
     for (int i = 0; i < rank; ++i)
-      for (int c = 0; c < rank; ++c) delta = std::max(delta, std::fabs(hG[size_t(i) * P + c] - (i == c ? 1.0 : 0.0)));
-    const bool pd = host_cholesky(L, hG, P, rank);
-    const bool good = pd && double(P) * delta <= PL_DELTA_OK;
-    if (good || (pd && p == PL_PASS_CAP)) {
-      // W = T^T G^-1 B on the leading rank x rank block
-      for (int c = 0; c < q; ++c) {
-        for (int i = 0; i < rank; ++i) {
-          long double s = hB[size_t(i) * q + c];
-          for (int r = 0; r < i; ++r) s -= L[size_t(i) * rank + r] * z[r];
-          z[i] = s / L[size_t(i) * rank + i];
-        }
-        for (int i = rank - 1; i >= 0; --i) {
-          long double s = z[i];
-          for (int r = i + 1; r < rank; ++r) s -= L[size_t(r) * rank + i] * z[r];
-          z[i] = s / L[size_t(i) * rank + i];
-        }
-        for (int t = 0; t < P; ++t) {
-          long double s = 0.0L;
-          for (int i = 0; i < rank; ++i) s += (long double)hT[size_t(i) * P + t] * z[i];
-          hW[size_t(c) * P + t] = double(s);
-        }
-      }
-      executed += 2.0 * q * (double(rank) * rank + double(rank) * P) + double(rank) * rank * rank / 3.0;
-      solved = true;
-      stop = good ? (rank < P ? 1 : 0) : 2;
-      break;
-    }
-    ROM_CHECK(p < PL_PASS_CAP, "rom_poly_fit: the Gram matrix of pass %d is not positive definite (|delta|_max = %.3g): pass budget reached",
-              p, delta);
-    // T <- (whitening transform of G_p) T; a pivot at the noise level of G_p = I + delta lowers the rank
-    ROM_TRY(romb_pivchol_whiten(ctx, P, d_G, P, lam, That, P, double(P) * PL_EPS));
+      for (int c = 0; c < rank; ++c) delta = std::max(delta, std::fabs(hGB[size_t(i) * P + c] - (i == c ? 1.0 : 0.0)));
+    return ROM_OK;
+  }
+
+  // T <- (whitening transform of G_p) T; a pivot at the noise level of G_p = I + delta lowers the rank
+  int rewhiten(int p) {
+    ROM_TRY(romb_pivchol_whiten(ctx, P, d_G(), P, lam, That, P, double(P) * PL_EPS));
     executed += double(P) * P * P;
     ROM_HIP(hipMemcpyAsync(hsmall.data(), lam.p(), size_t(P) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ROM_TRY(download(ctx, That, hsmall.data() + 2 * P, pp));
     syncs += 1;
     const double* hl = hsmall.data();
-    const double* hTh = hsmall.data() + 2 * P;
     int r2 = 0;
     for (int i = 0; i < P; ++i) r2 += hl[i] > 0.0 ? 1 : 0;
     ROM_CHECK(r2 >= 1, "rom_poly_fit: the Gram matrix of pass %d has no positive pivot", p);
-    for (int i = 0; i < P; ++i)
-      for (int c = 0; c < P; ++c) {
-        long double s = 0.0L;
-        if (i < r2)
-          for (int r = 0; r < rank; ++r) s += (long double)hTh[size_t(i) * P + r] * hT[size_t(r) * P + c];
-        tnew[size_t(i) * P + c] = double(s);
-      }
+    poly_update_t(P, rank, r2, hl + 2 * P, hT.data(), tnew.data());
     hT.swap(tnew);
     rank = r2;
+    return ROM_OK;
   }
-  ROM_CHECK(solved, "rom_poly_fit: no pass was accepted");
-  ROM_HIP(hipMemcpyAsync(dev + PL_OFF_W, hW.data(), hW.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  ROM_HIP(hipStreamSynchronize(ctx->stream));   // (hW is host memory; the temporaries go back to the allocator)
-  syncs += 1;
-  h->rank = rank;
-  h->passes = passes;
-  h->syncs = (unsigned long long)syncs + (ctx->host_syncs - helper_syncs0);
-  if (info_host) {
-    info_host[0] = P;
-    info_host[1] = rank;
-    info_host[2] = passes;
-    info_host[3] = delta;
-    info_host[4] = piv_ratio;
-    info_host[5] = executed;
-    info_host[6] = double(h->syncs);
-    info_host[7] = stop;
+
+  // passes 2 .. PL_PASS_CAP: a pass is accepted and solved (W = T^T G^-1 B), or T is re-whitened for another
+  int pass_loop() {
+    for (int p = 2; p <= PL_PASS_CAP; ++p) {
+      ROM_TRY(gram_of_pass(p));
+      const bool pd = host_cholesky(L, hGB.data(), P, rank);
+      const bool good = pd && double(P) * delta <= PL_DELTA_OK;
+      if (good || (pd && p == PL_PASS_CAP)) {
+        poly_solve_w(P, q, rank, L, hGB.data() + pp, hT.data(), z.data(), hW.data());
+        executed += 2.0 * q * (double(rank) * rank + double(rank) * P) + double(rank) * rank * rank / 3.0;
+        solved = true;
+        stop = good ? (rank < P ? 1 : 0) : 2;
+        break;
+      }
+      ROM_CHECK(p < PL_PASS_CAP, "rom_poly_fit: the Gram matrix of pass %d is not positive definite (|delta|_max = %.3g): pass budget reached",
+                p, delta);
+      ROM_TRY(rewhiten(p));
+    }
+    ROM_CHECK(solved, "rom_poly_fit: no pass was accepted");
+    return ROM_OK;
   }
-  guard.h = nullptr;
-  *out = h;
+
+  // W to the handle, the handle's figures and info_host
+  int finish(double* info_host) {
+    ROM_HIP(hipMemcpyAsync(dev() + PL_OFF_W, hW.data(), hW.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ROM_HIP(hipStreamSynchronize(ctx->stream));   // (hW is host memory; the temporaries go back to the allocator)
+    syncs += 1;
+    h->rank = rank;
+    h->passes = passes;
+    h->syncs = (unsigned long long)syncs + (ctx->host_syncs - helper_syncs0);
+    if (info_host) {
+      info_host[0] = P;
+      info_host[1] = rank;
+      info_host[2] = passes;
+      info_host[3] = delta;
+      info_host[4] = piv_ratio;
+      info_host[5] = executed;
+      info_host[6] = double(h->syncs);
+      info_host[7] = stop;
+    }
+    return ROM_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" int rom_poly_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q,
+                            int64_t M, int d, double rcond, rom_poly** out, double* info_host) {
+  const char* who = "rom_poly_fit";
+  ROM_CHECK(ctx && X && Y && out, "rom_poly_fit: null argument (context, X, Y or the handle's address)");
+  ROM_CHECK(m >= 1 && m <= PL_MMAX, "rom_poly_fit: m = %d inputs, between 1 and %d", m, PL_MMAX);
+  ROM_CHECK(d >= 1 && d <= PL_DMAX, "rom_poly_fit: degree d = %d, between 1 and %d", d, PL_DMAX);
+  const long long Pl = poly_count(m, d);
+  ROM_CHECK(Pl <= PL_MAX, "rom_poly_fit: P = C(%d + %d, %d) = %lld terms, at most %d", m, d, d, Pl, PL_MAX);
+  ROM_CHECK(q >= 1 && q <= PL_QMAX, "rom_poly_fit: q = %d target columns, between 1 and %d", q, PL_QMAX);
+  ROM_TRY(rom_check_rows(who, M));
+  ROM_TRY(rom_check_block(who, {"X", "ldx", "m"}, X->n, x_off, ldx, m, M));
+  ROM_TRY(rom_check_block(who, {"Y", "ldy", "q"}, Y->n, y_off, ldy, q, M));
+  ROM_HIP(hipSetDevice(ctx->device));
+  const int P = int(Pl);
+  // A Cholesky factorisation of a Gram matrix sees the SQUARE of the condition number: a squared pivot of the column-
+  // normalised G_1 at or below about P eps of the largest is rounding noise of the P-term sums behind it, so the default
+  // drops a term there: rcond^2 = P eps, rcond = sqrt(P eps) (1e-7 at P = 96).
+  const double rc = rcond > 0.0 ? rcond : std::sqrt(double(P) * PL_EPS);
+
+  rom_poly* h = new rom_poly;
+  HandleGuard<rom_poly, rom_poly_destroy> guard{h};
+  h->ctx = ctx, h->m = m, h->d = d, h->P = P, h->q = q, h->M_train = M;
+  h->dropped.assign(P, 0.0);
+  PolyFit fit(h, X->p + x_off, ldx, Y->p + y_off, ldy, rc);
+  ROM_TRY(fit.setup());
+  ROM_TRY(fit.first_pass());
+  ROM_TRY(fit.pass_loop());
+  ROM_TRY(fit.finish(info_host));
+  *out = guard.release();
   return ROM_OK;
 }
 
@@ -663,36 +609,15 @@ extern "C" int rom_poly_predict(rom_poly* h, rom_buf* X, size_t x_off, int64_t l
   ROM_CHECK(OUT || sumsq_host, "rom_poly_predict: OUT == NULL requires sumsq_host");
   rom_ctx* ctx = h->ctx;
   const int m = h->m, d = h->d, P = h->P, q = h->q;
-  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 40), "rom_poly_predict: M = %lld rows, at least 1", (long long)M);
-  ROM_CHECK(ldx >= m, "rom_poly_predict: ldx = %lld < m = %d", (long long)ldx, m);
-  ROM_CHECK(x_off + size_t(M - 1) * size_t(ldx) + size_t(m) <= X->n,
-            "rom_poly_predict: X holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", X->n, (long long)M, m, x_off,
-            (long long)ldx);
-  if (OUT) {
-    ROM_CHECK(ldo >= q, "rom_poly_predict: ldo = %lld < q = %d", (long long)ldo, q);
-    ROM_CHECK(o_off + size_t(M - 1) * size_t(ldo) + size_t(q) <= OUT->n,
-              "rom_poly_predict: OUT holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", OUT->n, (long long)M, q,
-              o_off, (long long)ldo);
-    ROM_CHECK(!ranges_overlap(X->p + x_off, size_t(M - 1) * size_t(ldx) + m, OUT->p + o_off, size_t(M - 1) * size_t(ldo) + q),
-              "rom_poly_predict: OUT overlaps X (the inputs are read while the predictions are written)");
-  }
-  if (Yref) {
-    ROM_CHECK(ldr >= q, "rom_poly_predict: ldr = %lld < q = %d", (long long)ldr, q);
-    ROM_CHECK(r_off + size_t(M - 1) * size_t(ldr) + size_t(q) <= Yref->n,
-              "rom_poly_predict: Yref holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", Yref->n, (long long)M, q,
-              r_off, (long long)ldr);
-  }
+  ROM_TRY(rom_check_predict_blocks("rom_poly_predict", M, X, x_off, ldx, m, q, OUT, o_off, ldo, Yref, r_off, ldr));
   ROM_HIP(hipSetDevice(ctx->device));
   const SlabPlan plan = rom_slab_plan(ctx, M, P);
   const int ppad = plan.pad, ngroups = (q + PL_QG - 1) / PL_QG;
   const int qpad_max = (std::min(q, PL_QG) + 15) / 16 * 16;
   const size_t lds = predict_lds(ppad, qpad_max, m, d);
   if (lds > 64 * 1024) ROM_TRY(rom_lds_optin(ctx->lds_optin_poly_predict, reinterpret_cast<const void*>(k_poly_predict), 112 * 1024));
-  Tmp SS, sums;
-  if (sumsq_host) {
-    ROM_TRY(SS.get(ctx, size_t(plan.chunks) * q));
-    ROM_TRY(sums.get(ctx, q));
-  }
+  SumsqTail tail;
+  if (sumsq_host) ROM_TRY(tail.get(ctx, plan.chunks, q));
   const double* dev = h->dev->p;
   {
     char nm[48];
@@ -700,15 +625,10 @@ extern "C" int rom_poly_predict(rom_poly* h, rom_buf* X, size_t x_off, int64_t l
     ROM_PROF(ctx, nm, 2.0 * M * ppad * double(ngroups > 1 ? ngroups * PL_QG : qpad_max), 8.0 * M * (m + q * (Yref ? 2.0 : 1.0)));
     k_poly_predict<<<dim3(plan.chunks, ngroups), SLAB_THREADS, lds, ctx->stream>>>(
         X->p + x_off, ldx, m, d, dev, reinterpret_cast<const unsigned char*>(dev + PL_OFF_TAB), P, ppad, dev + PL_OFF_W, q, M, plan.per_chunk,
-        OUT ? OUT->p + o_off : nullptr, ldo, Yref ? Yref->p + r_off : nullptr, ldr, sumsq_host ? SS.p() : nullptr);
+        OUT ? OUT->p + o_off : nullptr, ldo, Yref ? Yref->p + r_off : nullptr, ldr, tail.partials());
   }
   ROM_HIP(hipGetLastError());
-  if (sumsq_host) {
-    kb_partials_colsum<<<blocks_for(q), 256, 0, ctx->stream>>>(SS, plan.chunks, q, 1.0, sums);
-    ROM_HIP(hipGetLastError());
-    ROM_HIP(hipMemcpyAsync(sumsq_host, sums.p(), size_t(q) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  ROM_HIP(hipStreamSynchronize(ctx->stream));
+  ROM_TRY(tail.finish(ctx, plan.chunks, q, sumsq_host));
   h->syncs += 1;
   return ROM_OK;
 }

@@ -23,6 +23,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "rom_basis_int.h"
+#include "rom_block.h"
 
 namespace {
 
@@ -388,16 +389,87 @@ __global__ __launch_bounds__(256) void k_tree_predict(const int* __restrict__ fe
   if (SS && t < q) SS[size_t(blockIdx.x) * q + t] = acc;
 }
 
-bool tr_ranges_overlap(const double* a, size_t na, const double* b, size_t nb) { return a < b + nb && b < a + na; }
-
-// carves arrays out of one block of doubles
+// carves arrays out of one block of doubles; without a block it only measures
 struct Carver {
+  double* base = nullptr;
   size_t at = 0;
   template <typename V>
-  size_t take(size_t n) {
+  V* take(size_t n) {
     const size_t o = at;
     at += (n * sizeof(V) + sizeof(double) - 1) / sizeof(double);
-    return o;
+    return base ? reinterpret_cast<V*>(base + o) : nullptr;
+  }
+};
+
+// the node arrays a fitted forest keeps, N nodes: the layout of rom_tree::dev
+struct TreeNodes {
+  double *thr, *n, *val;
+  int *feat, *left, *tree;
+  size_t doubles;
+  TreeNodes(double* base, size_t N, int q) {
+    Carver c{base};
+    thr = c.take<double>(N), n = c.take<double>(N), val = c.take<double>(N * q);
+    feat = c.take<int>(N), left = c.take<int>(N), tree = c.take<int>(N);
+    doubles = c.at;
+  }
+};
+
+// the sizes of one fit
+struct TreeShape {
+  int64_t M;
+  int m, q, T;
+  bool counts;    // bootstrap counts given
+  int R = 0, ntiles = 0, mt = 0;
+  size_t nmax = 0;   // a binary tree over n rows has at most 2 n - 1 nodes
+  std::vector<int> tree_start;   // T + 1: the positions of tree t are tree_start[t] .. tree_start[t + 1] - 1
+};
+
+// The workspace of a fit, one block: the one place that knows its layout.  d holds the node arrays (nmax nodes) and the scratch
+// of a level; beside it the two copies of ord and nid that the levels alternate between, and the scratch of the presort.
+struct TreeWorkspace {
+  Tmp buf;
+  size_t doubles = 0, sort_bytes = 0;
+  TreeDev d;
+  int *ord[2], *nid[2], *itail, *sorted, *rows, *ccnt, *tstart, *counter, *counts;
+  double *keys0, *keys1;
+  char* sort;
+  unsigned* bad() const { return reinterpret_cast<unsigned*>(counter + 1); }   // (counter: 4 ints, the first the level's new nodes)
+
+  void carve(double* base, const TreeShape& s) {
+    Carver cv{base};
+    const size_t nmax = s.nmax, R = size_t(s.R), m = size_t(s.m), M = size_t(s.M), q = size_t(s.q);
+    d.start = cv.take<int>(nmax), d.end = cv.take<int>(nmax), d.parent = cv.take<int>(nmax), d.treeid = cv.take<int>(nmax);
+    d.depth = cv.take<int>(nmax), d.feat = cv.take<int>(nmax), d.left = cv.take<int>(nmax), d.nlr = cv.take<int>(nmax);
+    d.nonconst = cv.take<int>(nmax), d.thr = cv.take<double>(nmax), d.n = cv.take<double>(nmax);
+    d.bestgain = cv.take<u64>(nmax), d.bestkey = cv.take<u64>(nmax), d.val = cv.take<double>(nmax * q);
+    d.c1 = cv.take<double>(R * q), d.stot = cv.take<double>(R * q);
+    d.tail = cv.take<double>(m * s.ntiles * (q + 1)), d.G = cv.take<u64>(m * R);
+    ord[0] = cv.take<int>(m * R), ord[1] = cv.take<int>(m * R), nid[0] = cv.take<int>(R), nid[1] = cv.take<int>(R);
+    itail = cv.take<int>(m * s.ntiles), sorted = cv.take<int>(m * M);
+    keys0 = cv.take<double>(M), keys1 = cv.take<double>(M), rows = cv.take<int>(M);
+    ccnt = cv.take<int>(size_t(s.T) * m * s.mt), tstart = cv.take<int>(s.T + 1), counter = cv.take<int>(4);
+    counts = cv.take<int>(s.counts ? size_t(s.T) * M : 0);
+    if (!s.counts) counts = nullptr;
+    sort = cv.take<char>(sort_bytes);
+    doubles = cv.at;
+  }
+
+  // the block for the sizes s, and d complete but for the level's ord, nid and lvl0: X and Y are the blocks at their offsets
+  int get(rom_ctx* ctx, const TreeShape& s, const double* x, int64_t ldx, const double* y, int64_t ldy) {
+    {
+      double* kd = nullptr;
+      int* vd = nullptr;
+      ROM_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, kd, kd, vd, vd, size_t(s.M), 0u, 64u, ctx->stream));
+    }
+    carve(nullptr, s);
+    const size_t ws_bytes = doubles * sizeof(double);
+    ROM_CHECK(ws_bytes <= ctx->ws_limit, "rom_tree_fit: %zu bytes of workspace for %d rows in %d trees exceed the limit of %zu", ws_bytes, s.R,
+              s.T, ctx->ws_limit);
+    ROM_TRY(buf.get(ctx, doubles));
+    carve(buf.p(), s);
+    d.X = x, d.ldx = ldx, d.Y = y, d.ldy = ldy, d.M = s.M, d.counts = counts;
+    d.m = s.m, d.q = s.q, d.R = s.R, d.ntiles = s.ntiles;
+    return ROM_OK;
   }
 };
 
@@ -423,27 +495,13 @@ extern "C" int rom_tree_destroy(rom_tree* h) {
   return ROM_OK;
 }
 
-extern "C" int rom_tree_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q,
-                            int64_t M, int T, const int32_t* counts_host, int max_depth, int min_samples_split, int min_samples_leaf,
-                            rom_tree** out, double* info_host) {
-  ROM_CHECK(ctx && X && Y && out, "rom_tree_fit: null argument (context, X, Y or the handle's address)");
-  ROM_CHECK(m >= 1 && m <= TR_MMAX, "rom_tree_fit: m = %d inputs, between 1 and %d", m, TR_MMAX);
-  ROM_CHECK(q >= 1 && q <= TR_QMAX, "rom_tree_fit: q = %d target columns, between 1 and %d", q, TR_QMAX);
-  ROM_CHECK(T >= 1 && T <= TR_TMAX, "rom_tree_fit: T = %d trees, between 1 and %d", T, TR_TMAX);
-  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 30), "rom_tree_fit: M = %lld rows, between 1 and 2^30", (long long)M);
-  ROM_CHECK(max_depth >= 0, "rom_tree_fit: max_depth = %d, 0 (no limit) or more", max_depth);
-  ROM_CHECK(min_samples_split >= 2, "rom_tree_fit: min_samples_split = %d, at least 2", min_samples_split);
-  ROM_CHECK(min_samples_leaf >= 1, "rom_tree_fit: min_samples_leaf = %d, at least 1", min_samples_leaf);
-  ROM_CHECK(ldx >= m, "rom_tree_fit: ldx = %lld < m = %d", (long long)ldx, m);
-  ROM_CHECK(ldy >= q, "rom_tree_fit: ldy = %lld < q = %d", (long long)ldy, q);
-  ROM_CHECK(x_off + size_t(M - 1) * size_t(ldx) + size_t(m) <= X->n,
-            "rom_tree_fit: X holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", X->n, (long long)M, m, x_off,
-            (long long)ldx);
-  ROM_CHECK(y_off + size_t(M - 1) * size_t(ldy) + size_t(q) <= Y->n,
-            "rom_tree_fit: Y holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", Y->n, (long long)M, q, y_off,
-            (long long)ldy);
-  // the rows of every tree
-  std::vector<int> tree_start(T + 1, 0);
+namespace {
+
+// the rows of every tree: those with a positive count, all M without counts
+int tree_rows(const int32_t* counts_host, TreeShape& s) {
+  const int T = s.T;
+  const int64_t M = s.M;
+  s.tree_start.assign(T + 1, 0);
   for (int t = 0; t < T; ++t) {
     long long nt = M;
     if (counts_host) {
@@ -455,240 +513,224 @@ extern "C" int rom_tree_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx,
       }
       ROM_CHECK(nt > 0, "rom_tree_fit: every count of tree %d is 0: a tree without rows", t);
     }
-    ROM_CHECK((long long)tree_start[t] + nt <= (1ll << 30), "rom_tree_fit: more than 2^30 rows in all trees together");
-    tree_start[t + 1] = tree_start[t] + int(nt);
+    ROM_CHECK((long long)s.tree_start[t] + nt <= (1ll << 30), "rom_tree_fit: more than 2^30 rows in all trees together");
+    s.tree_start[t + 1] = s.tree_start[t] + int(nt);
   }
-  ROM_HIP(hipSetDevice(ctx->device));
-  const int R = tree_start[T], ntiles = (R + 63) / 64, mt = int((M + 63) / 64), Q1 = q + 1;
-  const size_t nmax = 2 * size_t(R) - T;   // a binary tree over n rows has at most 2 n - 1 nodes
-  const double* x = X->p + x_off;
-  const double* y = Y->p + y_off;
-  hipStream_t st = ctx->stream;
+  s.R = s.tree_start[T];
+  s.ntiles = (s.R + 63) / 64;
+  s.mt = int((M + 63) / 64);
+  s.nmax = 2 * size_t(s.R) - T;
+  return ROM_OK;
+}
 
-  // ---- workspace ----
-  size_t sort_bytes = 0;
-  {
-    double* kd = nullptr;
-    int* vd = nullptr;
-    ROM_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, kd, kd, vd, vd, size_t(M), 0u, 64u, st));
-  }
-  Carver cv;
-  const size_t o_start = cv.take<int>(nmax), o_end = cv.take<int>(nmax), o_parent = cv.take<int>(nmax), o_tree = cv.take<int>(nmax),
-               o_depth = cv.take<int>(nmax), o_feat = cv.take<int>(nmax), o_left = cv.take<int>(nmax), o_nlr = cv.take<int>(nmax),
-               o_nonconst = cv.take<int>(nmax), o_thr = cv.take<double>(nmax), o_n = cv.take<double>(nmax),
-               o_bg = cv.take<u64>(nmax), o_bk = cv.take<u64>(nmax), o_val = cv.take<double>(nmax * q),
-               o_c1 = cv.take<double>(size_t(R) * q), o_stot = cv.take<double>(size_t(R) * q),
-               o_tail = cv.take<double>(size_t(m) * ntiles * Q1), o_G = cv.take<u64>(size_t(m) * R),
-               o_ord0 = cv.take<int>(size_t(m) * R), o_ord1 = cv.take<int>(size_t(m) * R), o_nid0 = cv.take<int>(R),
-               o_nid1 = cv.take<int>(R), o_itail = cv.take<int>(size_t(m) * ntiles), o_sorted = cv.take<int>(size_t(m) * M),
-               o_keys0 = cv.take<double>(M), o_keys1 = cv.take<double>(M), o_rows = cv.take<int>(M),
-               o_ccnt = cv.take<int>(size_t(T) * m * mt), o_tstart = cv.take<int>(T + 1), o_counter = cv.take<int>(4),
-               o_counts = cv.take<int>(counts_host ? size_t(T) * M : 0), o_sort = cv.take<char>(sort_bytes);
-  const size_t ws_bytes = cv.at * sizeof(double);
-  ROM_CHECK(ws_bytes <= ctx->ws_limit, "rom_tree_fit: %zu bytes of workspace for %d rows in %d trees exceed the limit of %zu", ws_bytes, R, T,
-            ctx->ws_limit);
-  Tmp ws;
-  ROM_TRY(ws.get(ctx, cv.at));
-  double* base = ws.p();
-  auto ip = [&](size_t o) { return reinterpret_cast<int*>(base + o); };
-  int* d_counter = ip(o_counter);
-  unsigned* d_bad = reinterpret_cast<unsigned*>(d_counter + 1);
-  int* d_counts = counts_host ? ip(o_counts) : nullptr;
-  int* d_ord[2] = {ip(o_ord0), ip(o_ord1)};
-  int* d_nid[2] = {ip(o_nid0), ip(o_nid1)};
-
+// One fit between its steps: ws.get, check_and_presort, roots, grow, handle.  The steps enqueue on ctx->stream in this order.
+struct TreeFit {
+  rom_ctx* ctx;
+  hipStream_t st;
+  const TreeShape& s;
+  const int32_t* counts_host;
+  TreeWorkspace ws;
   unsigned long long launches = 0, syncs = 0;
-  // ---- NaN / Inf ----
-  ROM_HIP(hipMemsetAsync(d_counter, 0, 4 * sizeof(int), st));
-  {
-    ROM_PROF(ctx, "tree_finite", 0.0, 8.0 * M * (m + q));
-    k_tree_finite<<<blocks_for(size_t(M) * (m + q)), 256, 0, st>>>(x, ldx, m, y, ldy, q, M, d_bad);
-    ROM_HIP(hipGetLastError());
-    ++launches;
-  }
-  unsigned bad = 0;
-  ROM_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  ROM_HIP(hipStreamSynchronize(st));
-  ++syncs;
-  ROM_CHECK(bad == 0, "rom_tree_fit: the inputs or targets contain %u NaN / Inf entries", bad);
+  int levels = 0, nodes = 0;
+  std::vector<int> h_nid, h_int;   // what roots() uploads: the copies are asynchronous, the arrays stay until the fit ends
+  std::vector<u64> h_key;
 
-  // ---- presort: every input column once (stable radix sort of (x, row)), then the rows of every tree in that order ----
-  if (counts_host) ROM_HIP(hipMemcpyAsync(d_counts, counts_host, size_t(T) * M * sizeof(int), hipMemcpyHostToDevice, st));
-  ROM_HIP(hipMemcpyAsync(ip(o_tstart), tree_start.data(), (T + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-  for (int f = 0; f < m; ++f) {
-    ROM_PROF(ctx, "tree_sort", 0.0, 64.0 * M);
-    k_tree_keys<<<blocks_for(size_t(M)), 256, 0, st>>>(x, ldx, f, M, base + o_keys0, ip(o_rows));
-    ROM_HIP(hipGetLastError());
-    size_t sb = sort_bytes;
-    ROM_HIP(rocprim::radix_sort_pairs(reinterpret_cast<void*>(base + o_sort), sb, base + o_keys0, base + o_keys1, ip(o_rows),
-                                      ip(o_sorted) + size_t(f) * M, size_t(M), 0u, 64u, st));
-    launches += 2;
-  }
-  {
-    ROM_PROF(ctx, "tree_compact", 0.0, 8.0 * T * m * M);
-    const dim3 grid(unsigned((mt + TR_WAVES - 1) / TR_WAVES), unsigned(m), unsigned(T));
-    k_tree_compact<false><<<grid, 256, 0, st>>>(ip(o_sorted), d_counts, M, mt, m, ip(o_ccnt), ip(o_tstart), d_ord[0], R);
-    k_tree_compact<true><<<grid, 256, 0, st>>>(ip(o_sorted), d_counts, M, mt, m, ip(o_ccnt), ip(o_tstart), d_ord[0], R);
-    ROM_HIP(hipGetLastError());
-    launches += 2;
-  }
+  TreeFit(rom_ctx* c, const TreeShape& shape, const int32_t* counts) : ctx(c), st(c->stream), s(shape), counts_host(counts) {}
 
-  // ---- the roots ----
-  std::vector<int> h_nid(R), h_int(T);
-  std::vector<u64> h_key(T, TR_NOKEY);
-  for (int t = 0; t < T; ++t)
-    for (int p = tree_start[t]; p < tree_start[t + 1]; ++p) h_nid[p] = t;
-  ROM_HIP(hipMemcpyAsync(d_nid[0], h_nid.data(), size_t(R) * sizeof(int), hipMemcpyHostToDevice, st));
-  ROM_HIP(hipMemcpyAsync(ip(o_start), tree_start.data(), T * sizeof(int), hipMemcpyHostToDevice, st));
-  ROM_HIP(hipMemcpyAsync(ip(o_end), tree_start.data() + 1, T * sizeof(int), hipMemcpyHostToDevice, st));
-  for (int t = 0; t < T; ++t) h_int[t] = t;
-  ROM_HIP(hipMemcpyAsync(ip(o_tree), h_int.data(), T * sizeof(int), hipMemcpyHostToDevice, st));
-  ROM_HIP(hipMemsetAsync(ip(o_parent), 0xff, T * sizeof(int), st));   // -1
-  ROM_HIP(hipMemsetAsync(ip(o_feat), 0xff, T * sizeof(int), st));
-  ROM_HIP(hipMemsetAsync(ip(o_left), 0xff, T * sizeof(int), st));
-  ROM_HIP(hipMemsetAsync(ip(o_depth), 0, T * sizeof(int), st));
-  ROM_HIP(hipMemsetAsync(ip(o_nlr), 0, T * sizeof(int), st));
-  ROM_HIP(hipMemsetAsync(ip(o_nonconst), 0, T * sizeof(int), st));
-  ROM_HIP(hipMemsetAsync(base + o_thr, 0, T * sizeof(double), st));
-  ROM_HIP(hipMemsetAsync(base + o_n, 0, T * sizeof(double), st));
-  ROM_HIP(hipMemsetAsync(base + o_bg, 0, T * sizeof(u64), st));
-  ROM_HIP(hipMemcpyAsync(base + o_bk, h_key.data(), T * sizeof(u64), hipMemcpyHostToDevice, st));
-
-  TreeDev d;
-  d.X = x;
-  d.ldx = ldx;
-  d.Y = y;
-  d.ldy = ldy;
-  d.M = M;
-  d.counts = d_counts;
-  d.m = m;
-  d.q = q;
-  d.R = R;
-  d.ntiles = ntiles;
-  d.start = ip(o_start);
-  d.end = ip(o_end);
-  d.parent = ip(o_parent);
-  d.treeid = ip(o_tree);
-  d.depth = ip(o_depth);
-  d.feat = ip(o_feat);
-  d.left = ip(o_left);
-  d.nlr = ip(o_nlr);
-  d.nonconst = ip(o_nonconst);
-  d.thr = base + o_thr;
-  d.n = base + o_n;
-  d.val = base + o_val;
-  d.bestgain = reinterpret_cast<u64*>(base + o_bg);
-  d.bestkey = reinterpret_cast<u64*>(base + o_bk);
-  d.c1 = base + o_c1;
-  d.stot = base + o_stot;
-  d.tail = base + o_tail;
-  d.G = reinterpret_cast<u64*>(base + o_G);
-
-  // ---- the levels ----
-  const unsigned gx = unsigned((ntiles + TR_WAVES - 1) / TR_WAVES);
-  const dim3 g1(gx, 1), gm(gx, unsigned(m));
-  const double msl = double(min_samples_leaf), mss = double(min_samples_split);
-  const double lvl_bytes = 8.0 * double(R) * (q + 2);
-  int lvl0 = 0, lvl1 = T, cur = 0, levels = 0;
-  for (;;) {
-    d.lvl0 = lvl0;
-    d.ord = d_ord[cur];
-    d.nid = d_nid[cur];
+  // NaN / Inf in the inputs or targets; then the presort: every input column once (stable radix sort of (x, row)), then the
+  // rows of every tree in that order
+  int check_and_presort() {
+    const TreeDev& d = ws.d;
+    const int64_t M = s.M;
+    const int m = s.m, q = s.q, T = s.T;
+    ROM_HIP(hipMemsetAsync(ws.counter, 0, 4 * sizeof(int), st));
     {
-      ROM_PROF(ctx, "tree_stats", 4.0 * R * Q1, 4.0 * lvl_bytes);
-      k_tree_scan<0><<<g1, 256, 0, st>>>(d, 0, msl);
-      k_tree_scan<1><<<g1, 256, 0, st>>>(d, 0, msl);
+      ROM_PROF(ctx, "tree_finite", 0.0, 8.0 * M * (m + q));
+      k_tree_finite<<<blocks_for(size_t(M) * (m + q)), 256, 0, st>>>(d.X, d.ldx, m, d.Y, d.ldy, q, M, ws.bad());
       ROM_HIP(hipGetLastError());
+      ++launches;
     }
-    {
-      ROM_PROF(ctx, "tree_tiles", 1.0 * m * R * Q1, m * lvl_bytes);
-      k_tree_scan<0><<<gm, 256, 0, st>>>(d, 1, msl);
-      ROM_HIP(hipGetLastError());
-    }
-    {
-      ROM_PROF(ctx, "tree_stats", 4.0 * R * Q1, 4.0 * lvl_bytes);
-      k_tree_scan<2><<<g1, 256, 0, st>>>(d, 1, msl);
-      ROM_HIP(hipGetLastError());
-    }
-    {
-      ROM_PROF(ctx, "tree_gain", 6.0 * m * R * Q1, m * lvl_bytes);
-      k_tree_scan<3><<<gm, 256, 0, st>>>(d, 1, msl);
-      ROM_HIP(hipGetLastError());
-    }
-    {
-      ROM_PROF(ctx, "tree_decide", 0.0, 12.0 * m * R);
-      k_tree_pick<<<blocks_for(size_t(m) * R), 256, 0, st>>>(d);
-      k_tree_decide<<<1, 1024, 0, st>>>(d, lvl1, max_depth, mss, d_counter);
-      ROM_HIP(hipGetLastError());
-    }
-    launches += 7;
-    ++levels;
-    int fresh = 0;
-    ROM_HIP(hipMemcpyAsync(&fresh, d_counter, sizeof(int), hipMemcpyDeviceToHost, st));
+    unsigned bad = 0;
+    ROM_HIP(hipMemcpyAsync(&bad, ws.bad(), sizeof(unsigned), hipMemcpyDeviceToHost, st));
     ROM_HIP(hipStreamSynchronize(st));
     ++syncs;
-    if (fresh == 0) break;
-    ROM_CHECK(size_t(lvl1) + size_t(fresh) <= nmax, "rom_tree_fit: %d + %d nodes exceed the bound 2 R - T = %zu (internal error)", lvl1, fresh,
-              nmax);
-    {
-      ROM_PROF(ctx, "tree_partition", 0.0, 24.0 * m * R);
-      k_tree_part<false><<<gm, 256, 0, st>>>(d, ip(o_itail), d_ord[cur ^ 1], d_nid[cur ^ 1]);
-      k_tree_part<true><<<gm, 256, 0, st>>>(d, ip(o_itail), d_ord[cur ^ 1], d_nid[cur ^ 1]);
+    ROM_CHECK(bad == 0, "rom_tree_fit: the inputs or targets contain %u NaN / Inf entries", bad);
+
+    if (counts_host) ROM_HIP(hipMemcpyAsync(ws.counts, counts_host, size_t(T) * M * sizeof(int), hipMemcpyHostToDevice, st));
+    ROM_HIP(hipMemcpyAsync(ws.tstart, s.tree_start.data(), (T + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int f = 0; f < m; ++f) {
+      ROM_PROF(ctx, "tree_sort", 0.0, 64.0 * M);
+      k_tree_keys<<<blocks_for(size_t(M)), 256, 0, st>>>(d.X, d.ldx, f, M, ws.keys0, ws.rows);
       ROM_HIP(hipGetLastError());
+      size_t sb = ws.sort_bytes;
+      ROM_HIP(rocprim::radix_sort_pairs(reinterpret_cast<void*>(ws.sort), sb, ws.keys0, ws.keys1, ws.rows, ws.sorted + size_t(f) * M, size_t(M), 0u,
+                                        64u, st));
+      launches += 2;
     }
-    launches += 2;
-    cur ^= 1;
-    lvl0 = lvl1;
-    lvl1 += fresh;
+    {
+      ROM_PROF(ctx, "tree_compact", 0.0, 8.0 * T * m * M);
+      const dim3 grid(unsigned((s.mt + TR_WAVES - 1) / TR_WAVES), unsigned(m), unsigned(T));
+      k_tree_compact<false><<<grid, 256, 0, st>>>(ws.sorted, ws.counts, M, s.mt, m, ws.ccnt, ws.tstart, ws.ord[0], s.R);
+      k_tree_compact<true><<<grid, 256, 0, st>>>(ws.sorted, ws.counts, M, s.mt, m, ws.ccnt, ws.tstart, ws.ord[0], s.R);
+      ROM_HIP(hipGetLastError());
+      launches += 2;
+    }
+    return ROM_OK;
   }
 
-  // ---- the handle: the node arrays at their final size ----
-  const size_t N = size_t(lvl1);
-  rom_tree* h = new rom_tree;
-  struct Guard {
-    rom_tree* h;
-    ~Guard() { if (h) rom_tree_destroy(h); }
-  } guard{h};
-  h->ctx = ctx;
-  h->m = m;
-  h->q = q;
-  h->T = T;
-  h->M_train = M;
-  h->nodes = int64_t(N);
-  h->levels = levels;
-  Carver hc;
-  const size_t f_thr = hc.take<double>(N), f_n = hc.take<double>(N), f_val = hc.take<double>(N * q), f_feat = hc.take<int>(N),
-               f_left = hc.take<int>(N), f_tree = hc.take<int>(N);
-  ROM_TRY(rom_buf_alloc(ctx, hc.at, &h->dev));
-  double* hb = h->dev->p;
-  ROM_HIP(hipMemcpyAsync(hb + f_thr, base + o_thr, N * sizeof(double), hipMemcpyDeviceToDevice, st));
-  ROM_HIP(hipMemcpyAsync(hb + f_n, base + o_n, N * sizeof(double), hipMemcpyDeviceToDevice, st));
-  ROM_HIP(hipMemcpyAsync(hb + f_val, base + o_val, N * q * sizeof(double), hipMemcpyDeviceToDevice, st));
-  ROM_HIP(hipMemcpyAsync(hb + f_feat, ip(o_feat), N * sizeof(int), hipMemcpyDeviceToDevice, st));
-  ROM_HIP(hipMemcpyAsync(hb + f_left, ip(o_left), N * sizeof(int), hipMemcpyDeviceToDevice, st));
-  ROM_HIP(hipMemcpyAsync(hb + f_tree, ip(o_tree), N * sizeof(int), hipMemcpyDeviceToDevice, st));
-  ROM_HIP(hipStreamSynchronize(st));   // (the workspace goes back to the allocator)
-  ++syncs;
-  h->thr = hb + f_thr;
-  h->n = hb + f_n;
-  h->val = hb + f_val;
-  h->feat = reinterpret_cast<const int*>(hb + f_feat);
-  h->left = reinterpret_cast<const int*>(hb + f_left);
-  h->tree = reinterpret_cast<const int*>(hb + f_tree);
-  h->launches = launches;
-  h->syncs = syncs;
-  if (info_host) {
-    info_host[0] = double(N);
-    info_host[1] = double((N + T) / 2);   // nodes = 2 leaves - 1 in every tree
-    info_host[2] = double(levels - 1);
-    info_host[3] = double(levels);
-    info_host[4] = double(launches);
-    info_host[5] = double(syncs);
-    info_host[6] = double(ws_bytes);
-    info_host[7] = 0.0;
+  // the roots: node t is the root of tree t and owns the tree's positions
+  int roots() {
+    const TreeDev& d = ws.d;
+    const int T = s.T, R = s.R;
+    h_nid.resize(R);
+    h_int.resize(T);
+    h_key.assign(T, TR_NOKEY);
+    for (int t = 0; t < T; ++t)
+      for (int p = s.tree_start[t]; p < s.tree_start[t + 1]; ++p) h_nid[p] = t;
+    ROM_HIP(hipMemcpyAsync(ws.nid[0], h_nid.data(), size_t(R) * sizeof(int), hipMemcpyHostToDevice, st));
+    ROM_HIP(hipMemcpyAsync(d.start, s.tree_start.data(), T * sizeof(int), hipMemcpyHostToDevice, st));
+    ROM_HIP(hipMemcpyAsync(d.end, s.tree_start.data() + 1, T * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int t = 0; t < T; ++t) h_int[t] = t;
+    ROM_HIP(hipMemcpyAsync(d.treeid, h_int.data(), T * sizeof(int), hipMemcpyHostToDevice, st));
+    ROM_HIP(hipMemsetAsync(d.parent, 0xff, T * sizeof(int), st));   // -1
+    ROM_HIP(hipMemsetAsync(d.feat, 0xff, T * sizeof(int), st));
+    ROM_HIP(hipMemsetAsync(d.left, 0xff, T * sizeof(int), st));
+    ROM_HIP(hipMemsetAsync(d.depth, 0, T * sizeof(int), st));
+    ROM_HIP(hipMemsetAsync(d.nlr, 0, T * sizeof(int), st));
+    ROM_HIP(hipMemsetAsync(d.nonconst, 0, T * sizeof(int), st));
+    ROM_HIP(hipMemsetAsync(d.thr, 0, T * sizeof(double), st));
+    ROM_HIP(hipMemsetAsync(d.n, 0, T * sizeof(double), st));
+    ROM_HIP(hipMemsetAsync(d.bestgain, 0, T * sizeof(u64), st));
+    ROM_HIP(hipMemcpyAsync(d.bestkey, h_key.data(), T * sizeof(u64), hipMemcpyHostToDevice, st));
+    return ROM_OK;
   }
-  guard.h = nullptr;
-  *out = h;
+
+  // the levels: all open nodes of all trees per level, one read-back (the number of new nodes) each
+  int grow(int max_depth, int min_samples_split, int min_samples_leaf) {
+    TreeDev& d = ws.d;
+    const int m = s.m, R = s.R, Q1 = s.q + 1;
+    const unsigned gx = unsigned((s.ntiles + TR_WAVES - 1) / TR_WAVES);
+    const dim3 g1(gx, 1), gm(gx, unsigned(m));
+    const double msl = double(min_samples_leaf), mss = double(min_samples_split);
+    const double lvl_bytes = 8.0 * double(R) * (s.q + 2);
+    int lvl0 = 0, lvl1 = s.T, cur = 0;
+    for (;;) {
+      d.lvl0 = lvl0;
+      d.ord = ws.ord[cur];
+      d.nid = ws.nid[cur];
+      {
+        ROM_PROF(ctx, "tree_stats", 4.0 * R * Q1, 4.0 * lvl_bytes);
+        k_tree_scan<0><<<g1, 256, 0, st>>>(d, 0, msl);
+        k_tree_scan<1><<<g1, 256, 0, st>>>(d, 0, msl);
+        ROM_HIP(hipGetLastError());
+      }
+      {
+        ROM_PROF(ctx, "tree_tiles", 1.0 * m * R * Q1, m * lvl_bytes);
+        k_tree_scan<0><<<gm, 256, 0, st>>>(d, 1, msl);
+        ROM_HIP(hipGetLastError());
+      }
+      {
+        ROM_PROF(ctx, "tree_stats", 4.0 * R * Q1, 4.0 * lvl_bytes);
+        k_tree_scan<2><<<g1, 256, 0, st>>>(d, 1, msl);
+        ROM_HIP(hipGetLastError());
+      }
+      {
+        ROM_PROF(ctx, "tree_gain", 6.0 * m * R * Q1, m * lvl_bytes);
+        k_tree_scan<3><<<gm, 256, 0, st>>>(d, 1, msl);
+        ROM_HIP(hipGetLastError());
+      }
+      {
+        ROM_PROF(ctx, "tree_decide", 0.0, 12.0 * m * R);
+        k_tree_pick<<<blocks_for(size_t(m) * R), 256, 0, st>>>(d);
+        k_tree_decide<<<1, 1024, 0, st>>>(d, lvl1, max_depth, mss, ws.counter);
+        ROM_HIP(hipGetLastError());
+      }
+      launches += 7;
+      ++levels;
+      int fresh = 0;
+      ROM_HIP(hipMemcpyAsync(&fresh, ws.counter, sizeof(int), hipMemcpyDeviceToHost, st));
+      ROM_HIP(hipStreamSynchronize(st));
+      ++syncs;
+      if (fresh == 0) break;
+      ROM_CHECK(size_t(lvl1) + size_t(fresh) <= s.nmax, "rom_tree_fit: %d + %d nodes exceed the bound 2 R - T = %zu (internal error)", lvl1,
+                fresh, s.nmax);
+      {
+        ROM_PROF(ctx, "tree_partition", 0.0, 24.0 * m * R);
+        k_tree_part<false><<<gm, 256, 0, st>>>(d, ws.itail, ws.ord[cur ^ 1], ws.nid[cur ^ 1]);
+        k_tree_part<true><<<gm, 256, 0, st>>>(d, ws.itail, ws.ord[cur ^ 1], ws.nid[cur ^ 1]);
+        ROM_HIP(hipGetLastError());
+      }
+      launches += 2;
+      cur ^= 1;
+      lvl0 = lvl1;
+      lvl1 += fresh;
+    }
+    nodes = lvl1;
+    return ROM_OK;
+  }
+
+  // the handle: the node arrays at their final size, the counters and info_host
+  int handle(rom_tree* h, double* info_host) {
+    const TreeDev& d = ws.d;
+    const size_t N = size_t(nodes), q = size_t(s.q);
+    h->nodes = int64_t(N);
+    h->levels = levels;
+    ROM_TRY(rom_buf_alloc(ctx, TreeNodes(nullptr, N, s.q).doubles, &h->dev));
+    const TreeNodes a(h->dev->p, N, s.q);
+    ROM_HIP(hipMemcpyAsync(a.thr, d.thr, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    ROM_HIP(hipMemcpyAsync(a.n, d.n, N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    ROM_HIP(hipMemcpyAsync(a.val, d.val, N * q * sizeof(double), hipMemcpyDeviceToDevice, st));
+    ROM_HIP(hipMemcpyAsync(a.feat, d.feat, N * sizeof(int), hipMemcpyDeviceToDevice, st));
+    ROM_HIP(hipMemcpyAsync(a.left, d.left, N * sizeof(int), hipMemcpyDeviceToDevice, st));
+    ROM_HIP(hipMemcpyAsync(a.tree, d.treeid, N * sizeof(int), hipMemcpyDeviceToDevice, st));
+    ROM_HIP(hipStreamSynchronize(st));   // (the workspace goes back to the allocator)
+    ++syncs;
+    h->thr = a.thr, h->n = a.n, h->val = a.val, h->feat = a.feat, h->left = a.left, h->tree = a.tree;
+    h->launches = launches, h->syncs = syncs;
+    if (info_host) {
+      info_host[0] = double(N);
+      info_host[1] = double((N + s.T) / 2);   // nodes = 2 leaves - 1 in every tree
+      info_host[2] = double(levels - 1);
+      info_host[3] = double(levels);
+      info_host[4] = double(launches);
+      info_host[5] = double(syncs);
+      info_host[6] = double(ws.doubles * sizeof(double));
+      info_host[7] = 0.0;
+    }
+    return ROM_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" int rom_tree_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int m, rom_buf* Y, size_t y_off, int64_t ldy, int q,
+                            int64_t M, int T, const int32_t* counts_host, int max_depth, int min_samples_split, int min_samples_leaf,
+                            rom_tree** out, double* info_host) {
+  const char* who = "rom_tree_fit";
+  ROM_CHECK(ctx && X && Y && out, "rom_tree_fit: null argument (context, X, Y or the handle's address)");
+  ROM_CHECK(m >= 1 && m <= TR_MMAX, "rom_tree_fit: m = %d inputs, between 1 and %d", m, TR_MMAX);
+  ROM_CHECK(q >= 1 && q <= TR_QMAX, "rom_tree_fit: q = %d target columns, between 1 and %d", q, TR_QMAX);
+  ROM_CHECK(T >= 1 && T <= TR_TMAX, "rom_tree_fit: T = %d trees, between 1 and %d", T, TR_TMAX);
+  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 30), "rom_tree_fit: M = %lld rows, between 1 and 2^30", (long long)M);
+  ROM_CHECK(max_depth >= 0, "rom_tree_fit: max_depth = %d, 0 (no limit) or more", max_depth);
+  ROM_CHECK(min_samples_split >= 2, "rom_tree_fit: min_samples_split = %d, at least 2", min_samples_split);
+  ROM_CHECK(min_samples_leaf >= 1, "rom_tree_fit: min_samples_leaf = %d, at least 1", min_samples_leaf);
+  ROM_TRY(rom_check_block(who, {"X", "ldx", "m"}, X->n, x_off, ldx, m, M));
+  ROM_TRY(rom_check_block(who, {"Y", "ldy", "q"}, Y->n, y_off, ldy, q, M));
+  TreeShape shape{M, m, q, T, counts_host != nullptr};
+  ROM_TRY(tree_rows(counts_host, shape));
+  ROM_HIP(hipSetDevice(ctx->device));
+
+  TreeFit fit(ctx, shape, counts_host);
+  ROM_TRY(fit.ws.get(ctx, shape, X->p + x_off, ldx, Y->p + y_off, ldy));
+  ROM_TRY(fit.check_and_presort());
+  ROM_TRY(fit.roots());
+  ROM_TRY(fit.grow(max_depth, min_samples_split, min_samples_leaf));
+  rom_tree* h = new rom_tree;
+  HandleGuard<rom_tree, rom_tree_destroy> guard{h};
+  h->ctx = ctx, h->m = m, h->q = q, h->T = T, h->M_train = M;
+  ROM_TRY(fit.handle(h, info_host));
+  *out = guard.release();
   return ROM_OK;
 }
 
@@ -698,52 +740,26 @@ extern "C" int rom_tree_predict(rom_tree* h, rom_buf* X, size_t x_off, int64_t l
   ROM_CHECK(OUT || sumsq_host, "rom_tree_predict: OUT == NULL requires sumsq_host");
   rom_ctx* ctx = h->ctx;
   const int m = h->m, q = h->q;
-  ROM_CHECK(M >= 1 && M <= (int64_t(1) << 40), "rom_tree_predict: M = %lld rows, at least 1", (long long)M);
-  ROM_CHECK(ldx >= m, "rom_tree_predict: ldx = %lld < m = %d", (long long)ldx, m);
-  ROM_CHECK(x_off + size_t(M - 1) * size_t(ldx) + size_t(m) <= X->n,
-            "rom_tree_predict: X holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", X->n, (long long)M, m, x_off,
-            (long long)ldx);
-  if (OUT) {
-    ROM_CHECK(ldo >= q, "rom_tree_predict: ldo = %lld < q = %d", (long long)ldo, q);
-    ROM_CHECK(o_off + size_t(M - 1) * size_t(ldo) + size_t(q) <= OUT->n,
-              "rom_tree_predict: OUT holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", OUT->n, (long long)M, q,
-              o_off, (long long)ldo);
-    ROM_CHECK(!tr_ranges_overlap(X->p + x_off, size_t(M - 1) * size_t(ldx) + m, OUT->p + o_off, size_t(M - 1) * size_t(ldo) + q),
-              "rom_tree_predict: OUT overlaps X (the inputs are read while the predictions are written)");
-  }
-  if (Yref) {
-    ROM_CHECK(ldr >= q, "rom_tree_predict: ldr = %lld < q = %d", (long long)ldr, q);
-    ROM_CHECK(r_off + size_t(M - 1) * size_t(ldr) + size_t(q) <= Yref->n,
-              "rom_tree_predict: Yref holds %zu doubles, %lld rows of %d at offset %zu with stride %lld need more", Yref->n, (long long)M, q,
-              r_off, (long long)ldr);
-  }
+  ROM_TRY(rom_check_predict_blocks("rom_tree_predict", M, X, x_off, ldx, m, q, OUT, o_off, ldo, Yref, r_off, ldr));
   ROM_HIP(hipSetDevice(ctx->device));
   const long long groups = (M + TR_PRED_ROWS - 1) / TR_PRED_ROWS;
   const int chunks = int(std::min<long long>(groups, 4ll * std::max(ctx->n_cu, 1)));
   const long long per = (groups + chunks - 1) / chunks;
-  Tmp SS, sums;
-  if (sumsq_host) {
-    ROM_TRY(SS.get(ctx, size_t(chunks) * q));
-    ROM_TRY(sums.get(ctx, q));
-  }
+  SumsqTail tail;
+  if (sumsq_host) ROM_TRY(tail.get(ctx, chunks, q));
   {
     ROM_PROF(ctx, "tree_predict", 0.0, 8.0 * M * (m + q * (Yref ? 2.0 : 1.0)));
     k_tree_predict<<<chunks, 256, 0, ctx->stream>>>(h->feat, h->left, h->thr, h->val, q, h->T, X->p + x_off, ldx, M, groups, per,
                                                     OUT ? OUT->p + o_off : nullptr, ldo, Yref ? Yref->p + r_off : nullptr, ldr,
-                                                    sumsq_host ? SS.p() : nullptr);
+                                                    tail.partials());
   }
   ROM_HIP(hipGetLastError());
-  h->launches += 1;
-  if (sumsq_host) {
-    kb_partials_colsum<<<blocks_for(q), 256, 0, ctx->stream>>>(SS, chunks, q, 1.0, sums);
-    ROM_HIP(hipGetLastError());
-    h->launches += 1;
-    ROM_HIP(hipMemcpyAsync(sumsq_host, sums.p(), size_t(q) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  ROM_HIP(hipStreamSynchronize(ctx->stream));
+  h->launches += sumsq_host ? 2 : 1;   // (the column sums of the tail are a launch)
+  ROM_TRY(tail.finish(ctx, chunks, q, sumsq_host));
   h->syncs += 1;
   return ROM_OK;
 }
+
 
 extern "C" int rom_tree_query(rom_tree* h, int64_t* out8) {
   ROM_CHECK(h && out8, "rom_tree_query: null argument");

@@ -327,6 +327,20 @@ def test_error_cases(ctx):
     fails(["rom_mlp_download", "count"], lambda: _ffi.check(ctx.lib.rom_mlp_download(h.h, 0, np.zeros(4).ctypes.data, 4)))
 
 
+def test_blocks_that_end_on_the_last_double_of_their_buffers(ctx):
+    import tight_blocks as tb
+    from romhighcontrast_amd import _ffi
+    from romhighcontrast_amd.nonlinear import MLPMap
+    w0 = MLPMap.initial_weights([tb.m, 5, tb.q], "tanh", 0)
+    h, bufs = tb.check(ctx, "rom_mlp", lambda *blocks: ctx.mlp_fit(*blocks, [5], w0, max_iter=3))
+    # rom_mlp_loss_grad reads X and Y the same way
+    (loss, grad), (loss64, grad64) = (h.loss_grad(bufs[s][0], tb.X_OFF, tb.LD, bufs[s][1], tb.Y_OFF, tb.LD, tb.M) for s in (0, 64))
+    assert _same_bits([loss], [loss64]) and _same_bits(grad, grad64)
+    for words, s_x, s_y in ((f"X holds {bufs[-1][0].n}", -1, 0), (f"Y holds {bufs[-1][1].n}", 0, -1)):
+        with pytest.raises(_ffi.RomLibraryError, match=words):
+            h.loss_grad(bufs[s_x][0], tb.X_OFF, tb.LD, bufs[s_y][1], tb.Y_OFF, tb.LD, tb.M)
+
+
 def test_estimator_nn(ctx):
     from src.lib.Estimators import EstimatorNN
     from romhighcontrast_amd.nonlinear import MLPMap

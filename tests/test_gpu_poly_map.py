@@ -362,6 +362,11 @@ def test_error_cases(ctx):
     assert pmc.info["stop_reason"] == "terms_dropped" and pmc.info["rank"] == 3 and pmc.download("h")[1] == 0.0, pmc.info
 
 
+def test_blocks_that_end_on_the_last_double_of_their_buffers(ctx):
+    import tight_blocks
+    tight_blocks.check(ctx, "rom_poly", lambda *blocks: ctx.poly_fit(*blocks, 2))
+
+
 # ---- which kernels ran: a child process (ROMHC_PROF_DETAIL is read once per process) -----------------------------------
 def test_kernels_confirmed_by_profile_names():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -308,3 +308,9 @@ def test_error_cases(ctx):
     fails(["rom_tree_predict", "Yref holds 400"], tm.predict, Z, 0, 8, 50, OUT=out, Yref=Z, r_off=6, ldr=8)
     fails(["rom_tree_predict", "OUT overlaps X"], tm.predict, Z, 0, 8, 40, OUT=Z, o_off=4, ldo=8)
     fails(["rom_tree_download", "count"], lambda: _ffi.check(ctx.lib.rom_tree_download(tm.h, 1, np.zeros(4).ctypes.data, 4)))
+
+
+def test_blocks_that_end_on_the_last_double_of_their_buffers(ctx):
+    import tight_blocks
+    counts = np.random.default_rng(6).integers(0, 3, (2, tight_blocks.M)).astype(np.int32)
+    tight_blocks.check(ctx, "rom_tree", lambda *blocks: ctx.tree_fit(*blocks, 2, counts))
