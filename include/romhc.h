@@ -549,6 +549,52 @@ int rom_tree_destroy(rom_tree* h);
 int rom_nearest(rom_ctx* ctx, rom_buf* Q, size_t q_off, int64_t ldq, int64_t M, rom_buf* P, size_t p_off, int64_t ldp, int K, int r,
                 int t, int mode, int64_t* idx_host, double* dist2_host, double* info_host);
 
+/* ---- k-means on a tall block: the clustering of the local reduced bases (romhighcontrast_amd/local.py) --------------------------
+ * Lloyd's algorithm on the M rows of X (r columns from an element offset with a row stride, as in rom_poly_fit; never modified)
+ * against kc centroids.  Limits: 1 <= r <= 128, 1 <= kc <= 256, padded kc (to 16) x padded r (to 4) <= 8192 doubles -- (64, 128),
+ * (128, 64) and (256, 32) are inside -- and kc <= M < 2^31; ROM_ERR_INVALID outside, and for NaN / Inf in the block or the
+ * initial centroids.
+ * The answer is defined as rom_nearest defines its own: dist2 = sum_c (x_c - c_c)^2 from the original operands by the ONE device
+ * function of rom_nearest (differences first, one fma chain in column order: within (r + 2) eps relative of the exact value, 0.0
+ * for a coincident row), and the label of a row is the centroid that is smallest under the order (that value, centroid index):
+ * bit for bit what an exhaustive scan returns.  mode 1 (test hook and definition) is that scan; mode 0, the product path, is one
+ * fused MFMA kernel per iteration -- screen scores |c~|^2 - 2 x~ . c~ on operands shifted by the column means mu of the block,
+ * exact rescoring of every centroid within a proven bound of the smallest score, one-hot accumulation of the cluster sums and
+ * counts -- and returns the same bits.  Update: c_j = mu + (sum of x - mu over the members, fixed order) / n_j; an empty cluster
+ * keeps its centroid bit for bit and reports the count 0.
+ * Iteration t assigns against C_t and updates to C_t+1.  It stops when no label changed (converged), when max_j |C_t+1,j -
+ * C_t,j|^2 <= tol x (mean column variance of the block), or at max_iter; the call always ends with an assignment against the
+ * centroids it returns, which labels, counts and the last inertia refer to.  The stop test runs on the device; the host
+ * enqueues iterations in groups of 8 and reads one status word per group: host synchronisations <= 2 + ceil(iterations / 8).
+ * No floating-point atomics: the same bits on a repeated call. */
+typedef struct rom_kmeans rom_kmeans;
+/* (local reduced bases: no counterpart in the reference) host only, no context; the single place of the limits and of the LDS
+ * carve-up of the fused kernel.  out8: padded r, padded kc, LDS bytes of the fused kernel, rows of a slab (a workgroup's chunk
+ * is a whole number of them), padded r + 1, row stride of the score / one-hot tile, doubles of a workgroup's partial,
+ * accumulator tiles per wave. */
+int rom_kmeans_layout(int r, int kc, int64_t* out8);
+/* (local reduced bases) deterministic farthest-point start: rows_host[0] = the row nearest to the column means, rows_host[s] =
+ * the row farthest from the rows chosen before it (largest minimum of dist2), the lowest row index among equals in both.  One
+ * small kernel per centre, one host synchronisation. */
+int rom_kmeans_init_maximin(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int r, int64_t M, int kc, int64_t* rows_host);
+/* (local reduced bases) init_host: kc x r initial centroids.  max_iter = 0: the handle holds the initial centroids and their
+ * assignment.  info_host (8 doubles or NULL): iterations, converged (0 / 1), kernel launches, host synchronisations, bytes of
+ * workspace, workgroup chunks, rows rescored beyond the first candidate (all passes), executed flops. */
+int rom_kmeans_fit(rom_ctx* ctx, rom_buf* X, size_t x_off, int64_t ldx, int r, int64_t M, int kc, const double* init_host,
+                   int max_iter, double tol, int mode, rom_kmeans** out, double* info_host);
+/* (local reduced bases) labels (and dist2_host, inertia_host: either may be NULL) of any block of M rows against the handle's
+ * centroids, by the same kernels.  One host synchronisation. */
+int rom_kmeans_assign(rom_kmeans* h, rom_buf* X, size_t x_off, int64_t ldx, int64_t M, int mode, int32_t* labels_host,
+                      double* dist2_host, double* inertia_host);
+/* (local reduced bases) out8: r, kc, M_train, iterations, converged, stop reason (0 no label changed, 1 tolerance, 2 iteration
+ * budget), kernel launches, host synchronisations so far */
+int rom_kmeans_query(rom_kmeans* h, int64_t* out8);
+/* (local reduced bases) host copies: what = 0 centroids (kc x r), 1 counts (kc), 2 inertia of the assignment of every iteration,
+ * then of the final one (iterations + 1), 3 the shift mu (r), 4 labels of the training rows (M_train, as doubles).  count must
+ * be the size of the part. */
+int rom_kmeans_download(rom_kmeans* h, int what, double* host, size_t count);
+int rom_kmeans_destroy(rom_kmeans* h);
+
 /* ---- the polish of the library-based parameter estimation (romhighcontrast_amd/inverse.py::polish_parameters) ----------------
  * Levenberg-Marquardt in theta = log a for  min ||p - G_r c(theta)||^2 + perp2,  c(theta) = (sum_q e^theta_q Ahat_q)^-1 bhat,
  * for K queries from t starts each: the algorithm of polish_parameters (damping, acceptance, lambda schedule, eight trials, the

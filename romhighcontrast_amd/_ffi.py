@@ -137,6 +137,14 @@ PROTOTYPES = {
     "rom_mlp_destroy": (C.c_int, [_vp]),
     "rom_nearest": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, C.c_int,
                               C.c_int, _vp, _vp, _vp]),
+    "rom_kmeans_layout": (C.c_int, [C.c_int, C.c_int, _vp]),
+    "rom_kmeans_init_maximin": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int, _vp]),
+    "rom_kmeans_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int, _vp, C.c_int, C.c_double, C.c_int, _vp,
+                                 _vp]),
+    "rom_kmeans_assign": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "rom_kmeans_query": (C.c_int, [_vp, _vp]),
+    "rom_kmeans_download": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
+    "rom_kmeans_destroy": (C.c_int, [_vp]),
     "rom_lm_polish": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp,
                                 _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_poly_sense": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
@@ -374,6 +382,29 @@ class Context:
                  launches=int(info[4]), host_syncs=int(info[5]), workspace_bytes=int(info[6]), executed_flops=float(info[7]))
         return idx, dist2, d
 
+    def kmeans_layout(self, r, kc) -> dict:
+        """rom_kmeans_layout (host only): see the module function ``kmeans_layout``."""
+        return kmeans_layout(r, kc)
+
+    def kmeans_init_maximin(self, X: "Buffer", x_off, ldx, r, M, kc) -> np.ndarray:
+        """rom_kmeans_init_maximin: the kc rows of the deterministic farthest-point start (the row nearest to the column means,
+        then always the row farthest from the rows chosen so far; lowest index among equals), int64."""
+        kmeans_layout(r, kc)
+        rows = np.zeros(int(kc), dtype=np.int64)
+        _check_kmeans(self.lib.rom_kmeans_init_maximin(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(r), int(M), int(kc),
+                                                       rows.ctypes.data))
+        return rows
+
+    def kmeans_fit(self, X: "Buffer", x_off, ldx, r, M, kc, init, max_iter=50, tol=0.0, mode=0) -> "KMeansHandle":
+        """rom_kmeans_fit: Lloyd's algorithm on the M rows of X (r columns from element x_off, row stride ldx; not modified) from
+        the (kc, r) initial centroids ``init``.  mode 1: the exhaustive scan instead of the fused screen (the same bits).
+        max_iter = 0: the handle holds ``init`` and its assignment.  Returns the KMeansHandle."""
+        return KMeansHandle(self, X, x_off, ldx, r, M, kc, init, max_iter, tol, mode)
+
+    def kmeans_assign(self, handle: "KMeansHandle", X: "Buffer", x_off, ldx, M, mode=0, dist2=True):
+        """rom_kmeans_assign: (labels (M,) int32, dist2 (M,) or None, inertia) of the M rows of X against the handle's centroids."""
+        return handle.assign(X, x_off, ldx, M, mode=mode, dist2=dist2)
+
     def lm_polish(self, n, k, r, Ahat: "Buffer", bhat: "Buffer", Gr: "Buffer", P: "Buffer", p_off, ldp, K, t, THETA0: "Buffer", lo, hi,
                   AUX: "Buffer | None" = None, max_iter=30, misfit_tol=1e-3, OUT: "Buffer | None" = None, out_off=0, ldo=None):
         """rom_lm_polish: inverse.polish_parameters on the device in reduced sensor coordinates (P: K rows p = U^T (w y) of r
@@ -544,6 +575,24 @@ def poly_terms(m: int, degree: int) -> np.ndarray:
     powers = np.zeros((P.value, int(m)), dtype=np.int32)
     check(lib.rom_poly_terms(int(m), int(degree), C.byref(P), powers.ctypes.data))
     return powers
+
+
+def _check_kmeans(status: int):
+    """``check`` with the limits and NaN / Inf of rom_kmeans_* as ValueError (scikit-learn's estimators raise that)."""
+    if status == ROM_ERR_INVALID:
+        raise ValueError(last_error())
+    check(status)
+
+
+def kmeans_layout(r: int, kc: int) -> dict:
+    """rom_kmeans_layout (host only; the single place of the limits and of the LDS carve-up of the fused kernel).  ValueError
+    outside the limits."""
+    lib = load_library()
+    out = np.zeros(8, dtype=np.int64)
+    if lib.rom_kmeans_layout(int(r), int(kc), out.ctypes.data) != ROM_OK:
+        raise ValueError(last_error())
+    keys = ("r_padded", "kc_padded", "lds_bytes", "slab_rows", "r1_padded", "tile_stride", "partial_doubles", "tiles_per_wave")
+    return {k: int(v) for k, v in zip(keys, out)}
 
 
 MLP_ACTIVATIONS = {"tanh": 0, "logistic": 1, "sigmoid": 1, "relu": 2}
@@ -797,6 +846,64 @@ class TreeMapHandle(_MapHandle):
             check(self.ctx.lib.rom_tree_download(self.h, what, a.ctypes.data, a.size))
             out[part] = a.reshape(n, self.q) if what == 5 else a if what in (2, 4) else a.astype(np.int64)
         return out
+
+
+class KMeansHandle:
+    """Handle of a fitted k-means (rom_kmeans_*): owns the device centroids, shift and training labels, destroyed on
+    collection."""
+
+    _QUERY_KEYS = ("r", "kc", "M_train", "iterations", "converged", "stop_reason", "launches", "host_syncs")
+    _PARTS = {"centroids": 0, "counts": 1, "inertia": 2, "shift": 3, "labels": 4}
+    h = None
+
+    def __init__(self, ctx: Context, X: Buffer, x_off, ldx, r, M, kc, init, max_iter=50, tol=0.0, mode=0):
+        self.ctx = ctx
+        self.h = None
+        self.layout = kmeans_layout(r, kc)              # (ValueError outside the limits, before any device call)
+        init = _host(np.asarray(init, dtype=np.float64))
+        if init.shape != (int(kc), int(r)):
+            raise ValueError(f"kmeans_fit: initial centroids of shape {init.shape}, expected ({kc}, {r})")
+        h, info = _vp(), np.zeros(8)
+        _check_kmeans(ctx.lib.rom_kmeans_fit(ctx.h, X.h if X is not None else None, int(x_off), int(ldx), int(r), int(M), int(kc),
+                                             init.ctypes.data, int(max_iter), float(tol), int(mode), C.byref(h), info.ctypes.data))
+        self.h = h
+        self.r, self.kc, self.M = int(r), int(kc), int(M)
+        self.info = dict(iterations=int(info[0]), converged=bool(info[1]), launches=int(info[2]), host_syncs=int(info[3]),
+                         workspace_bytes=int(info[4]), chunks=int(info[5]), rows_rescored_more=int(info[6]),
+                         executed_flops=float(info[7]))
+
+    def query(self) -> dict:
+        out = np.zeros(8, dtype=np.int64)
+        check(self.ctx.lib.rom_kmeans_query(self.h, out.ctypes.data))
+        return {k: int(v) for k, v in zip(self._QUERY_KEYS, out)}
+
+    def download(self, part: str) -> np.ndarray:
+        """Host copy of "centroids" (kc, r), "counts" (kc,) int64, "inertia" (iterations + 1,: of the assignment of every
+        iteration, then of the final one), "shift" (r,) or the "labels" of the training rows (M,) int32."""
+        it = self.info["iterations"]
+        shape = {"centroids": (self.kc, self.r), "counts": (self.kc,), "inertia": (it + 1,), "shift": (self.r,), "labels": (self.M,)}[part]
+        out = np.zeros(shape)
+        check(self.ctx.lib.rom_kmeans_download(self.h, self._PARTS[part], out.ctypes.data, out.size))
+        return out.astype(np.int64) if part == "counts" else out.astype(np.int32) if part == "labels" else out
+
+    def assign(self, X: Buffer, x_off, ldx, M, mode=0, dist2=True):
+        labels = np.zeros(int(M), dtype=np.int32)
+        d2 = np.zeros(int(M)) if dist2 else None
+        inertia = np.zeros(1)
+        _check_kmeans(self.ctx.lib.rom_kmeans_assign(self.h, X.h if X is not None else None, int(x_off), int(ldx), int(M), int(mode),
+                                                     labels.ctypes.data, d2.ctypes.data if dist2 else None, inertia.ctypes.data))
+        return labels, d2, float(inertia[0])
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.rom_kmeans_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 _contexts = {}

@@ -29,37 +29,19 @@
 
 #include "rom_basis_int.h"
 #include "rom_block.h"
+#include "rom_dist.h"
 #include "rom_slab.h"
 
 namespace {
 
-constexpr int NN_RMAX = 128, NN_TMAX = 8;
+constexpr int NN_TMAX = 8;              // (NN_RMAX, NN_EPS, NN_INF, nn_dist2, nn_less and the column statistics: rom_dist.h)
 constexpr int NN_EXTRA = 4;          // T' = t + NN_EXTRA groups are rescored
 constexpr int NN_SLOTS = 16;         // slabs whose minima wait in LDS: one query's minima leave as a 128-byte line
 constexpr int NN_LDM = NN_SLOTS + 1;
 constexpr int NN_QB = 16;            // queries of one workgroup of the exhaustive kernel (four per wave)
 constexpr int NN_TILE = 64;          // library rows of one tile of the exhaustive kernel (a lane each)
 constexpr int NN_STAT = 130;         // mean (128) | non-finite entries of Q | of P
-constexpr double NN_EPS = 2.220446049250313e-16;   // 2^-52
-constexpr double NN_INF = __builtin_huge_val();
 constexpr long long NN_NOROW = 0x7fffffffffffffffLL;
-
-// ---- THE distance: out[n] += sum_c (p_n[c] - q[c])^2, n < N query rows ldp apart, columns in order ----------------------------
-template <int N>
-__device__ __forceinline__ void nn_dist2(const double* __restrict__ p, int ldp, const double* __restrict__ q, int r, double (&out)[N]) {
-#pragma unroll
-  for (int n = 0; n < N; ++n) out[n] = 0.0;
-  for (int c = 0; c < r; ++c) {
-    const double qc = q[c];
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-      const double d = p[n * ldp + c] - qc;
-      out[n] = fma(d, d, out[n]);
-    }
-  }
-}
-
-__device__ __forceinline__ bool nn_less(double d, long long j, double d2, long long j2) { return d < d2 || (d == d2 && j < j2); }
 
 // ---- a sorted list of t (distance, row) pairs held by the lanes s < t of a wave ----------------------------------------------
 // insert the wave-uniform candidate (cd, cj): the entries below it are a prefix of the list, the rest moves up one lane
@@ -91,64 +73,6 @@ __device__ __forceinline__ void topt_offer(double& ed, long long& ej, double d, 
     const double cd = __shfl(d, l, 64);
     const long long cj = __shfl(j, l, 64);
     topt_insert(ed, ej, cd, cj, t, lane);
-  }
-}
-
-// ---- column sums and the count of non-finite entries, fixed-order partials ---------------------------------------------------
-// part[chunk][c] = sum of column c over the chunk's rows, part[chunk][128] = its entries that are NaN or Inf.  256 threads =
-// (256 / rp) row lanes x rp columns, rp the power of two >= r.
-__global__ __launch_bounds__(256) void k_nn_stats_partial(const double* __restrict__ X, long long ld, long long rows, int r, int rp,
-                                                          long long rows_per_chunk, double* __restrict__ part) {
-  __shared__ double ssum[256], sbad[256];
-  const int t = threadIdx.x, c = t & (rp - 1), nl = 256 / rp, ry = t / rp;
-  const long long r0 = (long long)blockIdx.x * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
-  double s = 0.0, bad = 0.0;
-  if (c < r)
-    for (long long j = r0 + ry; j < r1; j += nl) {
-      const double v = X[j * ld + c];
-      s += v;
-      bad += fabs(v) <= 1.7976931348623157e308 ? 0.0 : 1.0;
-    }
-  ssum[t] = s;
-  sbad[t] = bad;
-  __syncthreads();
-  double* out = part + size_t(blockIdx.x) * (NN_RMAX + 1);
-  if (t < rp && t < r) {
-    for (int q = 1; q < nl; ++q) s += ssum[q * rp + t];
-    out[t] = s;
-  }
-  if (t == 0) {
-    double b = 0.0;
-    for (int q = 0; q < 256; ++q) b += sbad[q];   // (a count: exact in any order)
-    out[NN_RMAX] = b;
-  }
-}
-// stat[c] = column mean (mean != 0), stat[bad_at] = the count.  1024 threads = 8 sub-sums x 128 columns: sub-sum s adds the
-// chunks s, s + 8, ... in order, then the eight are added in order (a single chain over all chunks is latency-bound)
-__global__ __launch_bounds__(1024) void k_nn_stats_finish(const double* __restrict__ part, int chunks, int r, long long rows, int mean,
-                                                          int bad_at, double* __restrict__ stat) {
-  __shared__ double sub[8][NN_RMAX + 1];
-  const int c = threadIdx.x & 127, sl = threadIdx.x >> 7;
-  {
-    double s = 0.0, b = 0.0;
-    for (int q = sl; q < chunks; q += 8) {
-      if (c < r) s += part[size_t(q) * (NN_RMAX + 1) + c];
-      if (c == 0) b += part[size_t(q) * (NN_RMAX + 1) + NN_RMAX];
-    }
-    sub[sl][c] = s;
-    if (c == 0) sub[sl][NN_RMAX] = b;
-  }
-  __syncthreads();
-  if (sl != 0) return;
-  if (mean && c < r) {
-    double s = sub[0][c];
-    for (int q = 1; q < 8; ++q) s += sub[q][c];
-    stat[c] = s / double(rows);
-  }
-  if (c == 0) {
-    double b = 0.0;
-    for (int q = 0; q < 8; ++q) b += sub[q][NN_RMAX];
-    stat[bad_at] = b;
   }
 }
 

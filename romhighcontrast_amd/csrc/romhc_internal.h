@@ -96,6 +96,7 @@ struct rom_ctx {
   bool lds_optin_poly_pass = false, lds_optin_poly_predict = false;
   bool lds_optin_nn_screen = false, lds_optin_nn_exhaust = false;
   bool lds_optin_mlp_eval = false, lds_optin_mlp_predict = false;
+  bool lds_optin_km_step = false;
 };
 
 struct rom_buf {

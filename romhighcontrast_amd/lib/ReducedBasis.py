@@ -873,3 +873,7 @@ def pca_tall(ctx: _ffi.Context, X, n=None, center=True, scores=True, download=Tr
         comps, mu = DeviceArray(V, n, dim), DeviceArray(mean, 1, dim)
         sc = DeviceArray(S, M, n) if scores else None
     return TallPCA(comps, sig, mu, M, info["resolved_modes"], scores=sc, info=info, ctx=ctx)
+
+
+# ---- clustered local bases (romhighcontrast_amd/local.py), exported beside the global ones ---------------------------------
+from ..local import KMeans, LocalReducedBasis  # noqa: E402,F401
