@@ -1,4 +1,4 @@
-// Pieces of the basis stage shared by the files built on rom_basis.hip (internal).
+// Pieces of the basis stage shared by the files built on rom_basis.hip and rom_small_dense.hip (internal).
 #pragma once
 #include <algorithm>
 
@@ -152,18 +152,12 @@ __global__ void kb_grow_ahat(double* __restrict__ Ahat, int k, int ld, int j, co
                              const int* __restrict__ degenerate, int it);
 __global__ void kb_galerkin_gap(int M, int n, const double* __restrict__ P, const double* __restrict__ c, double* __restrict__ extra2);
 
-// ---- small dense problems and orthonormalisation helpers of rom_basis.hip, shared with rom_pod.hip ------------------
-enum { SE_EIG = 0, SE_WHITEN = 1, SE_LOWDIN = 2 };
-constexpr int SE_LDS_MAX = 96, SE_MAX = 1024;
-// (the grid-wide Jacobi takes larger orders -- four buffers of n^2 doubles, n launches per sweep: ~1 s at 2048 -- as the
-// whole-matrix fallback of the POD's Gram route; SE_MAX stays the limit of the public entries and of the modes per request)
-constexpr int SE_GRID_MAX = 2048;
+// ---- small dense problems (rom_small_dense.hip): SE_* modes and limits, romb_small_eig, romb_pivchol_whiten ---------
+#include "rom_small_dense_host.h"
+
+// ---- orthonormalisation helpers of rom_basis.hip, shared with rom_pod.hip -------------------------------------------
 __global__ void kb_rows_axpy(double* __restrict__ out, const double* __restrict__ x, const double* __restrict__ y,
                              const double* __restrict__ f, double s, long long dim);
 int romb_fill_random(rom_ctx* ctx, double* p, size_t n, unsigned long long seed, bool gaussian);
-// tight (with gram_like): rotate down to |a_pq| <= 16 eps sqrt(a_pp a_qq) instead of n eps
-int romb_small_eig(rom_ctx* ctx, int n, const double* A, int lda, double* lam, double* T, int ldt, int mode, double rel_tol,
-                   bool gram_like = true, bool tight = false);
-int romb_pivchol_whiten(rom_ctx* ctx, int n, const double* A, int lda, double* lam, double* T, int ldt, double rel_tol);
 int romb_gram_transform(rom_ctx* ctx, double* X, double* Y, int b, int64_t dim, int mode, double rel_tol, int rounds);
 int romb_orthonormalize_against(rom_ctx* ctx, double* V, int found, int take, int64_t dim);

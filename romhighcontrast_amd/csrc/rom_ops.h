@@ -1,5 +1,5 @@
-// Internal launchers of rom_ops.hip shared with rom_basis.hip: raw device pointers, work only ENQUEUED on the context's
-// compute stream (no host synchronisation), results left on the device.
+// Internal launchers of rom_ops.hip shared with rom_basis.hip and rom_small_dense.hip: raw device pointers, work only
+// ENQUEUED on the context's compute stream (no host synchronisation), results left on the device.
 #pragma once
 #include "romhc_internal.h"
 

@@ -1,8 +1,27 @@
-// Small dense device routines shared by the basis-stage kernels (rom_basis.hip, rom_pod.hip): the Jacobi eigensolver of
+// Small dense device routines shared by the kernels of rom_small_dense.hip and rom_pod.hip: the Jacobi eigensolver of
 // matrices of order <= 32 as a __device__ function on an LDS-resident matrix, so that a kernel that has just produced a
-// small Gram matrix (the one-workgroup Rayleigh-Ritz loop of rom_pod.hip) diagonalises it in the same launch.
+// small Gram matrix (the one-workgroup Rayleigh-Ritz loop of rom_pod.hip) diagonalises it in the same launch.  The rules
+// that every Jacobi implementation shares (thresholds, pairs, block update, ranking) are in rom_small_dense_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "rom_small_dense_host.h"
+
+// max of v over a workgroup of NW waves, the same bits in every thread; red: NW doubles of LDS (the barrier in front lets a
+// kernel reduce through the same red again and again)
+template <int NW>
+__device__ inline double block_max(double v, double* red) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+  __syncthreads();
+  if ((t & 63) == 0) red[t >> 6] = v;
+  __syncthreads();
+  double m = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) m = fmax(m, red[w]);
+  return m;
+}
 
 // 1 / sqrt(x) to full precision from the hardware estimate (two Newton steps): the cosine of a rotation must satisfy
 // c^2 (1 + t^2) = 1 to rounding, or the accumulated eigenvector rows drift from orthonormality
@@ -78,11 +97,10 @@ __device__ inline bool jacobi32_run(int n, Jacobi32Lds& L, int gram_like, double
       L.Vt[r * LD + c] = r == c ? 1.0 : 0.0;
     }
   }
-  if (t < 32) L.nu2[0][t] = t < n ? (gram_like ? fabs(L.As[t * LD + t]) : dmax) : 0.0;
+  if (t < 32) L.nu2[0][t] = t < n ? jacobi_nu2_init(gram_like, L.As[t * LD + t], dmax) : 0.0;
   const bool on = t < half * half;
   const int bk = on ? t / half : 0, bl = on ? t - bk * half : 0;
-  const double tol = (gram_like == 2 ? 16.0 : double(n > 8 ? n : 8)) * 1.1e-16;   // (gram_like == 2: romb_small_eig's `tight`)
-  const double tol2 = tol * tol, floor_abs = fmax(1e-300, 1e-40 * dmax);
+  const double tol2 = jacobi_tol2(n, gram_like), floor_abs = jacobi_floor(dmax);
   __syncthreads();
   int cur = 0;
   bool ever = false;
@@ -94,22 +112,8 @@ __device__ inline bool jacobi32_run(int n, Jacobi32Lds& L, int gram_like, double
       double* An = cur ? L.As : L.A1;
       double* Vn = cur ? L.Vt : L.V1;
       if (on) {
-        // the pairs of this round (round robin: index ne - 1 stays, the others move around it)
-        int pk = r, qk = nm1, pl = r, ql = nm1;
-        if (bk) {
-          pk = r + bk;
-          if (pk >= nm1) pk -= nm1;
-          qk = r - bk;
-          if (qk < 0) qk += nm1;
-          if (pk > qk) { const int x = pk; pk = qk; qk = x; }
-        }
-        if (bl) {
-          pl = r + bl;
-          if (pl >= nm1) pl -= nm1;
-          ql = r - bl;
-          if (ql < 0) ql += nm1;
-          if (pl > ql) { const int x = pl; pl = ql; ql = x; }
-        }
+        const auto [pk, qk] = jacobi_pair(bk, r, nm1);   // the pairs of this round
+        const auto [pl, ql] = jacobi_pair(bl, r, nm1);
         const double kpp = A[pk * LD + pk], kqq = A[qk * LD + qk], kpq = A[pk * LD + qk];
         const double lpp = A[pl * LD + pl], lqq = A[ql * LD + ql], lpq = A[pl * LD + ql];
         const double nkp = L.nu2[cur][pk], nkq = L.nu2[cur][qk], nlp = L.nu2[cur][pl], nlq = L.nu2[cur][ql];
@@ -120,13 +124,7 @@ __device__ inline bool jacobi32_run(int n, Jacobi32Lds& L, int gram_like, double
         const bool rk = jacobi_rotation(kpp, kqq, kpq, nkp, nkq, tol2, floor_abs, ck, sk, nkpo, nkqo);
         (void)jacobi_rotation(lpp, lqq, lpq, nlp, nlq, tol2, floor_abs, cl, sl, nlpo, nlqo);
         rotated = rotated || rk;
-        // A <- J^T A J on the block: R_k B R_l^T
-        const double r00 = ck * b00 - sk * b10, r01 = ck * b01 - sk * b11;
-        const double r10 = sk * b00 + ck * b10, r11 = sk * b01 + ck * b11;
-        An[pk * LD + pl] = cl * r00 - sl * r01;
-        An[pk * LD + ql] = sl * r00 + cl * r01;
-        An[qk * LD + pl] = cl * r10 - sl * r11;
-        An[qk * LD + ql] = sl * r10 + cl * r11;
+        jacobi_block_update(ck, sk, cl, sl, b00, b01, b10, b11, An[pk * LD + pl], An[pk * LD + ql], An[qk * LD + pl], An[qk * LD + ql]);
         // eigenvector rows: Vt <- J^T Vt
         Vn[pk * LD + j0] = ck * vp0 - sk * vq0;
         Vn[pk * LD + j0 + 1] = ck * vp1 - sk * vq1;
@@ -160,12 +158,7 @@ __device__ inline bool jacobi32_run(int n, Jacobi32Lds& L, int gram_like, double
   }
   if (t < n) L.ev[t] = L.As[t * LD + t];
   __syncthreads();
-  if (t < n) {
-    int rank = 0;
-    const double v = L.ev[t];
-    for (int j = 0; j < n; ++j) rank += (L.ev[j] > v || (L.ev[j] == v && j < t)) ? 1 : 0;
-    L.perm[rank] = t;
-  }
+  if (t < n) L.perm[rank_descending(L.ev, n, t)] = t;
   __syncthreads();
   return ever;
 }

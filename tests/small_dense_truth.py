@@ -1,4 +1,4 @@
-"""Truth for the small dense layer of the basis stage (csrc/rom_basis.hip, csrc/rom_small_dense.h): the eigen-solvers and
+"""Truth for the small dense layer of the basis stage (csrc/rom_small_dense.hip, csrc/rom_small_dense.h): the eigen-solvers and
 whitenings behind ctx.small_eig / ctx.symmetric_orthonormalize, on every device route.  TEST INFRASTRUCTURE: imports no
 product code; tests/test_small_dense_host.py proves it on the CPU, tests/test_gpu_small_dense.py uses it on the device.
 

@@ -626,7 +626,7 @@ def test_pod_fuzz_vs_lapack(api):
     """rom_pod against numpy.linalg.svd on random shapes (2 ... 400 rows, 2 ... 5000 columns), requests (a few modes ... all of
     them), centring and spectra: geometric decay at a random rate, a plateau and a cliff of nine orders, independent random rows
     (a flat spectrum: the Gram route, whose subspace iteration stalls there -- the whole Gram matrix is then diagonalised by
-    the grid-wide Jacobi, rom_basis.hip jacobi_grid), exact low rank.  Every singular value within 1e-7 relative + 50 eps ||X||_2
+    the grid-wide Jacobi, rom_small_dense.hip jacobi_grid), exact low rank.  Every singular value within 1e-7 relative + 50 eps ||X||_2
     (what the stored numbers determine) of LAPACK's; a mode the POD completes with sigma = 0 must be below its floor there."""
     SM, RB = api
     from romhighcontrast_amd import _ffi
