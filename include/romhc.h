@@ -614,6 +614,40 @@ int rom_lm_polish(rom_ctx* ctx, int n, int k, int r, rom_buf* Ahat, rom_buf* bha
                   int K, int t, rom_buf* THETA0, const double* lo_host, const double* hi_host, rom_buf* AUX, int max_iter,
                   double misfit_tol, rom_buf* OUT, size_t out_off, int64_t ldo, double* info8_host);
 
+/* ---- posterior sampling of the parameters (romhighcontrast_amd/inverse.py::mcmc_host) ------------------------------------------
+ * Which parameters are compatible with noisy data: adaptive random-walk Metropolis in theta = log a on the box [lo, hi]^k with a
+ * uniform prior, for the potential Phi(theta) = ||p - G_r c(theta)||^2 in the reduced sensor coordinates of rom_lm_polish (Ahat,
+ * bhat, Gr, P as there) and the log-posterior -invvar Phi / 2 inside the box; INVVAR (K) = 1 / sigma^2 per query, LPROP (K, k, k)
+ * row-major lower triangular: the query's proposal factor L.  One CHAIN is a pair (query, chain index), K t of them, one workgroup
+ * each with the loop over the steps inside the launch; the algorithm is mcmc_host's, step for step.  Step i (the global index,
+ * step0 <= i < step0 + steps): k standard normals xi and a uniform u from Philox4x32-10 with the key (seed low word, seed high
+ * word) and the counter (i, chain id low, chain id high, purpose), chain id = chain0 + the chain's index in the call -- purpose
+ * j < ceil(k / 2): the Box-Muller pair (2 j, 2 j + 1) from the uniforms ((w0 >> 6) 2^26 + (w1 >> 6) + 0.5) 2^-52 and the same of
+ * w2, w3; purpose 0xFFFFFFFF: u from w0, w1.  Proposal theta' = theta + e^ls L xi, a pinned coordinate (lo_q == hi_q) stays bit
+ * for bit.  Outside the box: rejected without an evaluation, alpha = 0.  Inside: a non-positive pivot of A(theta') rejects with
+ * alpha = 0; otherwise l = -invvar (Phi' - Phi) / 2, accepted iff log u < l, alpha = min(1, e^min(l, 0)).  i < burn:
+ * ls += (i + 1)^-0.6 (alpha - 0.234), frozen afterwards.  i >= burn: the state enters the Welford mean and M2 (k x k) of theta,
+ * the running mean of c, the smallest Phi with its theta; with SAMPLES and (i - burn) % thin == thin - 1 theta goes to slot
+ * (i - burn) / thin of the chain (SAMPLES is [chain][slot][k] from smp_off; slots beyond `slots` are not written; NULL: none).
+ * STATE row of a chain (lds apart, from s_off; rom_mcmc_layout): theta (k) | Phi | ls | mean (k) | M2 (k k) | mean of c (n) | kept |
+ * accepted (both of the steps i >= burn) | outside | not_spd (of all steps) | Phi_min | theta_min (k).  With step0 == 0 only theta
+ * is read, the start, and clipped to the box; otherwise the chain resumes from its row.  At most 1024 steps run per launch; a call
+ * split at any step, here or by the caller through step0, returns the bits of the unsplit call.
+ * 1 <= n <= 64, 1 <= k <= 16, 1 <= r <= 64, 1 <= t <= 8, K t <= 2^30, steps >= 0, burn >= 0, thin >= 1, step0 + steps <= 2^31:
+ * ROM_ERR_INVALID outside; K = 0 is a no-op; steps = 0 leaves the clipped start and its Phi.  A start whose A(theta) is not positive
+ * definite: ROM_ERR_NOT_SPD, its row NaN.  A query whose Phi at the start is NaN has a NaN row and no error.  No input buffer is
+ * modified; no floating-point atomics: the same bits on a repeated call.  One host synchronisation.
+ * seed: its 64 bits are the key (an unsigned seed above 2^63 is passed as the signed number of the same bits).
+ * info8_host (8 doubles or NULL): kernel launches, host synchronisations, bytes of workspace, chains K t, steps taken, evaluations
+ * of the model (both summed on the device in integers), 0, 0. */
+/* out8: the row length, then the offsets of Phi, ls, mean, M2, the mean of c, kept (accepted, outside, not_spd follow it) and
+ * Phi_min (theta_min follows it) */
+int rom_mcmc_layout(int n, int k, int64_t* out8);
+int rom_mcmc(rom_ctx* ctx, int n, int k, int r, rom_buf* Ahat, rom_buf* bhat, rom_buf* Gr, rom_buf* P, size_t p_off, int64_t ldp, int K,
+             int t, rom_buf* INVVAR, rom_buf* LPROP, const double* lo_host, const double* hi_host, int64_t seed, int64_t chain0,
+             int64_t step0, int steps, int burn, int thin, rom_buf* STATE, size_t s_off, int64_t lds, rom_buf* SAMPLES, size_t smp_off,
+             int64_t slots, double* info8_host);
+
 /* ---- sensor state estimation on the polynomial manifold (src/experiments/NonLinearROM.py:54-70, src/lib/ReducedBasis.py:65-70) ----
  * The decoder of a fitted rom_poly map, u(z) = mean + z V_known + g(z) V_unknown (the model of src/experiments/NonLinearROM.py:54-70),
  * fitted to point measurements instead of being given its known coordinates: the nonlinear counterpart of the linear state

@@ -147,6 +147,10 @@ PROTOTYPES = {
     "rom_kmeans_destroy": (C.c_int, [_vp]),
     "rom_lm_polish": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp,
                                 _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
+    "rom_mcmc_layout": (C.c_int, [C.c_int, C.c_int, _vp]),
+    "rom_mcmc": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                           C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t,
+                           C.c_int64, _vp]),
     "rom_poly_sense": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                  C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_mlp_sense": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp,
@@ -431,6 +435,37 @@ class Context:
         d = dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), systems=int(info[3]),
                  iterations=int(info[4]), factorisations=int(info[5]))
         return res, d
+
+    def mcmc_layout(self, n, k) -> dict:
+        """rom_mcmc_layout: the state row of a chain, offsets by name and ``row``, its length (inverse.mcmc_layout)."""
+        v = np.zeros(8, dtype=np.int64)
+        check(self.lib.rom_mcmc_layout(int(n), int(k), v.ctypes.data))
+        row, phi, ls, mean, M2, mean_c, kept, phi_min = (int(x) for x in v)
+        return dict(theta=0, phi=phi, ls=ls, mean=mean, M2=M2, mean_c=mean_c, kept=kept, accepted=kept + 1, outside=kept + 2,
+                    not_spd=kept + 3, phi_min=phi_min, theta_min=phi_min + 1, row=row)
+
+    def mcmc(self, n, k, r, Ahat: "Buffer", bhat: "Buffer", Gr: "Buffer", P: "Buffer", p_off, ldp, K, t, INVVAR: "Buffer",
+             LPROP: "Buffer", lo, hi, seed, steps, burn, thin, STATE: "Buffer", s_off=0, lds=None, SAMPLES: "Buffer | None" = None,
+             smp_off=0, slots=0, chain0=0, step0=0) -> dict:
+        """rom_mcmc: inverse.mcmc_host on the device in reduced sensor coordinates (P: K rows of r columns, INVVAR (K,) = 1 /
+        sigma^2, LPROP (K, k, k) the proposal factors), t chains per query with the ids chain0 + position, the steps step0 ..
+        step0 + steps - 1.  STATE (rows of lds >= the row of ``mcmc_layout`` from s_off) holds the starts in its first k columns
+        (step0 = 0) or the rows to resume from and receives the rows; SAMPLES ([chain][slot][k] from smp_off) or None.  Returns
+        the info dict."""
+        k = int(k)
+        lds = self.mcmc_layout(n, k)["row"] if lds is None else int(lds)
+        lo = _host(np.broadcast_to(np.asarray(lo, dtype=np.float64), (k,)))
+        hi = _host(np.broadcast_to(np.asarray(hi, dtype=np.float64), (k,)))
+        info = np.zeros(8)
+        h = lambda b: b.h if b is not None else None  # noqa: E731
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        seed -= (seed >> 63) << 64   # (the same 64 bits as a signed number)
+        check(self.lib.rom_mcmc(self.h, int(n), k, int(r), Ahat.h, bhat.h, Gr.h, h(P), int(p_off), int(ldp), int(K), int(t), h(INVVAR),
+                                h(LPROP), lo.ctypes.data, hi.ctypes.data, seed, int(chain0), int(step0),
+                                int(steps), int(burn), int(thin), h(STATE), int(s_off), lds, h(SAMPLES), int(smp_off), int(slots),
+                                info.ctypes.data))
+        return dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), chains=int(info[3]),
+                    steps=int(info[4]), evaluations=int(info[5]))
 
     def poly_sense(self, m, d, r, Gr: "Buffer", P: "Buffer", p_off, ldp, K, t, T0: "Buffer", lo, hi, AUX: "Buffer | None" = None,
                    max_iter=30, misfit_tol=1e-3, OUT: "Buffer | None" = None, out_off=0, ldo=None):

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "rom_lm_drive.h"
+#include "rom_lm_eval.h"
 
 namespace {
 
@@ -83,41 +84,8 @@ struct LmSys {
   // py:51-58 without the Jacobian: c(theta) -> cn, rho = p - G_r c -> rhon, |rho|^2 -> scal[LMS_FN]; theta from sm[thx ..).
   // Returns whether every pivot of A(theta) was positive (otherwise cn, rhon and fn mean nothing).
   __device__ bool eval(int thx) {
-    const int tid = threadIdx.x, lane = tid & 63, n = a.n, k = a.k, r = a.r, l16 = tid & 15;
-    double* As = sm + m.As;
-    if (tid < k) sm[m.ea + tid] = exp(sm[thx + tid]);   // py:53
-    __syncthreads();
-    for (int idx = tid; idx < n * n; idx += LM_THREADS) {   // py:54
-      const int row = idx / n, col = idx - row * n;
-      double s = 0.0;
-      for (int q = 0; q < k; ++q) s = fma(sm[m.ea + q], a.Ahat[size_t(q) * n * n + idx], s);
-      As[row * m.ldn + col] = s;
-    }
-    __syncthreads();
-    const bool ok = lm_factor(As, m.ldn, n, sm + m.invd, sm + m.scal + LMS_OKA);
     factorisations += 1;
-    if (tid < 64) {   // py:55
-      double b[1] = {lane < n ? a.bhat[lane] : 0.0};
-      lm_solve<1>(As, m.ldn, n, sm + m.invd, b, lane);
-      if (lane < n) sm[m.cn + lane] = b[0];
-    }
-    __syncthreads();
-    for (int i0 = 0; i0 < r; i0 += 16) {   // py:56: 16 lanes per row of G_r
-      const int i = i0 + (tid >> 4);
-      double s = 0.0;
-      if (i < r)
-        for (int j = l16; j < n; j += 16) s = fma(a.Gr[size_t(i) * n + j], sm[m.cn + j], s);
-      s = group16_sum(s);
-      if (i < r && l16 == 0) sm[m.rhon + i] = sm[m.ps + i] - s;
-    }
-    __syncthreads();
-    if (tid < 64) {
-      const double v = lane < r ? sm[m.rhon + lane] : 0.0;
-      const double f = wave_sum(v * v);
-      if (lane == 0) sm[m.scal + LMS_FN] = f;
-    }
-    __syncthreads();
-    return ok;
+    return lm_eval(sm, m, a.n, a.k, a.r, a.Ahat, a.bhat, a.Gr, thx);   // (rom_lm_eval.h, shared with k_mcmc)
   }
 
   // py:59-61 and py:97-98 at the current theta (th), its c (cs), its rho and ITS FACTOR in As: X = A^-1 [e^theta_q Ahat_q c]_q,

@@ -28,7 +28,7 @@
 namespace {
 
 constexpr int LM_TRIALS = 8;   // py:101
-enum { LMS_FN = 0, LMS_MOVED = 1, LMS_MAXNEW = 2, LMS_OKH = 3, LMS_OKA = 4 };   // the slots of `scal` (5 .. 7: the system's own)
+// (the slots LMS_* of `scal`: rom_lm_small.h)
 
 // py:84: perp2 and the scale of a query from aux, or 0 and max |p| of its row ps; the scale is at least the smallest normal
 __device__ __forceinline__ double lm_scale(const double* aux, long long query, const double* ps, int r, double& perp2) {

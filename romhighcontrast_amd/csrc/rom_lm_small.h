@@ -9,6 +9,7 @@ namespace {
 
 constexpr int LMS_THREADS = 256;   // the workgroup the routines below assume
 constexpr int LMS_SWEEPS = 30;     // bound of the Jacobi sweeps (<= 16 columns converge in under 10)
+enum { LMS_FN = 0, LMS_MOVED = 1, LMS_MAXNEW = 2, LMS_OKH = 3, LMS_OKA = 4 };   // the slots of `scal` (5 .. 7: the system's own)
 
 __device__ __forceinline__ double wave_sum(double v) {   // (the butterfly leaves the same bits in every lane)
 #pragma unroll

@@ -305,6 +305,55 @@ class ParameterLibrary:
         return ParameterEstimate(a.reshape((K,) + tuple(sm.blocks_geometry)), res.misfit, idx, start_misfit, res.converged,
                                  res.iterations, res.sigma_min, res.coefficients, bound, S)
 
+    def posterior(self, measurements, sigma, t=4, steps=2000, burn=500, thin=0, seed=0, states=False, device=True) -> "ParameterPosterior":
+        """Which parameters are compatible with the K measurement vectors (K, m) under independent noise of standard deviation
+        ``sigma`` (a scalar or (K,), in the units of the weighted measurements): t chains per vector of adaptive random-walk
+        Metropolis in log a inside the library's box (``rom_mcmc``; ``mcmc_host`` is its specification and what ``device=False``
+        runs).  The chains start at the t library rows of the search, which are dispersed and so suit R-hat; the proposal factors
+        are ``proposal_factors`` at the device-polished estimate.  ``thin`` = 0 keeps no samples, else every thin-th state past
+        burn-in; ``states``: the posterior-mean states.  Returns a ``ParameterPosterior``; its a_map is (K, k)."""
+        sm, ctx = self.sm, self.sm._ctx
+        Y = np.atleast_2d(np.asarray(measurements, dtype=np.float64))
+        K, k, n = len(Y), self.a.shape[1], self.n
+        if self.points is None:
+            raise RuntimeError("ParameterLibrary.observe(points) comes first")
+        t = min(int(t), self.M)
+        _check_mcmc_limits(n, k, self.r, t)
+        steps, burn, thin = int(steps), int(burn), int(thin)
+        if thin < 0:
+            raise ValueError(f"thin = {thin}: 0 (no samples) or the stride of the kept samples")
+        idx, _, _, Pq_dev, Yw, perp2 = self._search(Y, t, 0)
+        la = np.log(self.a)
+        lo, hi = la.min(axis=0), la.max(axis=0)
+        res, _ = self._estimate_device(Y, idx, Pq_dev, Yw, perp2, la, False, 30, 1e-3)
+        invvar = 1.0 / np.broadcast_to(np.asarray(sigma, dtype=np.float64), (K,)) ** 2
+        Gr = self.Gr.download(self.r * n).reshape(self.r, n)
+        L = proposal_factors(self.Ahat, self.bhat, Gr, res.theta, invvar, lo, hi) if K else np.zeros((0, k, k))
+        slots = max(0, steps - burn) // thin if thin else 0
+        o = mcmc_layout(n, k)
+        if not device:
+            run = mcmc_host(self.Ahat, self.bhat, Gr, Yw @ self.U, invvar, la[idx], L, lo, hi, seed, steps, burn, max(thin, 1), slots=slots)
+            rows, samples = run.state, run.samples
+        else:
+            rows = np.zeros((K * t, o["row"]))
+            rows[:, :k] = la[idx].reshape(K * t, k)
+            samples = None
+            if K:
+                STATE = ctx.upload(rows)
+                SAMPLES = ctx.upload(np.full(K * t * slots * k, np.nan)) if slots else None
+                ctx.mcmc(n, k, self.r, self._lm_model[0], self._lm_model[1], self.Gr, Pq_dev, 0, self.r, K, t, ctx.upload(invvar),
+                         ctx.upload(L), lo, hi, seed, steps, burn, max(thin, 1), STATE, SAMPLES=SAMPLES, slots=slots)
+                rows = STATE.download().reshape(K * t, o["row"])
+                samples = SAMPLES.download().reshape(K * t, slots, k) if slots else None
+        post = posterior_summary(rows, n, k, t, samples=samples if slots else None, perp2=perp2)
+        if states:
+            dim = sm.vspace_dim
+            out = ctx.alloc(max(K * dim, 1))
+            if K:
+                ctx.gemm_nn(K, dim, n, ctx.upload(np.ascontiguousarray(post.mean_coefficients)), 0, n, self._W, 0, dim, out, 0, dim)
+            post = post._replace(states=DeviceArray(out, K, dim))
+        return post
+
 
 # ---- box-constrained least squares (Stark-Parker BVLS): the noise-robust linear state estimate ----------------------------------
 class BvlsResult(NamedTuple):
@@ -472,3 +521,355 @@ def bounded_lstsq(ctx, E, Y, lo, hi, weights=None, device=True) -> BvlsResult:
     _check_bvls_limits(n, r)
     res, _ = ctx.bvls(n, r, ctx.upload(Gr), ctx.upload(Pq) if K else None, 0, r, K, lo, hi, AUX=ctx.upload(aux) if K else None)
     return res
+
+
+# ---- posterior sampling of the parameters: which log a are compatible with noisy data ---------------------------------------------
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_U32, _S32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+MCMC_ACCEPT = 0xFFFFFFFF          # the purpose word of the acceptance uniform
+MCMC_TARGET = 0.234               # the acceptance rate the scale adapts to
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10: counter (..., 4) and key (..., 2) of 32-bit words (broadcast against each other) -> (..., 4) uint32.
+    ``csrc/rom_philox.h`` is the same function for the host and the device."""
+    counter, key = np.asarray(counter, dtype=np.uint64), np.asarray(key, dtype=np.uint64)
+    c0, c1, c2, c3 = (counter[..., i] for i in range(4))
+    k0, k1 = key[..., 0], key[..., 1]
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ k0, p1 & _U32, (p0 >> _S32) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+def mcmc_uniform(hi, lo):
+    """u = ((hi >> 6) 2^26 + (lo >> 6) + 0.5) 2^-52 from two 32-bit words: 52 random bits and a half, exact in float64, never 0
+    and never 1 (with 53 bits the half would not fit the significand and all-ones words would round to 1)."""
+    hi, lo = np.asarray(hi, dtype=np.uint64), np.asarray(lo, dtype=np.uint64)
+    bits = ((hi >> np.uint64(6)) << np.uint64(26)) | (lo >> np.uint64(6))
+    return (bits.astype(np.float64) + 0.5) * 2.0 ** -52
+
+
+def mcmc_draws(seed, chain, step, k, dtype=np.float64):
+    """The draws of step ``step`` of the chains with the ids ``chain`` (B,): (xi (B, k) standard normals, u (B,) uniform).  Key
+    (seed low word, seed high word), counter (step, chain low, chain high, purpose): purpose j < ceil(k / 2) gives the Box-Muller
+    pair (2 j, 2 j + 1) -- words 0, 1 -> u1, words 2, 3 -> u2, z0 = sqrt(-2 log u1) cos(2 pi u2), z1 = .. sin(2 pi u2) -- and purpose
+    0xFFFFFFFF the uniform (words 0, 1).  The uniforms are exact; ``dtype`` is that of the logarithm and the circular functions."""
+    chain = np.atleast_1d(np.asarray(chain, dtype=np.uint64))
+    B, kh, T = len(chain), (int(k) + 1) // 2, dtype
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
+    step = np.broadcast_to(np.asarray(step, dtype=np.uint64) & _U32, (B,))
+    purpose = np.concatenate([np.arange(kh, dtype=np.uint64), np.array([MCMC_ACCEPT], dtype=np.uint64)])
+    ctr = np.empty((B, kh + 1, 4), dtype=np.uint64)
+    ctr[..., 0], ctr[..., 1], ctr[..., 2], ctr[..., 3] = step[:, None], (chain & _U32)[:, None], (chain >> _S32)[:, None], purpose[None, :]
+    w = philox4x32(ctr, key)
+    u1, u2 = mcmc_uniform(w[:, :kh, 0], w[:, :kh, 1]).astype(T), mcmc_uniform(w[:, :kh, 2], w[:, :kh, 3]).astype(T)
+    rad, ang = np.sqrt(T(-2.0) * np.log(u1)), T(6.283185307179586) * u2
+    xi = np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=-1).reshape(B, 2 * kh)[:, :int(k)]
+    return xi, mcmc_uniform(w[:, kh, 0], w[:, kh, 1])
+
+
+def mcmc_layout(n, k):
+    """The state row of a chain (``rom_mcmc_layout``): offsets by name and ``row``, its length:
+    theta (k) | phi | ls | mean (k) | M2 (k k) | mean_c (n) | kept | accepted | outside | not_spd | phi_min | theta_min (k)."""
+    o = dict(theta=0, phi=k, ls=k + 1, mean=k + 2, M2=2 * k + 2, mean_c=2 * k + 2 + k * k)
+    o["kept"] = o["mean_c"] + n
+    o.update(accepted=o["kept"] + 1, outside=o["kept"] + 2, not_spd=o["kept"] + 3, phi_min=o["kept"] + 4, theta_min=o["kept"] + 5)
+    o["row"] = o["theta_min"] + k
+    return o
+
+
+class McmcRun(NamedTuple):
+    """``mcmc_host`` / ``mcmc_device``: state (B, row) the chains' rows (``mcmc_layout``), B = K t, chain = query t + index;
+    samples (B, slots, k) with NaN in the slots this call did not write, or None; margin (B,): the smallest |log u - l| over the
+    chain's evaluated steps of this call (inf without one) and margin_step (B,) the global step it occurred at (-1) -- host only,
+    None from the device; info: the device call's dictionary, or None."""
+    state: np.ndarray
+    samples: Optional[np.ndarray]
+    margin: Optional[np.ndarray]
+    margin_step: Optional[np.ndarray]
+    info: Optional[dict]
+
+
+def _mcmc_eval(Ahat, bhat, Gr, p, theta):
+    """c(theta) (B, n), Phi = |p - G_r c|^2 (B,) and whether every pivot of A(theta) is positive (B,), in the dtype of theta:
+    A = sum_q e^theta_q Ahat_q factored as L D L^T without pivoting (the elimination of ``lm_factor``, csrc/rom_lm_small.h)."""
+    A = np.einsum("bq,qij->bij", np.exp(theta), Ahat)
+    n = A.shape[1]
+    with np.errstate(all="ignore"):
+        for j in range(n - 1):
+            l = A[:, j + 1:, j] / A[:, j, j, None]
+            A[:, j + 1:, j + 1:] -= A[:, j + 1:, j, None] * l[:, None, :]
+        d = np.einsum("bjj->bj", A)
+        invd = 1.0 / d
+        c = np.array(np.broadcast_to(bhat, (len(theta), n)))
+        for j in range(n - 1):
+            c[:, j + 1:] -= (A[:, j + 1:, j] * invd[:, j, None]) * c[:, j, None]
+        c *= invd
+        for j in range(n - 1, 0, -1):
+            c[:, :j] -= (A[:, j, :j] * invd[:, :j]) * c[:, j, None]
+        rho = p - c @ Gr.T
+    return c, np.einsum("br,br->b", rho, rho), (d > 0).all(axis=1)
+
+
+def _mcmc_box(lo, hi, k):
+    lo = np.array(np.broadcast_to(np.asarray(lo, dtype=np.float64), (k,)))
+    hi = np.array(np.broadcast_to(np.asarray(hi, dtype=np.float64), (k,)))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all()):
+        raise ValueError("mcmc: the box needs finite lo <= hi")
+    return lo, hi
+
+
+def mcmc_host(Ahat, bhat, Gr, P, invvar, theta0, L, lo, hi, seed, steps, burn, thin, chain0=0, step0=0, state=None, slots=None,
+              dtype=np.float64) -> McmcRun:
+    """Adaptive random-walk Metropolis for the posterior of theta = log a given noisy data: THE SPECIFICATION of ``rom_mcmc``
+    (csrc/rom_mcmc.hip), pure NumPy, vectorised over the chains.
+
+    The model: theta in the box [lo, hi]^k with a uniform prior; in the reduced sensor coordinates of ``polish_parameters_device``
+    (p = U^T (w y), G_r) the potential is Phi(theta) = ||p - G_r c(theta)||^2 and the log-posterior inside the box
+    -invvar Phi / 2, invvar = 1 / sigma^2 per query.  Ahat (k, n, n), bhat (n,), Gr (r, n), P (K, r), invvar (K,), theta0 (K, k) or
+    (K, t, k) the starts (clipped to the box), L (K, k, k) the queries' lower-triangular proposal factors (the strict upper
+    triangle is not read).  One chain is a pair (query, index), B = K t of them, with the id chain0 + its position.  Step i, the
+    GLOBAL index step0 <= i < step0 + steps:
+
+    1. k standard normals xi and a uniform u: ``mcmc_draws(seed, id, i, k)``.
+    2. theta' = theta + e^ls (L xi); a pinned coordinate (lo_q == hi_q) keeps theta_q bit for bit.
+    3. A coordinate of theta' outside [lo, hi]: rejected without an evaluation, alpha = 0, ``outside`` goes up.
+    4. Else Phi(theta'): a pivot of A(theta') that is not positive rejects with alpha = 0 and ``not_spd`` goes up; otherwise
+       l = -invvar (Phi' - Phi) / 2, accepted iff log u < l, alpha = min(1, e^min(l, 0)) (a NaN l rejects with alpha = 0).
+    5. i < burn: ls += (i + 1)^-0.6 (alpha - 0.234) (Robbins-Monro; frozen afterwards, so the chain past burn-in is a Metropolis
+       chain).
+    6. i >= burn: the current state (again after a rejection) enters ``kept``, the Welford mean and M2 (k, k) of theta
+       (M2 += (theta - old mean)(theta - new mean)^T), the running mean of c, ``accepted``, and the smallest Phi with its theta
+       (both start at the start's); if (i - burn) % thin == thin - 1 and its slot (i - burn) / thin < slots, theta is a sample.
+
+    ``state`` (B, row) with step0 > 0 resumes the chains from their rows (``mcmc_layout``); the model is evaluated at the row's
+    theta once more, so a split run returns the bits of the unsplit one.  ``slots`` None: every slot of the steps up to
+    step0 + steps; 0: no samples.  A start whose A(theta) is not positive definite raises LinAlgError; a query whose Phi at the
+    start is NaN gets a NaN row.  ``dtype=np.longdouble`` runs the same arithmetic in long double from the same Philox words.
+    Returns a ``McmcRun``; its margin tells up to which step another arithmetic can be held to this trajectory."""
+    T = dtype
+    Ahat, bhat, Gr = np.asarray(Ahat, dtype=T), np.asarray(bhat, dtype=T), np.asarray(Gr, dtype=T)
+    k, n, r = Ahat.shape[0], Ahat.shape[1], Gr.shape[0]
+    P = np.asarray(P, dtype=T).reshape(-1, r)
+    K = len(P)
+    steps, burn, thin, step0, chain0 = int(steps), int(burn), int(thin), int(step0), int(chain0)
+    if steps < 0 or burn < 0 or thin < 1 or step0 < 0 or chain0 < 0:
+        raise ValueError(f"mcmc: steps = {steps}, burn = {burn}, thin = {thin}, step0 = {step0}, chain0 = {chain0} (steps, burn, "
+                         "step0, chain0 >= 0, thin >= 1)")
+    lo, hi = _mcmc_box(lo, hi, k)
+    o = mcmc_layout(n, k)
+    if state is None:
+        if step0:
+            raise ValueError("mcmc: step0 > 0 resumes from `state`")
+        theta = np.asarray(theta0, dtype=T).reshape(K, -1, k)
+        t = theta.shape[1]
+        theta = np.clip(theta.reshape(K * t, k), lo.astype(T), hi.astype(T))
+    else:
+        state = np.array(state, dtype=T).reshape(-1, o["row"])
+        t = len(state) // max(K, 1)
+        theta = state[:, :k].copy()
+    B = K * t
+    if len(theta) != B:
+        raise ValueError(f"mcmc: {len(theta)} chains for K = {K} queries")
+    query = np.repeat(np.arange(K), t)
+    p, iv = P[query], np.asarray(invvar, dtype=T).reshape(K)[query]
+    Lc = np.tril(np.asarray(L, dtype=T).reshape(K, k, k))[query]
+    ids = (chain0 + np.arange(B)).astype(np.uint64)
+    pinned = lo == hi
+    loT, hiT = lo.astype(T), hi.astype(T)
+
+    c, phi, ok = _mcmc_eval(Ahat, bhat, Gr, p, theta)
+    dead = np.isnan(theta[:, 0]) if (state is not None and step0 > 0) else np.zeros(B, dtype=bool)
+    if (~ok & ~dead).any():
+        raise np.linalg.LinAlgError("mcmc: A(theta) not positive definite at a start")
+    dead |= np.isnan(phi)
+    if state is None or step0 == 0:
+        ls, mean, M2, meanc = np.zeros(B, dtype=T), np.zeros((B, k), dtype=T), np.zeros((B, k, k), dtype=T), np.zeros((B, n), dtype=T)
+        cnt = {name: np.zeros(B, dtype=np.int64) for name in ("kept", "accepted", "outside", "not_spd")}
+        phimin, thmin = phi.copy(), theta.copy()
+    else:
+        ls, mean, M2 = state[:, o["ls"]].copy(), state[:, o["mean"]:o["mean"] + k].copy(), state[:, o["M2"]:o["M2"] + k * k].reshape(B, k, k).copy()
+        meanc = state[:, o["mean_c"]:o["mean_c"] + n].copy()
+        cnt = {name: np.nan_to_num(state[:, o[name]]).astype(np.int64) for name in ("kept", "accepted", "outside", "not_spd")}
+        phimin, thmin = state[:, o["phi_min"]].copy(), state[:, o["theta_min"]:o["theta_min"] + k].copy()
+    total = max(0, step0 + steps - burn) // thin
+    slots = total if slots is None else int(slots)
+    samples = np.full((B, slots, k), np.nan, dtype=T) if slots > 0 else None
+    margin, margin_step = np.full(B, np.inf), np.full(B, -1, dtype=np.int64)
+    s = np.exp(ls)
+
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(step0, step0 + steps):
+            xi, u = mcmc_draws(seed, ids, i, k, dtype=T)                                         # 1
+            prop = np.where(pinned, theta, theta + s[:, None] * np.einsum("bqp,bp->bq", Lc, xi))  # 2
+            out = ~((prop >= loT) & (prop <= hiT)).all(axis=1)                                   # 3
+            cnt["outside"][out] += 1
+            alpha, accept = np.zeros(B, dtype=T), np.zeros(B, dtype=bool)
+            ins = np.flatnonzero(~out)
+            if ins.size:                                                                         # 4
+                cn, phin, okn = _mcmc_eval(Ahat, bhat, Gr, p[ins], prop[ins])
+                cnt["not_spd"][ins[~okn]] += 1
+                l = T(-0.5) * iv[ins] * (phin - phi[ins])
+                good = okn & ~np.isnan(l)
+                logu = np.log(u[ins].astype(T))
+                acc = good & (logu < l)
+                alpha[ins] = np.where(good, np.minimum(T(1.0), np.exp(np.minimum(l, T(0.0)))), T(0.0))
+                gap = np.where(good, np.abs(logu - l), np.inf).astype(np.float64)
+                closer = gap < margin[ins]
+                margin[ins[closer]], margin_step[ins[closer]] = gap[closer], i
+                ia = ins[acc]
+                theta[ia], c[ia], phi[ia] = prop[ins][acc], cn[acc], phin[acc]
+                accept[ia] = True
+            if i < burn:                                                                         # 5
+                ls = ls + T(i + 1) ** T(-0.6) * (alpha - T(MCMC_TARGET))
+                s = np.exp(ls)
+                continue
+            cnt["kept"] += 1                                                                     # 6
+            cnt["accepted"][accept] += 1
+            kept = cnt["kept"].astype(T)
+            d = theta - mean
+            mean = mean + d / kept[:, None]
+            M2 = M2 + d[:, :, None] * (theta - mean)[:, None, :]
+            meanc = meanc + (c - meanc) / kept[:, None]
+            lower = phi < phimin
+            phimin[lower], thmin[lower] = phi[lower], theta[lower]
+            j = i - burn
+            if samples is not None and j % thin == thin - 1 and j // thin < slots:
+                samples[:, j // thin] = theta
+
+    out_state = np.zeros((B, o["row"]), dtype=T)
+    out_state[:, :k], out_state[:, o["phi"]], out_state[:, o["ls"]] = theta, phi, ls
+    out_state[:, o["mean"]:o["mean"] + k], out_state[:, o["M2"]:o["M2"] + k * k] = mean, M2.reshape(B, k * k)
+    out_state[:, o["mean_c"]:o["mean_c"] + n] = meanc
+    for name in ("kept", "accepted", "outside", "not_spd"):
+        out_state[:, o[name]] = cnt[name]
+    out_state[:, o["phi_min"]], out_state[:, o["theta_min"]:o["theta_min"] + k] = phimin, thmin
+    out_state[dead] = np.nan
+    return McmcRun(out_state, samples, margin, margin_step, None)
+
+
+MCMC_LIMITS = dict(n=64, k=16, r=64, t=8)   # rom_mcmc (csrc/rom_mcmc.hip)
+
+
+def _check_mcmc_limits(n, k, r, t):
+    for name, v in (("n", n), ("k", k), ("r", r), ("t", t)):
+        if not 1 <= v <= MCMC_LIMITS[name]:
+            raise ValueError(f"the device sampler (rom_mcmc) needs 1 <= {name} <= {MCMC_LIMITS[name]}, got {name} = {v}: "
+                             "use device=False (mcmc_host)")
+
+
+def mcmc_device(ctx, Ahat, bhat, Gr, P, invvar, theta0, L, lo, hi, seed, steps, burn, thin, chain0=0, step0=0, state=None,
+                slots=None) -> McmcRun:
+    """``mcmc_host`` on the device of ``ctx`` (``rom_mcmc``, one workgroup per chain): the same arguments, in the reduced sensor
+    coordinates of ``reduce_sensors`` / ``reduce_measurements`` (Gr = S V^T, P = U^T (w y)), and the same rows.  margin and
+    margin_step are None."""
+    Ahat, bhat, Gr = np.asarray(Ahat, dtype=np.float64), np.asarray(bhat, dtype=np.float64), np.asarray(Gr, dtype=np.float64)
+    k, n, r = Ahat.shape[0], Ahat.shape[1], Gr.shape[0]
+    P = np.asarray(P, dtype=np.float64).reshape(-1, r)
+    K = len(P)
+    o = mcmc_layout(n, k)
+    lo, hi = _mcmc_box(lo, hi, k)
+    if state is None:
+        theta0 = np.asarray(theta0, dtype=np.float64).reshape(K, -1, k)
+        t = theta0.shape[1]
+        rows = np.zeros((K * t, o["row"]))
+        rows[:, :k] = theta0.reshape(K * t, k)
+    else:
+        rows = np.array(state, dtype=np.float64).reshape(-1, o["row"])
+        t = len(rows) // max(K, 1)
+    _check_mcmc_limits(n, k, r, t)
+    steps, burn, thin = int(steps), int(burn), int(thin)
+    total = max(0, int(step0) + steps - burn) // max(thin, 1)
+    slots = total if slots is None else int(slots)
+    if K == 0:
+        return McmcRun(rows, None, None, None, None)
+    STATE = ctx.upload(rows)
+    SAMPLES = ctx.upload(np.full(K * t * slots * k, np.nan)) if slots > 0 else None
+    info = ctx.mcmc(n, k, r, ctx.upload(Ahat), ctx.upload(bhat), ctx.upload(Gr), ctx.upload(P), 0, r, K, t,
+                    ctx.upload(np.asarray(invvar, dtype=np.float64).reshape(K)), ctx.upload(np.asarray(L, dtype=np.float64).reshape(K, k, k)),
+                    lo, hi, seed, steps, burn, thin, STATE, SAMPLES=SAMPLES, slots=slots, chain0=chain0, step0=step0)
+    samples = SAMPLES.download().reshape(K * t, slots, k) if slots > 0 else None
+    return McmcRun(STATE.download().reshape(K * t, o["row"]), samples, None, None, info)
+
+
+def proposal_factors(Ahat, bhat, Gr, theta, invvar, lo, hi):
+    """The default proposal factors L (K, k, k), lower triangular, at the points theta (K, k): with J_r = G_r dc/dtheta there,
+    H = invvar J_r^T J_r + diag(12 / (hi - lo)^2) -- the Gauss-Newton Hessian of the negative log-posterior plus the inverse
+    variance of the uniform prior, which caps the directions the data do not see -- and L = chol(H^-1) 2.38 / sqrt(k).  A pinned
+    coordinate (lo_q == hi_q) gets a zero row and column.  NumPy, batched over the queries."""
+    Ahat, bhat, Gr = np.asarray(Ahat, dtype=np.float64), np.asarray(bhat, dtype=np.float64), np.asarray(Gr, dtype=np.float64)
+    k = Ahat.shape[0]
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1, k)
+    K = len(theta)
+    lo, hi = _mcmc_box(lo, hi, k)
+    free = lo < hi
+    _, _, J = _rom_state(Ahat, bhat, Gr, np.zeros((K, Gr.shape[0])), theta)
+    H = np.asarray(invvar, dtype=np.float64).reshape(K, 1, 1) * np.einsum("bmq,bmp->bqp", J, J)
+    H = H + np.diag(12.0 / np.where(free, hi - lo, 1.0) ** 2)
+    both = free[:, None] & free[None, :]
+    H = np.where(both, H, 0.0) + np.diag((~free).astype(np.float64))
+    C = np.linalg.inv(H)
+    C = 0.5 * (C + C.transpose(0, 2, 1))
+    return np.where(both, np.linalg.cholesky(C), 0.0) * (2.38 / np.sqrt(k))
+
+
+class ParameterPosterior(NamedTuple):
+    """``ParameterLibrary.posterior`` / ``posterior_summary``, everything in theta = log a: mean (K, k), cov (K, k, k) and
+    sd (K, k) pooled over the t chains of a query by the law of total variance; rhat (K, k): Gelman-Rubin's potential scale
+    reduction from the chains' means and variances (NaN with one chain or a pinned coordinate); acceptance (K, t) of the steps
+    past burn-in and scale (K, t) = e^ls, the adapted proposal scales; a_map (K, k) = e^theta at the smallest misfit any chain
+    of the query saw, misfit_min (K,) = sqrt(Phi_min + perp2) there; mean_coefficients (K, n): the posterior mean of c;
+    outside, not_spd (K, t): proposals rejected for leaving the box / for a pivot that was not positive; samples (K, t, slots, k)
+    or None; states: DeviceArray (K, dim) of the posterior-mean states, or None."""
+    mean: np.ndarray
+    cov: np.ndarray
+    sd: np.ndarray
+    rhat: np.ndarray
+    acceptance: np.ndarray
+    scale: np.ndarray
+    a_map: np.ndarray
+    misfit_min: np.ndarray
+    mean_coefficients: np.ndarray
+    outside: np.ndarray
+    not_spd: np.ndarray
+    samples: Optional[np.ndarray]
+    states: Optional[DeviceArray]
+
+    def quantiles(self, q):
+        """The quantiles q (scalar or (Q,)) of theta per query over the kept samples of all its chains: (K, k) or (Q, K, k)."""
+        if self.samples is None:
+            raise ValueError("quantiles need kept samples: posterior(..., thin >= 1)")
+        K, t, slots, k = self.samples.shape
+        return np.quantile(self.samples.reshape(K, t * slots, k), q, axis=1)
+
+
+def posterior_summary(state, n, k, t, samples=None, perp2=None, states=None) -> ParameterPosterior:
+    """The ``ParameterPosterior`` of the state rows (K t, row) of ``mcmc_host`` / ``mcmc_device`` (t chains per query)."""
+    o = mcmc_layout(n, k)
+    S = np.asarray(state, dtype=np.float64).reshape(-1, t, o["row"])
+    K = len(S)
+    kept = S[:, :, o["kept"]]
+    m = S[:, :, o["mean"]:o["mean"] + k]
+    M2 = S[:, :, o["M2"]:o["M2"] + k * k].reshape(K, t, k, k)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = m.mean(axis=1)
+        dm = m - mean[:, None, :]
+        cov = (M2 / kept[:, :, None, None]).mean(axis=1) + np.einsum("ktq,ktp->kqp", dm, dm) / t
+        sd = np.sqrt(np.einsum("kqq->kq", cov))
+        W = (np.einsum("ktqq->ktq", M2) / (kept[:, :, None] - 1.0)).mean(axis=1)
+        Bn = (dm * dm).sum(axis=1) / (t - 1) if t > 1 else np.full((K, k), np.nan)
+        N = kept.mean(axis=1)[:, None]
+        rhat = np.sqrt(((N - 1.0) / N * W + Bn) / W)
+        acceptance = S[:, :, o["accepted"]] / kept
+        best = np.argmin(np.where(np.isnan(S[:, :, o["phi_min"]]), np.inf, S[:, :, o["phi_min"]]), axis=1)
+        pick = S[np.arange(K), best]
+        perp2 = np.zeros(K) if perp2 is None else np.asarray(perp2, dtype=np.float64).reshape(K)
+        misfit = np.sqrt(pick[:, o["phi_min"]] + perp2)
+    cnt = lambda name: np.nan_to_num(S[:, :, o[name]]).astype(np.int64)  # noqa: E731
+    return ParameterPosterior(mean, cov, sd, rhat, acceptance, np.exp(S[:, :, o["ls"]]), np.exp(pick[:, o["theta_min"]:o["theta_min"] + k]),
+                              misfit, S[:, :, o["mean_c"]:o["mean_c"] + n].mean(axis=1), cnt("outside"), cnt("not_spd"),
+                              None if samples is None else np.asarray(samples).reshape(K, t, -1, k), states)

@@ -477,6 +477,16 @@ class BaseReducedBasis:
         lib = ParameterLibrary(sm, self.basis, a_library).observe(measurement_points, weights=kw.pop("weights", None))
         return lib.estimate(measurements, **kw)
 
+    def parameter_posterior(self, sm: SolutionsManager, measurement_points: np.ndarray, measurements: np.ndarray, a_library, sigma,
+                            **kw):
+        """The posterior of log a given point measurements with noise of standard deviation ``sigma``: chains of adaptive
+        random-walk Metropolis on the Galerkin ROM from the library rows nearest to the data (``inverse.ParameterLibrary.posterior``,
+        ``rom_mcmc``) -- credible intervals next to ``parameter_estimation_library``'s point estimate.  ``kw``: weights (of
+        ``observe``), t, steps, burn, thin, seed, states, device (of ``posterior``).  Returns a ``ParameterPosterior``."""
+        from ..inverse import ParameterLibrary
+        lib = ParameterLibrary(sm, self.basis, a_library).observe(measurement_points, weights=kw.pop("weights", None))
+        return lib.posterior(measurements, sigma, **kw)
+
     def orthonormalize(self):
         """(:94-98) replace the basis by its contrast-sorted Euclidean-orthonormal version."""
         vectors = np.reshape(self.basis, (-1, self.ambient_space_dim))
