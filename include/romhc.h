@@ -723,6 +723,44 @@ int rom_bvls(rom_ctx* ctx, int n, int r, rom_buf* Gr, rom_buf* P, size_t p_off, 
              const double* hi_host, rom_buf* AUX, int max_iter, rom_buf* OUT, size_t out_off, int64_t ldo, rom_buf* BOUND,
              double* info8_host);
 
+/* ---- sensor state estimation with local reduced spaces: model selection by the PDE residual ----
+ * Cohen, Dahmen, Mula, Nichols, "Nonlinear reduced models for state and parameter estimation" (SIAM/ASA JUQ 10, 2022): the linear
+ * estimate is computed in each of kc local spaces, and the one whose residual, minimised over the cluster's parameter box, is
+ * smallest is kept; the minimiser is a parameter estimate.  romhighcontrast_amd/inverse.py::local_select_host is the same
+ * algorithm on the host.  For measurement vector i (row i of P: kc blocks of r reduced measurements, block j = p_ij, from an
+ * element offset with a row stride) and cluster j:
+ *   1. c_ij = argmin over c_lo[j] <= c <= c_hi[j] of ||p_ij - G_j c||, G_j (r x n row-major, full column rank) block j of GR:
+ *      the iteration of rom_bvls; misfit_ij = ||p_ij - G_j c_ij||.
+ *   2. B_ij[:, q] = sum_i' c_ij[i'] R_j[:, 1 + i' k + q] (rank x k), R_j (rank x (1 + k n) row-major, the residual table of
+ *      rom_resid_download what = 0, padded with zero rows to the common rank) block j of RT, rho_j = R_j[:, 0]:
+ *      ||r(a; c_ij W_j)||_H^-1 = ||rho_j - B_ij a|| for every a.
+ *   3. S_ij = min over a_lo[j] <= a <= a_hi[j] of ||rho_j - B_ij a||, the same iteration on B_ij (k unknowns); a_ij its minimiser.
+ *   4. label_i = the j of smallest (S_ij, j) among the systems of status 0 whose S is a number, or -1 when there is none.
+ * The boxes are host arrays, kc x n (c_lo, c_hi) and kc x k (a_lo, a_hi), with the rules of rom_bvls (lo == hi pins, infinite
+ * bounds allowed, lo > hi or NaN: ROM_ERR_INVALID).  max_iter bounds the passes of either solve; negative: 5 n + 10 and 5 k + 10.
+ * OUT row i kc + j (ldo >= n + k + 5 doubles apart, from out_off): c (n) | a (k) | S | misfit | passes of the state solve | passes
+ * of the parameter solve | status.  status: 1 the state solve failed on its data (NaN / Inf in p_ij or G_j, or G_j without full
+ * column rank: c, a, S, misfit are NaN), 2 the parameter solve did (NaN / Inf in R_j, or B_ij without full column rank: a and S
+ * are NaN), 4 the state solve stopped at max_iter, 8 the parameter solve did; bits add.  Bad data is no error of the call: it is
+ * reported per system.  label_host: K int32.
+ * Three launches whatever K and kc are (the Gram matrices G_j^T G_j; one workgroup per system for 1 - 3, with both iterations
+ * inside the launch and B_ij and its Gram matrix in LDS; the selection), one host synchronisation.  No input buffer is modified;
+ * no floating-point atomics, one fixed order in every sum, no system reads what another writes: the same bits on a repeated call
+ * and for every split of the rows.
+ * rom_local_select_layout (host only; the single place of the limits and of the LDS carve-up): 1 <= n <= 64, 1 <= k <= 16,
+ * n <= r <= 96, k <= rank <= rank_max(n, k, r), the largest rank whose B fits the workgroup's 64 KB of LDS beside the factor
+ * (638 at n = 32, k = 9; 1195 at n = 64, k = 4); ROM_ERR_INVALID outside.  rom_local_select adds 1 <= kc <= 256, K <= 2^23 and K kc <= 2^30; K = 0 is a
+ * no-op.  out8: LDS bytes of the fit kernel, doubles of an OUT row (n + k + 5), rank_max, the limit of kc, and in doubles the
+ * LDS offsets of the factor, of B and of B^T B; the number of launches.
+ * info8_host (8 doubles or NULL): systems K kc, kernel launches, host synchronisations, bytes of workspace, passes executed (both
+ * solves), factorisations executed (both summed on the device in integers), flops of steps 2 and of B^T B, systems of
+ * status != 0. */
+int rom_local_select_layout(int n, int k, int rank, int r, int64_t* out8);
+int rom_local_select(rom_ctx* ctx, int kc, int n, int k, int rank, int r, rom_buf* RT, rom_buf* GR, rom_buf* P, size_t p_off,
+                     int64_t ldp, int K, const double* c_lo_host, const double* c_hi_host, const double* a_lo_host,
+                     const double* a_hi_host, int max_iter, rom_buf* OUT, size_t out_off, int64_t ldo, int32_t* label_host,
+                     double* info8_host);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

@@ -157,6 +157,9 @@ PROTOTYPES = {
                                 _vp, _vp, _vp, C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_bvls": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_size_t,
                            C.c_int64, _vp, _vp]),
+    "rom_local_select_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "rom_local_select": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp,
+                                   _vp, _vp, _vp, C.c_int, _vp, C.c_size_t, C.c_int64, _vp, _vp]),
     "rom_tree_fit": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), _vp]),
     "rom_tree_predict": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64,
@@ -556,6 +559,39 @@ class Context:
                   passes=int(info[4]), factorisations=int(info[5]), bound_variables=rows[:, n + 1].astype(np.int64))
         return res, d8
 
+    def local_select_layout(self, n, k, rank, r) -> dict:
+        """rom_local_select_layout (host only): see the module function ``local_select_layout``."""
+        return local_select_layout(n, k, rank, r)
+
+    def local_select(self, kc, n, k, rank, r, RT: "Buffer", GR: "Buffer", P: "Buffer", p_off, ldp, K, c_lo, c_hi, a_lo, a_hi,
+                     max_iter=None, OUT: "Buffer | None" = None, out_off=0, ldo=None):
+        """rom_local_select: inverse.local_select_host on the device -- RT the kc residual tables (rank x (1 + k n) each), GR the
+        kc reduced sensor matrices (r x n each), P K rows of kc r reduced measurements (from p_off with stride ldp); the boxes
+        kc x n (c_lo, c_hi) and kc x k (a_lo, a_hi) host arrays; max_iter None: 5 n + 10 and 5 k + 10.  OUT (rows of
+        ldo >= n + k + 5 from out_off, row i kc + j: c | a | S | misfit | passes, passes | status) is allocated when None.
+        ValueError outside the limits of ``local_select_layout`` or for a bad box.  Returns (LocalSelectResult, info dict)."""
+        from .inverse import _local_select_result
+        kc, n, k, rank, r, K = int(kc), int(n), int(k), int(rank), int(r), int(K)
+        local_select_layout(n, k, rank, r)
+        w = n + k + 5
+        ldo = w if ldo is None else int(ldo)
+        box = [_host(np.broadcast_to(np.asarray(b, dtype=np.float64), (kc, d))) for b, d in ((c_lo, n), (c_hi, n), (a_lo, k), (a_hi, k))]
+        if OUT is None and K > 0:
+            OUT = self.alloc(int(out_off) + K * kc * ldo)
+        labels, info = np.full(K, -1, dtype=np.int32), np.zeros(8)
+        _check_kmeans(self.lib.rom_local_select(self.h, kc, n, k, rank, r, RT.h, GR.h, P.h if P is not None else None, int(p_off),
+                                                int(ldp), K, box[0].ctypes.data, box[1].ctypes.data, box[2].ctypes.data,
+                                                box[3].ctypes.data, -1 if max_iter is None else int(max_iter),
+                                                OUT.h if OUT is not None else None, int(out_off), ldo, labels.ctypes.data,
+                                                info.ctypes.data))
+        rows = np.zeros((K * kc, ldo))
+        if K:   # (the last row may end with the buffer, n + k + 5 doubles in)
+            rows.reshape(-1)[:(K * kc - 1) * ldo + w] = OUT.download((K * kc - 1) * ldo + w, offset=int(out_off))
+        res = _local_select_result(rows[:, :w].reshape(K, kc, w), labels, n, k)
+        d8 = dict(systems=int(info[0]), launches=int(info[1]), host_syncs=int(info[2]), workspace_bytes=int(info[3]),
+                  passes=int(info[4]), factorisations=int(info[5]), flops=float(info[6]), unconverged=int(info[7]))
+        return res, d8
+
     def symmetric_orthonormalize(self, V: "Buffer", n, dim, v_row0=0):
         check(self.lib.rom_symmetric_orthonormalize(self.h, V.h, v_row0, n, dim))
 
@@ -628,6 +664,17 @@ def kmeans_layout(r: int, kc: int) -> dict:
         raise ValueError(last_error())
     keys = ("r_padded", "kc_padded", "lds_bytes", "slab_rows", "r1_padded", "tile_stride", "partial_doubles", "tiles_per_wave")
     return {k: int(v) for k, v in zip(keys, out)}
+
+
+def local_select_layout(n: int, k: int, rank: int, r: int) -> dict:
+    """rom_local_select_layout (host only; the single place of the limits and of the LDS carve-up of the fit kernel).
+    ValueError, naming the limit, outside them."""
+    lib = load_library()
+    out = np.zeros(8, dtype=np.int64)
+    if lib.rom_local_select_layout(int(n), int(k), int(rank), int(r), out.ctypes.data) != ROM_OK:
+        raise ValueError(last_error())
+    keys = ("lds_bytes", "row_doubles", "rank_max", "kc_max", "factor_offset", "b_offset", "gram_offset", "launches")
+    return {k_: int(v) for k_, v in zip(keys, out)}
 
 
 MLP_ACTIVATIONS = {"tanh": 0, "logistic": 1, "sigmoid": 1, "relu": 2}

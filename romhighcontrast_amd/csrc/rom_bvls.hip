@@ -8,22 +8,16 @@
 // workgroup, free between workgroups.  Every loop is bounded by max_iter, n or r; nothing waits on another workgroup.  No
 // floating-point atomics and one fixed order in every sum: a repeated call returns the same bits.
 //
-// A pass (py:_bvls_solve): the Gram block of the free columns -- packed to the front in ascending order by a ballot, which gives
-// the factor the host gets from the identity rows it puts in the place of the bound ones, without their elimination steps -- is
-// factored in LDS (L D L^T, lm_factor of rom_lm_small.h, all four waves) and solved by wave 0 (lm_solve); one refinement step
-// follows with the residual formed on the columns of G_r themselves, so the error of c is that of a least-squares solve, not of
-// the bare normal equations.
+// The iteration itself is BvSys of rom_bvls_sys.h (shared with rom_local_select.hip).
 // G^T G is formed once per call by k_bvls_gram (shared by every system).  G_r (at most 48 KB) and G^T G (32 KB) are read through
 // L2: with G_r in LDS beside the 33 KB factor a CU would hold one workgroup; here the LDS is 40.2 KB and four fit.
 #include <cmath>
 
 #include "rom_basis_int.h"
 #include "rom_block.h"
-#include "rom_lm_small.h"
+#include "rom_bvls_sys.h"
 
 namespace {
-
-constexpr int BV_NMAX = 64, BV_RMAX = 96, BV_LD = BV_NMAX + 1;
 
 struct BvBox {
   double lo[BV_NMAX], hi[BV_NMAX];
@@ -38,115 +32,13 @@ struct BvArgs {
   int* status;                    // bit 0: NaN / Inf in an operand; bit 1: a pivot of the free Gram block is not positive
 };
 
-__device__ __forceinline__ bool bv_finite(double v) { return fabs(v) < __builtin_huge_val(); }
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
-// gram = G^T G (n x n): block j, thread k, ascending rows; every block also looks at every entry of G
-__global__ __launch_bounds__(BV_NMAX) void k_bvls_gram(const double* __restrict__ G, int n, int r, double* __restrict__ gram, int* status) {
-  const int j = blockIdx.x, k = threadIdx.x;
-  if (k >= n) return;
-  bool bad = false;
-  double s = 0.0;
-  for (int i = 0; i < r; ++i) {
-    const double gk = G[size_t(i) * n + k];
-    bad |= !bv_finite(gk);
-    s = fma(G[size_t(i) * n + j], gk, s);
-  }
-  gram[j * n + k] = s;
-  if (bad) atomicOr(status, 1);
-}
-
-struct BvSys {
-  const BvArgs& a;
-  double *H, *invd, *c, *z, *v, *gn, *part, *ps, *rs, *flag;
-  int *st, *idx, *nfree;   // the state; the free columns in ascending order and their number
-  int nf = 0;
-  unsigned long long factorisations = 0;
-
-  // rs = p - G v  (r rows, 16 lanes per row: columns q, q + 16, .. by fma, then the butterfly)
-  __device__ void residual() {
-    const int tid = threadIdx.x, q = tid & 15, n = a.n, r = a.r;
-    for (int row = tid >> 4; row < (r + 15) / 16 * 16; row += 16) {
-      double s = 0.0;
-      if (row < r)
-        for (int j = q; j < n; j += 16) s = fma(a.G[size_t(row) * n + j], v[j], s);
-      s = group16_sum(s);
-      if (row < r && q == 0) rs[row] = ps[row] - s;
-    }
-    __syncthreads();
-  }
-
-  // v = G^T rs  (lane = column; wave w takes the rows w, w + 4, .. by fma; the four partial sums are added in wave order)
-  __device__ void gradient() {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n = a.n, r = a.r;
-    double s = 0.0;
-    if (lane < n)
-      for (int i = w; i < r; i += 4) s = fma(a.G[size_t(i) * n + lane], rs[i], s);
-    part[tid] = s;
-    __syncthreads();
-    if (tid < n) v[tid] = ((part[tid] + part[64 + tid]) + part[128 + tid]) + part[192 + tid];
-    __syncthreads();
-  }
-
-  // wave 0: x = (L D L^T)^-1 (v on the free columns); lane = position among the free columns
-  __device__ double solve(int lane) const {
-    double b[1] = {lane < nf ? v[idx[lane]] : 0.0};
-    lm_solve<1>(H, BV_LD, nf, invd, b, lane);
-    return b[0];
-  }
-
-  // py:_bvls_solve with rhs = p - G (c on the bound columns): z = the solution on the free columns, c on the bound ones
-  __device__ void least_squares() {
-    const int tid = threadIdx.x, n = a.n;
-    if (tid < 64) {
-      const bool is_free = tid < n && st[tid] == 0;
-      const unsigned long long free_mask = __ballot(is_free);
-      if (is_free) idx[__popcll(free_mask & ((1ull << tid) - 1ull))] = tid;
-      if (tid == 0) *nfree = __popcll(free_mask);
-    }
-    if (tid < n) v[tid] = st[tid] == 0 ? 0.0 : c[tid];
-    __syncthreads();
-    nf = *nfree;
-    for (int x = tid; x < nf * nf; x += LMS_THREADS) {
-      const int i = x / nf, k = x - i * nf;
-      if (k <= i) H[i * BV_LD + k] = a.gram[idx[i] * n + idx[k]];
-    }
-    __syncthreads();
-    if (!lm_factor(H, BV_LD, nf, invd, flag) && tid == 0) atomicOr(a.status, 2);
-    factorisations += 1;
-    residual();
-    gradient();
-    if (tid < 64) {
-      const double x = solve(tid);
-      if (tid < nf) z[idx[tid]] = x;
-      if (tid < n && st[tid] != 0) z[tid] = c[tid];
-    }
-    __syncthreads();
-    if (tid < n) v[tid] = z[tid];
-    __syncthreads();
-    residual();
-    gradient();
-    if (tid < 64) {
-      const double x = solve(tid);
-      if (tid < nf) z[idx[tid]] += x;
-    }
-    __syncthreads();
-  }
-};
-
 __global__ __launch_bounds__(LMS_THREADS) void k_bvls(const BvArgs a, const BvBox box) {
   __shared__ double H[BV_NMAX * BV_LD];
   __shared__ double invd[BV_NMAX], c[BV_NMAX], z[BV_NMAX], v[BV_NMAX], gn[BV_NMAX], part[LMS_THREADS], ps[BV_RMAX], rs[BV_RMAX], flag[2];
   __shared__ int st[BV_NMAX], barred[BV_NMAX], idx[BV_NMAX], ctl[3];   // ctl: the pass was infeasible; nothing left to free; free columns
   const int tid = threadIdx.x, lane = tid & 63, n = a.n, r = a.r;
   const long long sys = blockIdx.x;
-  BvSys S = {a, H, invd, c, z, v, gn, part, ps, rs, flag, st, idx, ctl + 2};
-  const bool in = tid < n;   // (of wave 0: this lane has a column)
+  BvSys S = {n, r, a.G, a.gram, a.status, H, invd, c, z, v, gn, part, ps, rs, flag, st, barred, idx, ctl};
   const double lo = box.lo[lane], hi = box.hi[lane];
 
   if (tid < r) {
@@ -154,91 +46,11 @@ __global__ __launch_bounds__(LMS_THREADS) void k_bvls(const BvArgs a, const BvBo
     if (!bv_finite(p)) atomicOr(a.status, 1);
     ps[tid] = p;
   }
-  if (in) {
-    gn[tid] = sqrt(a.gram[tid * n + tid]);
-    st[tid] = 0, barred[tid] = 0, c[tid] = 0.0;
-  }
-  __syncthreads();
-  S.least_squares();   // py:`start`
-  if (in) {
-    const double x = z[tid];
-    c[tid] = fmin(fmax(x, lo), hi);
-    st[tid] = (lo == hi || x <= lo) ? -1 : (x >= hi ? 1 : 0);
-  }
-  __syncthreads();
-
-  int passes = 0, freed = -1, side = 0;   // (freed, side: wave 0's)
   bool conv = false;
-  for (int it = 0; it < a.max_iter && !conv; ++it) {
-    passes += 1;
-    S.least_squares();
-    if (tid < 64) {
-#pragma clang fp contract(off)   // (the step c + alpha (z - c) as the host forms it)
-      const int s_old = in ? st[lane] : 0;
-      const bool F = in && s_old == 0;
-      const double zj = in ? z[lane] : 0.0, cj = in ? c[lane] : 0.0;
-      const bool below = F && zj < lo, above = F && zj > hi;
-      const bool infeasible = __ballot(below || above) != 0ull;
-      if (infeasible) {   // py:`infeasible`: to the first bound on the segment; what hits it is bound
-        const double ratio = below ? (cj - lo) / (cj - zj) : (above ? (hi - cj) / (zj - cj) : __builtin_huge_val());
-        const double alpha = wave_min(ratio);
-        double cn = cj;
-        int s = s_old;
-        if (F) {
-          cn = fmin(fmax(cj + alpha * (zj - cj), lo), hi);
-          if (ratio == alpha) cn = below ? lo : hi;
-          s = cn == lo ? -1 : (cn == hi ? 1 : 0);
-        }
-        const unsigned long long changed = __ballot(s != s_old);
-        const int fs = __shfl(s, freed >= 0 ? freed : 0, 64);
-        const bool same = freed >= 0 && ((changed >> freed) & 1ull) && fs == side;
-        const unsigned long long others = same ? changed & ~(1ull << freed) : changed;
-        if (in) {
-          if (others) barred[lane] = 0;
-          if (same && lane == freed) barred[lane] = 1;
-          c[lane] = cn, st[lane] = s;
-        }
-        freed = -1;
-      } else if (in) {   // py:`~infeasible`: the solution is taken (a free variable exactly on a bound: bound)
-        c[lane] = zj, v[lane] = zj;
-        if (F) st[lane] = zj == lo ? -1 : (zj == hi ? 1 : 0);
-      }
-      if (lane == 0) ctl[0] = infeasible ? 1 : 0;
-    }
-    __syncthreads();
-    if (ctl[0] == 0) {
-      S.residual();
-      S.gradient();   // v = G^T (p - G c) = -g
-      if (tid < 64) {
-        if (freed >= 0 && in) barred[lane] = 0;   // the variable freed in the last pass has stayed free
-        const int s = in ? st[lane] : 0;
-        double viol = 0.0;
-        if (in && s != 0 && lo != hi && !barred[lane]) {
-          const double x = (s < 0 ? v[lane] : -v[lane]) / gn[lane];
-          viol = x > 0.0 ? x : 0.0;
-        }
-        const double worst = wave_max_nan(viol);
-        const unsigned long long at = __ballot(viol == worst && worst > 0.0);
-        freed = -1;
-        if (at) {   // the lowest index among equals
-          freed = __ffsll((long long)at) - 1;
-          side = __shfl(s, freed, 64);
-          if (lane == freed) st[lane] = 0;
-        }
-        if (lane == 0) ctl[1] = at ? 0 : 1;
-      }
-      __syncthreads();
-      conv = ctl[1] != 0;
-    }
-  }
-
-  if (in) v[tid] = c[tid];
-  __syncthreads();
-  S.residual();
+  const int passes = S.run(lo, hi, a.max_iter, &conv);   // (its first step is a barrier)
+  const double f = S.misfit2();
   if (tid < 64) {
-    double f = 0.0;
-    for (int i = lane; i < r; i += 64) f = fma(rs[i], rs[i], f);
-    f = wave_sum(f);
+    const bool in = tid < n;
     const unsigned long long nb = __ballot(in && st[lane] != 0);
     double* out = a.OUT + sys * a.ldo;
     if (in) {

@@ -489,6 +489,110 @@ def bvls_host(G, P, lo, hi, aux=None, max_iter=None) -> BvlsResult:
     return BvlsResult(c, misfit, st.astype(np.int64), conv, passes)
 
 
+# ---- model selection among local reduced spaces (Cohen, Dahmen, Mula, Nichols 2022) --------------------------------------------
+LS_BAD_STATE, LS_BAD_PARAM, LS_OPEN_STATE, LS_OPEN_PARAM = 1, 2, 4, 8   # the bits of a system's status
+
+
+class LocalSelectResult(NamedTuple):
+    """``local_select_host`` / ``Context.local_select``.  labels (K,) int32: the cluster of smallest (S, index) among the systems
+    of status 0, -1 when there is none; coefficients (K, n), a (K, k), surrogate (K,), misfit (K,): those of the chosen cluster
+    (NaN where the label is -1); c_all (K, kc, n), a_all (K, kc, k), surrogate_all, misfit_all (K, kc): every system;
+    passes (K, kc, 2): of the state and of the parameter solve; status (K, kc): 0, or the sum of 1 (the state solve failed on its
+    data: NaN / Inf, or G_j without full column rank), 2 (the parameter solve did), 4 (the state solve stopped at max_iter),
+    8 (the parameter solve did)."""
+    labels: np.ndarray
+    coefficients: np.ndarray
+    a: np.ndarray
+    surrogate: np.ndarray
+    misfit: np.ndarray
+    c_all: np.ndarray
+    a_all: np.ndarray
+    surrogate_all: np.ndarray
+    misfit_all: np.ndarray
+    passes: np.ndarray
+    status: np.ndarray
+
+
+def _local_select_result(rows, labels, n, k) -> LocalSelectResult:
+    """From the (K, kc, n + k + 5) rows c | a | S | misfit | passes, passes | status and the labels."""
+    K = rows.shape[0]
+    labels = np.asarray(labels, dtype=np.int32)
+    pick = rows[np.arange(K), np.maximum(labels, 0)] if K else np.zeros((0, n + k + 5))
+    pick = np.where((labels >= 0)[:, None], pick, np.nan)
+    return LocalSelectResult(labels, pick[:, :n].copy(), pick[:, n:n + k].copy(), pick[:, n + k].copy(), pick[:, n + k + 1].copy(),
+                             rows[:, :, :n].copy(), rows[:, :, n:n + k].copy(), rows[:, :, n + k].copy(), rows[:, :, n + k + 1].copy(),
+                             rows[:, :, n + k + 2:n + k + 4].astype(np.int64), rows[:, :, n + k + 4].astype(np.int64))
+
+
+def local_select_labels(surrogate_all, status):
+    """Step 4: per row the index of the smallest (S, index) among the entries of status 0 whose S is a number; -1 when there is
+    none."""
+    S = np.asarray(surrogate_all, dtype=np.float64)
+    ok = (np.asarray(status) == 0) & ~np.isnan(S)
+    S = np.where(ok, S, np.inf)
+    labels = np.argmin(S, axis=1).astype(np.int32) if S.shape[1] else np.zeros(len(S), dtype=np.int32)   # (the first minimum)
+    return np.where(ok.any(axis=1), labels, -1).astype(np.int32)
+
+
+def local_select_matrix(R, c, k):
+    """B (rank, k) = sum_i c_i R[:, 1 + i k : 1 + (i + 1) k], the terms in ascending i: ||R z(a, c)|| = ||R[:, 0] - B a||."""
+    R, c = np.asarray(R, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    B = np.zeros((R.shape[0], k))
+    for i in range(len(c)):
+        B = c[i] * R[:, 1 + i * k:1 + (i + 1) * k] + B
+    return B
+
+
+def local_select_host(RT, GR, P, c_lo, c_hi, a_lo, a_hi, max_iter=None) -> LocalSelectResult:
+    """The NumPy specification of ``rom_local_select``: state estimation from sensors with kc local reduced spaces, the space
+    chosen by the PDE residual (Cohen, Dahmen, Mula, Nichols, SIAM/ASA JUQ 10, 2022).  RT (kc, rank, 1 + k n): the residual
+    tables R_j of A_1-orthonormal bases W_j (``rom_resid_download`` what = 0; zero rows added to a common rank change nothing);
+    GR (kc, r, n): the reduced sensor matrices G_j; P (K, kc r): per measurement vector the kc reduced measurements p_ij; the
+    boxes (kc, n) for c and (kc, k) for a, with the rules of ``bvls_host``.  Per system (i, j), two ``bvls_host`` calls:
+
+      1. c_ij = argmin over c_lo[j] <= c <= c_hi[j] of ||p_ij - G_j c||, misfit_ij its residual norm;
+      2. B_ij = ``local_select_matrix(R_j, c_ij, k)``: the residual of the state c_ij W_j is rho_j - B_ij a, affine in a;
+      3. S_ij = min over a_lo[j] <= a <= a_hi[j] of ||rho_j - B_ij a||, a_ij its minimiser;
+
+    then label_i = the j of smallest (S_ij, j) among the systems of status 0 (``local_select_labels``).  A solve that
+    ``bvls_host`` refuses (NaN / Inf, no full column rank) sets the system's status instead of raising: after a refused state
+    solve c, a, S and the misfit are NaN, after a refused parameter solve a and S.  max_iter bounds the passes of either solve;
+    None: 5 n + 10 and 5 k + 10.  ValueError: a bad box."""
+    RT, GR = np.asarray(RT, dtype=np.float64), np.asarray(GR, dtype=np.float64)
+    kc, r, n = GR.shape
+    rank = RT.shape[1]
+    k = (RT.shape[2] - 1) // n
+    assert RT.shape == (kc, rank, 1 + k * n), f"local_select_host: RT {RT.shape} against kc = {kc}, n = {n}"
+    P = np.asarray(P, dtype=np.float64).reshape(-1, kc, r)
+    K = len(P)
+    box = [np.array(np.broadcast_to(np.asarray(b, dtype=np.float64), (kc, d))) for b, d in ((c_lo, n), (c_hi, n), (a_lo, k), (a_hi, k))]
+    for j in range(kc):
+        _bvls_box(box[0][j], box[1][j], n)
+        _bvls_box(box[2][j], box[3][j], k)
+    rows = np.full((K, kc, n + k + 5), np.nan)
+    rows[:, :, n + k + 2:] = 0.0
+    for i in range(K):
+        for j in range(kc):
+            row = rows[i, j]
+            try:
+                one = bvls_host(GR[j], P[i, j][None, :], box[0][j], box[1][j], max_iter=max_iter)
+            except ValueError:
+                row[n + k + 4] = LS_BAD_STATE
+                continue
+            status = 0 if one.converged[0] else LS_OPEN_STATE
+            row[:n], row[n + k + 1], row[n + k + 2] = one.c[0], one.misfit[0], one.iterations[0]
+            B = local_select_matrix(RT[j], one.c[0], k)
+            try:
+                two = bvls_host(B, RT[j][:, 0][None, :], box[2][j], box[3][j], max_iter=max_iter)
+                status |= 0 if two.converged[0] else LS_OPEN_PARAM
+                row[n:n + k], row[n + k], row[n + k + 3] = two.c[0], two.misfit[0], two.iterations[0]
+            except ValueError:
+                status |= LS_BAD_PARAM
+            row[n + k + 4] = status
+    labels = local_select_labels(rows[:, :, n + k], rows[:, :, n + k + 4])
+    return _local_select_result(rows, labels, n, k)
+
+
 def coefficient_box(C, inflate=0.1):
     """(lo, hi) (n each): min / max over the rows of a training coefficient matrix C (M, n), widened on both sides by
     ``inflate`` times the range."""

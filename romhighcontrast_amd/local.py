@@ -7,7 +7,12 @@ effective dimension of the manifold.
 ``kmeans_host`` / ``maximin_rows_host`` are the NumPy specification of ``rom_kmeans_fit`` / ``rom_kmeans_init_maximin`` (the same
 rules: the total order (dist2, centroid index), empty clusters kept where they are, the stop rules, the final assignment);
 ``KMeans`` is the estimator on the device and ``LocalReducedBasis`` the clustered POD bases with the online operations of
-``BaseReducedBasis``."""
+``BaseReducedBasis``.
+
+When the parameter is the unknown -- state estimation from point sensors -- the cluster cannot be looked up:
+``LocalReducedBasis.observe`` fixes the sensors and returns a ``LocalSensing``, whose ``estimate`` computes the linear estimate in
+every local space and keeps the one whose PDE residual, minimised over the cluster's parameter box, is smallest (Cohen, Dahmen,
+Mula, Nichols, SIAM/ASA JUQ 10, 2022; ``rom_local_select``, specification ``inverse.local_select_host``)."""
 from __future__ import annotations
 
 from logging import warning
@@ -15,7 +20,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-__all__ = ["kmeans_host", "maximin_rows_host", "dist2_host", "KMeansHostResult", "KMeans", "LocalReducedBasis"]
+__all__ = ["kmeans_host", "maximin_rows_host", "dist2_host", "KMeansHostResult", "KMeans", "LocalReducedBasis", "LocalSensing",
+           "LocalEstimate"]
 
 
 # ---- the NumPy specification ------------------------------------------------------------------------------------------------
@@ -243,6 +249,10 @@ class LocalReducedBasis:
         return np.log(a.reshape(len(a), -1))
 
     def build(self, n: int, sm, solutions2train, a2train, features=None, **kwargs):
+        """Cluster, then one POD per cluster.  For ``observe`` it also stores, per cluster, the parameter ranges (``a_ranges_``,
+        ``a_range_``) and the box its training snapshots span in the A_1-orthonormal basis of its modes
+        (``coefficient_boxes_``): one ``ResidualEstimator``, one stencil application and one GEMM per cluster, paid by every
+        ``build`` (None for a centred basis, which ``observe`` refuses)."""
         from .factored import FactoredSnapshots
         from .lib.ReducedBasis import BaseReducedBasis, pod_modes, pod_modes_h10
         from .lib.SolutionsManagers import DeviceArray, _as_device
@@ -256,7 +266,10 @@ class LocalReducedBasis:
         assert len(F) == Ud.rows, "LocalReducedBasis.build: one feature row per snapshot"
         self.kmeans = KMeans(self.n_clusters, max_iter=self.max_iter, ctx=ctx).fit(F)
         self.labels_ = self.kmeans.labels_
-        self.bases, self.singular_values_ = [], []
+        self.bases, self.singular_values_, self.coefficient_boxes_ = [], [], []
+        a_flat = a2.reshape(len(a2), -1)
+        self.a_range_ = (a_flat.min(axis=0), a_flat.max(axis=0))          # the box of all training parameters, per block
+        self.a_ranges_ = []                                              # and of every cluster's
         for j in range(self.n_clusters):
             idx = np.flatnonzero(self.labels_ == j)
             if idx.size < n + 1:
@@ -271,7 +284,28 @@ class LocalReducedBasis:
             rb.set(basis=comps, a=a2[idx][:n])   # (as ReducedBasisPCA: the parameters are not those of the modes)
             self.bases.append(rb)
             self.singular_values_.append(sigma)
+            self.a_ranges_.append((a_flat[idx].min(axis=0), a_flat[idx].max(axis=0)))
+            self.coefficient_boxes_.append(None if self.center else self._training_box(sm, comps, X))
         return self
+
+    @staticmethod
+    def _training_box(sm, comps, X):
+        """``coefficient_box`` of the coordinates X A_1 W^T of the cluster's snapshots X in the A_1-orthonormal basis W that a
+        residual estimator builds on ``comps`` (the coordinates ``LocalSensing`` works in); None when ``comps`` has dead rows."""
+        from .inverse import coefficient_box
+        from .lib.ReducedBasis import ResidualEstimator
+        ctx, dim, n = sm._ctx, sm.vspace_dim, len(comps)
+        est = ResidualEstimator(sm, comps)
+        try:
+            if est.handle.download("dead").any():
+                return None
+            Wd, AW, Cf = ctx.alloc(n * dim), ctx.alloc(n * dim), ctx.alloc(X.rows * n)
+            est.handle.basis(Wd)
+            sm._fem.stencil_apply(Wd, n, AW)
+            ctx.gemm_nt(X.rows, n, dim, X.buf, 0, dim, AW, 0, dim, Cf, 0, n)
+            return coefficient_box(Cf.download(X.rows * n, shape=(X.rows, n)))
+        finally:
+            est.handle.free()
 
     def classify(self, a=None, features=None) -> np.ndarray:
         """The cluster of every parameter (or feature row): (M,) int32."""
@@ -330,3 +364,187 @@ class LocalReducedBasis:
         proj = sm.H10norm_diff(self.projection(sm, Ud, a), Ud) / norms
         gal = sm.H10norm_diff(self.forward_modeling(sm, a), Ud) / norms
         return proj, gal
+
+    # -- the inverse problem: the parameter, and with it the cluster, is unknown ----------------------------------------------
+    def observe(self, sm, points, weights=None, bounds=None, a_box="cluster", inflate=0.1) -> "LocalSensing":
+        """Fix the sensors: ``points`` (m, 2) with optional weights (m,).  Per cluster a ``ResidualEstimator`` on its basis gives
+        the A_1-orthonormal basis W_j and the residual table R_j; W_j is evaluated at the points and the sensors are reduced
+        (``inverse.reduce_sensors``); the packed tables are uploaded once.  ValueError when a basis has dead directions, when the
+        sensors do not determine the n coefficients of a cluster, for a basis built with center=True, or outside the limits of
+        ``rom_local_select_layout``.
+        bounds: None (the plain least squares of the reference in every cluster), "training" (each cluster's
+        ``coefficient_boxes_``: the box its training snapshots span in W_j, computed by ``build``) or (lo, hi), kc x n arrays.
+        a_box: "cluster" -- per block [min, max] of the cluster's training parameters, widened on both sides by ``inflate`` times
+        the range in log a -- or "global": the box of all training parameters, for every cluster."""
+        assert self.kmeans is not None, "LocalReducedBasis.observe before build"
+        if self.center:
+            raise ValueError("LocalReducedBasis.observe: center=True is not supported (the local spaces are linear: the estimate "
+                             "c W_j has no mean added); build with center=False")
+        return LocalSensing(self, sm, points, weights, bounds, a_box, inflate)
+
+    def state_estimation(self, sm, measurement_points, measurements, return_coefs=False, **observe_kwargs):
+        """``BaseReducedBasis.state_estimation`` with the local space chosen per measurement vector by the residual surrogate:
+        the estimates (K, dim), with ``return_coefs`` also c (n, K) -- in the coordinates of the A_1-orthonormal basis of the
+        chosen cluster (``LocalSensing.W``).  ``observe_kwargs``: weights, bounds, a_box, inflate of ``observe``."""
+        est = self.observe(sm, measurement_points, **observe_kwargs).estimate(measurements, states=True)
+        return (np.ascontiguousarray(est.coefficients.T), est.states) if return_coefs else est.states
+
+
+class LocalEstimate(NamedTuple):
+    """``LocalSensing.estimate``.  labels (K,) int32 (-1: no cluster's two solves converged on finite data); coefficients (K, n)
+    in the chosen cluster's W; a (K, k): the minimiser of the surrogate, the blocks flattened as in ``a.reshape(K, -1)``;
+    surrogate (K,) = min over the box of ||r(a; c W)||_{H^-1}; misfit (K,): the weighted measurement residual including the part
+    outside the range of the reduced sensors; surrogate_all, misfit_all (K, kc), coefficients_all (K, kc, n), a_all (K, kc, k),
+    status (K, kc): every cluster's; converged (K,): label >= 0; states (K, dim) = c W_label, or None."""
+    labels: np.ndarray
+    coefficients: np.ndarray
+    a: np.ndarray
+    surrogate: np.ndarray
+    misfit: np.ndarray
+    surrogate_all: np.ndarray
+    misfit_all: np.ndarray
+    converged: np.ndarray
+    states: "np.ndarray | None"
+    coefficients_all: np.ndarray
+    a_all: np.ndarray
+    status: np.ndarray
+
+
+class LocalSensing:
+    """Sensors fixed on a ``LocalReducedBasis`` (``LocalReducedBasis.observe``).  Host: ``W`` (kc of (n, dim)), ``RT``
+    (kc, rank, 1 + k n), ``GR`` (kc, r, n), ``U`` (kc of (m, r)), the boxes ``c_lo``, ``c_hi`` (kc, n), ``a_lo``, ``a_hi`` (kc, k);
+    the same tables stay on the device.  It holds device state and is not picklable: pickle the ``LocalReducedBasis`` and call
+    ``observe`` again."""
+
+    def __init__(self, lrb, sm, points, weights, bounds, a_box, inflate):
+        from . import _ffi
+        from .inverse import reduce_sensors
+        from .lib.ReducedBasis import ResidualEstimator
+        ctx, kc = sm._ctx, lrb.n_clusters
+        points = np.asarray(points, dtype=np.float64)
+        m = len(points)
+        self.lrb, self.sm, self.ctx, self.kc, self.m = lrb, sm, ctx, kc, m
+        self.weights = np.ones(m) if weights is None else np.asarray(weights, dtype=np.float64).reshape(m)
+        self.W, self.U, tables, G = [], [], [], []
+        for j in range(kc):
+            est = ResidualEstimator(sm, lrb.bases[j].basis)
+            try:
+                dead = est.handle.download("dead")
+                if dead.any():
+                    raise ValueError(f"LocalReducedBasis.observe: the basis of cluster {j} has dead directions (rows "
+                                     f"{np.flatnonzero(dead)[:8].tolist()}): no A_1-orthonormal basis of its dimension")
+                tables.append(est.handle.download("R"))
+                self.W.append(est.handle.download("W"))
+            finally:
+                est.handle.free()
+            n = len(self.W[j])
+            E = sm.evaluate_solutions(points, self.W[j])
+            Uj, Gj, _ = reduce_sensors(E, self.weights)
+            if Uj.shape[1] < n:
+                raise ValueError(f"LocalReducedBasis.observe: the {m} weighted sensors determine {Uj.shape[1]} of the {n} coefficients "
+                                 f"of cluster {j} (E_j lacks full column rank)")
+            self.U.append(Uj)
+            G.append(Gj)
+        n = len(self.W[0])
+        assert all(len(W) == n for W in self.W), "LocalReducedBasis.observe: one dimension for all clusters"
+        self.n, self.r = n, n
+        self.k = (tables[0].shape[1] - 1) // n
+        self.rank = max(len(R) for R in tables)
+        self.layout = _ffi.local_select_layout(self.n, self.k, self.rank, self.r)   # (ValueError outside the limits)
+        if kc > self.layout["kc_max"]:
+            raise ValueError(f"LocalReducedBasis.observe: kc = {kc} clusters, at most {self.layout['kc_max']} (rom_local_select)")
+        self.RT = np.zeros((kc, self.rank, 1 + self.k * n))
+        for j, R in enumerate(tables):
+            self.RT[j, :len(R)] = R                  # (zero rows: exact)
+        self.GR = np.ascontiguousarray(np.stack(G))
+        self.Ucat = np.ascontiguousarray(np.concatenate(self.U, axis=1))   # (m, kc r): Y [U_1 .. U_kc] is one product
+        self.c_lo, self.c_hi = self._c_box(bounds)
+        self.a_lo, self.a_hi = self._a_box(a_box, inflate)
+        self.RT_dev, self.GR_dev, self.U_dev = ctx.upload(self.RT), ctx.upload(self.GR), ctx.upload(self.Ucat)
+        self.W_dev = [ctx.upload(W) for W in self.W]
+
+    def __getstate__(self):
+        raise TypeError("LocalSensing holds device state and is not picklable: pickle the LocalReducedBasis and call observe again")
+
+    def _c_box(self, bounds):
+        kc, n = self.kc, self.n
+        if bounds is None:
+            return np.full((kc, n), -np.inf), np.full((kc, n), np.inf)
+        if isinstance(bounds, str):
+            if bounds != "training":
+                raise ValueError(f"LocalReducedBasis.observe: bounds = {bounds!r}; None, 'training' or (lo, hi)")
+            boxes = getattr(self.lrb, "coefficient_boxes_", None)
+            if not boxes or any(b is None for b in boxes):
+                raise ValueError("LocalReducedBasis.observe: bounds = 'training' needs the boxes that build stores (coefficient_boxes_)")
+            return np.stack([b[0] for b in boxes]), np.stack([b[1] for b in boxes])
+        lo, hi = (np.array(np.broadcast_to(np.asarray(b, dtype=np.float64), (kc, n))) for b in bounds)
+        return lo, hi
+
+    def _a_box(self, a_box, inflate):
+        lrb, kc = self.lrb, self.kc
+        if a_box == "global":
+            return np.tile(lrb.a_range_[0], (kc, 1)), np.tile(lrb.a_range_[1], (kc, 1))
+        if a_box != "cluster":
+            raise ValueError(f"LocalReducedBasis.observe: a_box = {a_box!r}; 'cluster' or 'global'")
+        lo, hi = np.log(np.stack([b[0] for b in lrb.a_ranges_])), np.log(np.stack([b[1] for b in lrb.a_ranges_]))
+        pad = float(inflate) * (hi - lo)
+        return np.exp(lo - pad), np.exp(hi + pad)
+
+    def _perp2(self, Yw, P):
+        """(K, kc): |(w y) - U_j p_ij|^2, the part of the weighted measurements outside the range of U_j, from the product P."""
+        out = np.zeros((len(Yw), self.kc))
+        for j, Uj in enumerate(self.U):
+            perp = Yw - P[:, j * self.r:(j + 1) * self.r] @ Uj.T
+            out[:, j] = np.einsum("km,km->k", perp, perp)
+        return out
+
+    def reduce(self, measurements):
+        """On the host: (Y w (K, m), P = Y w [U_1 .. U_kc] (K, kc r) with p_ij = U_j^T (w y_i) in block j, perp2 (K, kc)) -- per
+        cluster what ``inverse.reduce_measurements`` returns, from one product."""
+        Yw = np.asarray(measurements, dtype=np.float64).reshape(-1, self.m) * self.weights[None, :]
+        P = np.ascontiguousarray(Yw @ self.Ucat)
+        return Yw, P, self._perp2(Yw, P)
+
+    def estimate(self, measurements, states=False, device=True) -> LocalEstimate:
+        """For the K rows of ``measurements`` (K, m): the linear estimate in every local space, the cluster of smallest residual
+        surrogate, its coefficients and parameter.  ``device``: one device product Y w [U_1 .. U_kc] for the reduced measurements
+        of all clusters (downloaded once, for the part of w y outside the range of each U_j that the misfit includes), then
+        ``rom_local_select``; False: ``reduce`` and the NumPy specification ``inverse.local_select_host``.  ``states``: also
+        c W_label (K, dim), one ``rom_gemm_nn`` per non-empty cluster (rows of label -1: NaN)."""
+        from .inverse import local_select_host
+        ctx, kc, n, k, r = self.ctx, self.kc, self.n, self.k, self.r
+        if device and len(np.atleast_2d(measurements)):
+            Yw = np.asarray(measurements, dtype=np.float64).reshape(-1, self.m) * self.weights[None, :]
+            K = len(Yw)
+            Pd = ctx.alloc(K * kc * r)
+            ctx.gemm_nn(K, kc * r, self.m, ctx.upload(Yw), 0, self.m, self.U_dev, 0, kc * r, Pd, 0, kc * r)
+            res, _ = ctx.local_select(kc, n, k, self.rank, r, self.RT_dev, self.GR_dev, Pd, 0, kc * r, K, self.c_lo, self.c_hi, self.a_lo,
+                                      self.a_hi)
+            perp2 = self._perp2(Yw, Pd.download(K * kc * r, shape=(K, kc * r)))
+        else:
+            Yw, P, perp2 = self.reduce(measurements)
+            K = len(Yw)
+            res = local_select_host(self.RT, self.GR, P, self.c_lo, self.c_hi, self.a_lo, self.a_hi)
+        misfit_all = np.sqrt(res.misfit_all ** 2 + perp2)
+        labels = res.labels
+        ok = labels >= 0
+        misfit = np.where(ok, misfit_all[np.arange(K), np.maximum(labels, 0)], np.nan)
+        lifted = self._lift(res.coefficients, labels) if states else None
+        return LocalEstimate(labels, res.coefficients, res.a, res.surrogate, misfit, res.surrogate_all, misfit_all, ok, lifted,
+                             res.c_all, res.a_all, res.status)
+
+    def _lift(self, coefficients, labels):
+        """c W_label per row (K, dim) on the host; rows of label -1 are NaN."""
+        from .lib.SolutionsManagers import DeviceArray
+        ctx, dim, n = self.ctx, self.sm.vspace_dim, self.n
+        ok = np.flatnonzero(labels >= 0)
+        out = np.full((len(labels), dim), np.nan)
+        if ok.size:
+            C = np.ascontiguousarray(coefficients[ok])
+
+            def run(j, idx):
+                part = ctx.alloc(idx.size * dim)
+                ctx.gemm_nn(idx.size, dim, n, ctx.upload(C[idx]), 0, n, self.W_dev[j], 0, dim, part, 0, dim)
+                return DeviceArray(part, idx.size, dim)
+            out[ok] = self.lrb._per_cluster(self.sm, labels[ok], run).numpy()
+        return out
