@@ -761,6 +761,56 @@ int rom_local_select(rom_ctx* ctx, int kc, int n, int k, int rank, int r, rom_bu
                      const double* a_hi_host, int max_iter, rom_buf* OUT, size_t out_off, int64_t ldo, int32_t* label_host,
                      double* info8_host);
 
+/* ---- D-optimal sensor selection for parameter estimation (greedy Bayesian experimental design) ----
+ * Which m of ncand candidate points make point measurements determine theta = log a best, on average over a library of M
+ * parameters: expected information gain under the linearised Gaussian model.  romhighcontrast_amd/inverse.py::sensor_dopt_host is
+ * the same algorithm on the host.  With c(theta) = A(theta)^-1 bhat, A = sum_q e^theta_q Ahat_q, X_j = -dc/dtheta at entry j
+ * (n x k, column q = e^theta_q A^-1 Ahat_q c), e_x (n) the basis at candidate x (row x of E, from an element offset with a row
+ * stride), independent noise N(0, sigma^2) per sensor and the prior covariance T0 T0^T, the posterior precision of a sensor set S
+ * at entry j is F_j(S) = Gamma_0 + sigma^-2 sum_S g g^T, g = X_j^T e_x, and the criterion
+ *     Phi(S) = 1 / (2 M) sum_j log det(Gamma_0^-1 F_j(S)),
+ * monotone submodular in S, so the greedy reaches (1 - 1/e) of the optimum.
+ * STATE holds one block per entry (rom_sensor_dopt_layout): Z_j^T (kp rows of n_pad doubles, Z_j = X_j T_j / sigma) | T_j (kp x kp
+ * row-major, T_j T_j^T = F_j^-1) | status | s of the last update; kp = k rounded up to 1, 2, 4, 8 or 16, n_pad = n rounded up to a
+ * multiple of 4, the padding zero.
+ * rom_sensor_dopt_init: STATE for the empty sensor set, Z_j = X_j T0 / sigma and T_j = T0 (T0_host: k x k row-major, any factor of
+ * the prior covariance; a zero column is a parameter that is known), from the rows theta_j of THETA (M rows of k, from t_off with
+ * stride ldt).  One workgroup per entry assembles A(theta_j), factors it (L D L^T) and solves for c and the k columns of X_j.  An
+ * entry whose A has a pivot that is not positive (status 1) or whose theta is not finite (status 2) gets Z_j = 0: it contributes
+ * exactly 0 to every score, and the call succeeds.  info_host (8 doubles or NULL): such entries, launches, host synchronisations,
+ * bytes of workspace, 0 ...
+ * rom_sensor_dopt_scores: SCORE[sc_off + x] = sum_j log1p(|Z_j^T e_x|^2), the gain in 2 M Phi of adding candidate x -- one
+ * scoring pass without an update, and the information map one plots.  The product E [Z_1 .. Z_M] (ncand x M kp) runs on
+ * v_mfma_f64_16x16x4_f64 and is never written: 128 candidates are an LDS-resident table, the rows of Z^T stream through in slabs
+ * of 32, the epilogue (square, sum over an entry's kp columns, log1p, add in ascending j) stays in registers.  The library is cut
+ * into chunks of 2048 / kp entries, whatever the candidates are, and the chunks' partial sums are added in chunk order by a second
+ * kernel: a candidate's score has the same bits whichever other candidates are in the call, and on every call.
+ * rom_sensor_dopt: m greedy steps, each the scoring pass, the pick -- the first maximum among the candidates not yet picked whose
+ * score is finite; a NaN or infinite score (NaN / Inf in a row of E) is never picked -- and the rank-one update of every entry,
+ *     u = Z_j^T e_x*, s = |u|^2, rho = sqrt(1 + s), beta = 1 / (rho (rho + 1)), Z_j -= beta (Z_j u) u^T, T_j -= beta (T_j u) u^T,
+ * the symmetric square root of the Sherman-Morrison downdate.  Three launches per step (four where the library has more than one
+ * chunk), enqueued without host involvement, one host synchronisation at the end.  Stop reasons: 0 m picks made; 1 the gain was
+ * <= rel_tol x the first gain of this call (with rel_tol = 0: no information left to gain); 2 no candidate left.  STATE is updated
+ * in place, so a second call continues the design: taken_host (ntaken candidate indices, or NULL with 0) lists the picks of the
+ * earlier calls, which are then not picked again -- a design split over calls has the bits of the unsplit one (rel_tol = 0).
+ * picks_out (m int32, -1 behind the picks made), gain_out (m doubles, 0 behind them): gain = the score of the pick; the information
+ * Phi after pick t is the sum of the gains up to t over 2 (M - skipped entries).
+ * info_host (8 doubles or NULL): picks made, stop reason, entries of status != 0, candidates whose first score was not finite, launches,
+ * host synchronisations, bytes of workspace, flops executed by the scoring passes.
+ * 1 <= n <= 64, 1 <= k <= 16, 1 <= M <= 2^24, 1 <= ncand <= 2^22, 1 <= m <= min(1024, ncand), sigma > 0, 0 <= rel_tol < 1, the
+ * partial sums (chunks x ncand doubles) within the workspace limit: ROM_ERR_INVALID outside, naming the limit.  No operand but
+ * STATE and the outputs is modified; fp64 only, no floating-point atomics: the same bits on a repeated call.
+ * rom_sensor_dopt_layout (host only) out8: kp, n_pad, doubles per entry, entries per chunk, LDS bytes of the scoring kernel, the
+ * offsets of T_j and of the status in an entry's block, candidates per table. */
+int rom_sensor_dopt_layout(int n, int k, int64_t* out8);
+int rom_sensor_dopt_init(rom_ctx* ctx, int n, int k, rom_buf* Ahat, rom_buf* bhat, rom_buf* THETA, size_t t_off, int64_t ldt, int64_t M,
+                         const double* T0_host, double sigma, rom_buf* STATE, size_t s_off, double* info_host);
+int rom_sensor_dopt_scores(rom_ctx* ctx, int n, int k, rom_buf* STATE, size_t s_off, int64_t M, rom_buf* E, size_t e_off, int64_t lde,
+                           int64_t ncand, rom_buf* SCORE, size_t sc_off);
+int rom_sensor_dopt(rom_ctx* ctx, int n, int k, rom_buf* STATE, size_t s_off, int64_t M, rom_buf* E, size_t e_off, int64_t lde,
+                    int64_t ncand, int m, double rel_tol, const int32_t* taken_host, int ntaken, int32_t* picks_out, double* gain_out,
+                    double* info_host);
+
 /* ---- multi-GPU: RCCL all-gather of the snapshot block --------------------- */
 /* id_out: 128 bytes (ncclUniqueId).  librccl is dlopen()ed on first use. */
 int rom_comm_unique_id(char* id_out, size_t cap);

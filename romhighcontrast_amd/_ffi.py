@@ -151,6 +151,13 @@ PROTOTYPES = {
     "rom_mcmc": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                            C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t,
                            C.c_int64, _vp]),
+    "rom_sensor_dopt_layout": (C.c_int, [C.c_int, C.c_int, _vp]),
+    "rom_sensor_dopt_init": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, C.c_double, _vp,
+                                       C.c_size_t, _vp]),
+    "rom_sensor_dopt_scores": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp,
+                                         C.c_size_t]),
+    "rom_sensor_dopt": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_int,
+                                  C.c_double, _vp, C.c_int, _vp, _vp, _vp]),
     "rom_poly_sense": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                  C.c_int, C.c_double, _vp, C.c_size_t, C.c_int64, _vp]),
     "rom_mlp_sense": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, C.c_int64, C.c_int, C.c_int, _vp,
@@ -470,6 +477,50 @@ class Context:
         return dict(launches=int(info[0]), host_syncs=int(info[1]), workspace_bytes=int(info[2]), chains=int(info[3]),
                     steps=int(info[4]), evaluations=int(info[5]))
 
+    def sensor_dopt_layout(self, n, k) -> dict:
+        """rom_sensor_dopt_layout (host only): see the module function ``sensor_dopt_layout``."""
+        return sensor_dopt_layout(n, k)
+
+    def sensor_dopt_init(self, n, k, Ahat: "Buffer", bhat: "Buffer", THETA: "Buffer", t_off, ldt, M, T0, sigma,
+                         STATE: "Buffer | None" = None, s_off=0):
+        """rom_sensor_dopt_init: the design state of the empty sensor set for the M rows theta_j of THETA (k columns from t_off,
+        stride ldt): per entry Z_j = X_j T0 / sigma and T_j = T0 (T0 (k, k): a factor of the prior covariance).  STATE (M blocks
+        of ``sensor_dopt_layout(n, k)["entry"]`` doubles from s_off) is allocated when None.  Returns (STATE, info dict)."""
+        n, k, M = int(n), int(k), int(M)
+        lay = sensor_dopt_layout(n, k)
+        T0 = _host(np.asarray(T0, dtype=np.float64).reshape(k, k))
+        if STATE is None:
+            STATE = self.alloc(int(s_off) + max(M, 1) * lay["entry"])
+        info = np.zeros(8)
+        _check_kmeans(self.lib.rom_sensor_dopt_init(self.h, n, k, Ahat.h, bhat.h, THETA.h, int(t_off), int(ldt), M, T0.ctypes.data,
+                                                    float(sigma), STATE.h, int(s_off), info.ctypes.data))
+        return STATE, dict(skipped=int(info[0]), launches=int(info[1]), host_syncs=int(info[2]), workspace_bytes=int(info[3]))
+
+    def sensor_dopt_scores(self, n, k, STATE: "Buffer", s_off, M, E: "Buffer", e_off, lde, ncand, SCORE: "Buffer | None" = None,
+                           sc_off=0) -> "Buffer":
+        """rom_sensor_dopt_scores: SCORE[sc_off + x] = sum_j log1p(|Z_j^T e_x|^2) for the ncand rows e_x of E (n columns from
+        e_off, stride lde): one scoring pass, no update -- the information map.  SCORE is allocated when None.  Returns SCORE."""
+        if SCORE is None:
+            SCORE = self.alloc(int(sc_off) + max(int(ncand), 1))
+        _check_kmeans(self.lib.rom_sensor_dopt_scores(self.h, int(n), int(k), STATE.h, int(s_off), int(M), E.h, int(e_off), int(lde),
+                                                      int(ncand), SCORE.h, int(sc_off)))
+        return SCORE
+
+    def sensor_dopt(self, n, k, STATE: "Buffer", s_off, M, E: "Buffer", e_off, lde, ncand, m, rel_tol=0.0, taken=None):
+        """rom_sensor_dopt: up to m greedy D-optimal picks among the ncand candidate rows of E; STATE is updated in place, so a
+        second call continues the design -- ``taken``: the picks of the earlier calls, which are not picked again.  Returns
+        (picks (made,) int64, gain (made,), info dict); ValueError, naming the limit, outside the limits."""
+        m = int(m)
+        picks, gain, info = np.full(max(m, 1), -1, dtype=np.int32), np.zeros(max(m, 1)), np.zeros(8)
+        tk = np.ascontiguousarray(np.zeros(0) if taken is None else taken, dtype=np.int32).ravel()
+        _check_kmeans(self.lib.rom_sensor_dopt(self.h, int(n), int(k), STATE.h, int(s_off), int(M), E.h, int(e_off), int(lde), int(ncand),
+                                               m, float(rel_tol), tk.ctypes.data if tk.size else None, int(tk.size),
+                                               picks.ctypes.data, gain.ctypes.data, info.ctypes.data))
+        made = int(info[0])
+        d = dict(picks=made, stop_reason=int(info[1]), skipped=int(info[2]), nan_candidates=int(info[3]), launches=int(info[4]),
+                 host_syncs=int(info[5]), workspace_bytes=int(info[6]), flops=float(info[7]))
+        return picks[:made].astype(np.int64), gain[:made].copy(), d
+
     def poly_sense(self, m, d, r, Gr: "Buffer", P: "Buffer", p_off, ldp, K, t, T0: "Buffer", lo, hi, AUX: "Buffer | None" = None,
                    max_iter=30, misfit_tol=1e-3, OUT: "Buffer | None" = None, out_off=0, ldo=None):
         """rom_poly_sense: nonlinear.sense_scores on the device (Gr (r, P) = Sigma V^T of the sensing matrix, the terms of
@@ -674,6 +725,18 @@ def local_select_layout(n: int, k: int, rank: int, r: int) -> dict:
     if lib.rom_local_select_layout(int(n), int(k), int(rank), int(r), out.ctypes.data) != ROM_OK:
         raise ValueError(last_error())
     keys = ("lds_bytes", "row_doubles", "rank_max", "kc_max", "factor_offset", "b_offset", "gram_offset", "launches")
+    return {k_: int(v) for k_, v in zip(keys, out)}
+
+
+def sensor_dopt_layout(n: int, k: int) -> dict:
+    """rom_sensor_dopt_layout (host only; the single place of the limits on n and k and of an entry's block in STATE):
+    Z^T (kp rows of n_padded) | T (kp x kp) at ``t_offset`` | status at ``status_offset`` | s of the last update.  ``chunk``:
+    entries of one chunk of the scoring pass.  ValueError, naming the limit, outside the limits."""
+    lib = load_library()
+    out = np.zeros(8, dtype=np.int64)
+    if lib.rom_sensor_dopt_layout(int(n), int(k), out.ctypes.data) != ROM_OK:
+        raise ValueError(last_error())
+    keys = ("kp", "n_padded", "entry", "chunk", "lds_bytes", "t_offset", "status_offset", "table")
     return {k_: int(v) for k_, v in zip(keys, out)}
 
 

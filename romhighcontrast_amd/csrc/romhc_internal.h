@@ -97,6 +97,7 @@ struct rom_ctx {
   bool lds_optin_nn_screen = false, lds_optin_nn_exhaust = false;
   bool lds_optin_mlp_eval = false, lds_optin_mlp_predict = false;
   bool lds_optin_km_step = false;
+  bool lds_optin_dopt_score[5] = {false, false, false, false, false};   // k_dopt_score<kp>, kp = 1, 2, 4, 8, 16
 };
 
 struct rom_buf {

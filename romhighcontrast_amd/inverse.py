@@ -354,6 +354,28 @@ class ParameterLibrary:
             post = post._replace(states=DeviceArray(out, K, dim))
         return post
 
+    def select_sensors(self, candidates, m, sigma, prior_cov=None, weights=None, subset=None, rel_tol=0.0, device=True) -> "SensorDesign":
+        """Up to m of the ``candidates`` (ncand, 2) as sensors for PARAMETER estimation: the greedy Bayesian D-optimal design
+        (``sensor_dopt_host``; on the GPU ``rom_sensor_dopt`` unless ``device=False``) averaged over the library's parameters, or
+        over its rows ``subset``.  sigma: the noise level of a weighted measurement, as in ``posterior``; ``weights`` (ncand,)
+        scales the candidates' rows -- the ``weights`` of ``observe`` -- default 1.  prior_cov None: per parameter the variance of a
+        uniform law on the library's box of log a (a parameter with a zero-width box counts as known); else (k,) variances or a
+        (k, k) covariance.  The result's ``.points`` is ready for ``.observe(points)``."""
+        sm = self.sm
+        P = np.asarray(candidates, dtype=np.float64).reshape(-1, 2)
+        Ec = np.ascontiguousarray(sm._fem.evaluate_points(self._W, self.n, *sm._locate(P)).T)    # (ncand, n)
+        if weights is not None:
+            Ec = Ec * np.asarray(weights, dtype=np.float64).reshape(len(P), 1)
+        la = np.log(self.a)
+        if prior_cov is None:
+            prior_cov = (la.max(axis=0) - la.min(axis=0)) ** 2 / 12.0
+        theta = la if subset is None else la[np.asarray(subset, dtype=np.int64).ravel()]
+        if device:
+            des = sensor_dopt_device(sm._ctx, self.Ahat, self.bhat, theta, Ec, m, sigma, prior_cov, rel_tol=rel_tol)
+        else:
+            des = sensor_dopt_host(self.Ahat, self.bhat, theta, Ec, m, sigma, prior_cov, rel_tol=rel_tol)
+        return des._replace(points=P[des.picks])
+
 
 # ---- box-constrained least squares (Stark-Parker BVLS): the noise-robust linear state estimate ----------------------------------
 class BvlsResult(NamedTuple):
@@ -977,3 +999,194 @@ def posterior_summary(state, n, k, t, samples=None, perp2=None, states=None) -> 
     return ParameterPosterior(mean, cov, sd, rhat, acceptance, np.exp(S[:, :, o["ls"]]), np.exp(pick[:, o["theta_min"]:o["theta_min"] + k]),
                               misfit, S[:, :, o["mean_c"]:o["mean_c"] + n].mean(axis=1), cnt("outside"), cnt("not_spd"),
                               None if samples is None else np.asarray(samples).reshape(K, t, -1, k), states)
+
+
+# ---- D-optimal sensor selection for the parameter problem: greedy Bayesian experimental design -----------------------------------
+DOPT_LIMITS = dict(n=64, k=16, m=1024)   # rom_sensor_dopt (csrc/rom_oed.hip)
+DOPT_STOPS = ("m", "no_gain", "no_candidates")   # stop reasons 0, 1, 2
+
+
+class SensorDesign(NamedTuple):
+    """``sensor_dopt_host`` / ``sensor_dopt_device`` / ``ParameterLibrary.select_sensors``.  picks (made,): indices into the
+    candidates, in pick order; gain (made,): the score of every pick, sum_j log1p(s_j) over the library; information (made,): the
+    criterion Phi after every pick, in nats -- the expected information gain, the sum of the gains over 2 (M - skipped);
+    posterior_sd (M, k): sqrt diag(F_j^-1) of the linearised posterior of log a at every library entry (the prior's for a skipped
+    entry); stop_reason: "m", "no_gain" (the gain fell to rel_tol times the first) or "no_candidates"; skipped (M,): 0, 1 (A(theta_j)
+    has a pivot that is not positive) or 2 (theta_j is not finite) -- such an entry takes no part; nan_candidates: candidates whose
+    first score was not finite (NaN / Inf in their row: never picked); points (made, 2): the picked points, where the candidates were points, else None."""
+    picks: np.ndarray
+    gain: np.ndarray
+    information: np.ndarray
+    posterior_sd: np.ndarray
+    stop_reason: str
+    skipped: np.ndarray
+    nan_candidates: int = 0
+    points: Optional[np.ndarray] = None
+
+
+def sensor_prior_factor(prior_cov, k):
+    """T0 (k, k) with T0 T0^T = the prior covariance of theta = log a: ``prior_cov`` a scalar or (k,) of variances (T0 diagonal) or
+    a (k, k) symmetric positive semi-definite matrix (T0 = V sqrt(lambda) of its eigen-decomposition).  A zero variance is a
+    parameter that is known."""
+    C = np.asarray(prior_cov, dtype=np.float64)
+    if C.ndim < 2:
+        v = np.array(np.broadcast_to(C, (k,)))
+        if not (np.isfinite(v).all() and (v >= 0).all()):
+            raise ValueError("sensor design: the prior variances must be finite and not negative")
+        return np.diag(np.sqrt(v))
+    if C.shape != (k, k) or not np.isfinite(C).all() or not np.allclose(C, C.T, rtol=1e-12, atol=0.0):
+        raise ValueError(f"sensor design: the prior covariance must be a finite symmetric ({k}, {k}) matrix")
+    lam, V = np.linalg.eigh(0.5 * (C + C.T))
+    if lam.min() < -1e-12 * max(lam.max(), 0.0):
+        raise ValueError("sensor design: the prior covariance is not positive semi-definite")
+    return V * np.sqrt(np.maximum(lam, 0.0))
+
+
+def sensor_sensitivities_host(Ahat, bhat, theta, status=False):
+    """X (M, n, k) = -dc/dtheta at the rows of theta (M, k): column q = e^theta_q A^-1 Ahat_q c (``_rom_state``, py:59-60), with
+    A = sum_q e^theta_q Ahat_q factored as L D L^T without pivoting (the elimination of ``lm_factor``, csrc/rom_lm_small.h).  A row
+    whose A has a pivot that is not positive (status 1) or whose theta is not finite (status 2) gets X = 0.  With ``status``:
+    (X, status (M,))."""
+    Ahat, bhat = np.asarray(Ahat, dtype=np.float64), np.asarray(bhat, dtype=np.float64)
+    k, n = Ahat.shape[0], Ahat.shape[1]
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1, k)
+    M = len(theta)
+    with np.errstate(all="ignore"):
+        ea = np.exp(theta)
+        A = np.einsum("bq,qij->bij", ea, Ahat)
+        for j in range(n - 1):
+            l = A[:, j + 1:, j] / A[:, j, j, None]
+            A[:, j + 1:, j + 1:] -= A[:, j + 1:, j, None] * l[:, None, :]
+        d = np.einsum("bjj->bj", A)
+        invd = 1.0 / d
+
+        def solve(R):   # R (M, n, cols)
+            R = R.copy()
+            for j in range(n - 1):
+                R[:, j + 1:] -= (A[:, j + 1:, j] * invd[:, j, None])[:, :, None] * R[:, j, None, :]
+            R *= invd[:, :, None]
+            for j in range(n - 1, 0, -1):
+                R[:, :j] -= (A[:, j, :j] * invd[:, :j])[:, :, None] * R[:, j, None, :]
+            return R
+
+        c = solve(np.broadcast_to(bhat, (M, n))[:, :, None].copy())[:, :, 0]
+        X = solve(np.einsum("qij,bj->biq", Ahat, c) * ea[:, None, :])
+    st = np.where(np.isfinite(theta).all(axis=1), np.where((d > 0).all(axis=1), 0, 1), 2).astype(np.int64)
+    X[st != 0] = 0.0
+    return (X, st) if status else X
+
+
+def sensor_dopt_scores_host(Z, E, block=4096):
+    """score (ncand,) = sum_j log1p(|Z_j^T e_x|^2) for the rows e_x of E (ncand, n) and Z (M, n, k), the entries added in
+    ascending j."""
+    out = np.empty(len(E))
+    with np.errstate(all="ignore"):
+        for x0 in range(0, len(E), block):
+            U = np.einsum("xn,jnk->xjk", E[x0:x0 + block], Z)
+            out[x0:x0 + block] = np.cumsum(np.log1p(np.einsum("xjk,xjk->xj", U, U)), axis=1)[:, -1]
+    return out
+
+
+def sensor_dopt_update_host(Z, T, e):
+    """The rank-one update of every entry for the sensor with the row e (n,), in place: u = Z_j^T e, s = |u|^2, rho = sqrt(1 + s),
+    beta = 1 / (rho (rho + 1)), Z_j -= beta (Z_j u) u^T, T_j -= beta (T_j u) u^T.  Returns s (M,)."""
+    u = np.einsum("n,jnk->jk", e, Z)
+    s = np.einsum("jk,jk->j", u, u)
+    rho = np.sqrt(1.0 + s)
+    beta = 1.0 / (rho * (rho + 1.0))
+    Z -= (beta[:, None] * np.einsum("jnk,jk->jn", Z, u))[:, :, None] * u[:, None, :]
+    T -= (beta[:, None] * np.einsum("jak,jk->ja", T, u))[:, :, None] * u[:, None, :]
+    return s
+
+
+def sensor_dopt_host(Ahat, bhat, theta, E, m, sigma, prior_cov, rel_tol=0.0) -> SensorDesign:
+    """Greedy Bayesian D-optimal sensor selection for the parameters: THE SPECIFICATION of ``rom_sensor_dopt`` (csrc/rom_oed.hip),
+    pure NumPy.  Ahat (k, n, n), bhat (n,): the reduced model; theta (M, k) = log a of the library entries the design averages
+    over; E (ncand, n): row x the basis at candidate x (times the weight of that sensor); sigma: the standard deviation of the
+    independent measurement noise; prior_cov: see ``sensor_prior_factor``.
+
+    With X_j = ``sensor_sensitivities_host`` the Jacobian row of candidate x at entry j is g = X_j^T e_x, the posterior precision
+    of a sensor set S is F_j(S) = Gamma_0 + sigma^-2 sum_S g g^T and the criterion Phi(S) = 1 / (2 M) sum_j log det(Gamma_0^-1 F_j(S))
+    -- the expected information gain of the linearised Gaussian model, monotone submodular in S, so that the greedy reaches
+    (1 - 1/e) of the optimum.  State per entry: T_j (k, k) with T_j T_j^T = F_j^-1 and Z_j = X_j T_j / sigma, from T_j = T0.  A step:
+
+    1. score(x) = sum_j log1p(|Z_j^T e_x|^2), the entries in ascending j (= 2 M times the gain in Phi of adding x);
+    2. the pick x* is the first maximum among the candidates not yet picked whose score is finite; none: stop "no_candidates";
+       score(x*) <= rel_tol times the first step's: stop "no_gain" (with rel_tol = 0: nothing left to learn);
+    3. ``sensor_dopt_update_host``: the symmetric square root of the Sherman-Morrison downdate, (I - beta u u^T)^2 =
+       I - u u^T / (1 + s), without a factorisation or a difference of near-equal numbers.
+
+    A skipped entry (see ``SensorDesign``) has Z_j = 0 and adds exactly 0 to every score."""
+    Ahat, bhat, E = np.asarray(Ahat, dtype=np.float64), np.asarray(bhat, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    k, n = Ahat.shape[0], Ahat.shape[1]
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1, k)
+    E = E.reshape(-1, n)
+    M, ncand, m = len(theta), len(E), int(m)
+    if not (sigma > 0 and np.isfinite(sigma)):
+        raise ValueError(f"sensor design: sigma = {sigma}, the noise level must be positive and finite")
+    if M < 1 or not 1 <= m <= ncand:
+        raise ValueError(f"sensor design: M = {M} library entries (at least 1), m = {m} picks of ncand = {ncand} candidates")
+    T0 = sensor_prior_factor(prior_cov, k)
+    X, st = sensor_sensitivities_host(Ahat, bhat, theta, status=True)
+    Z = (X @ T0) / sigma
+    T = np.array(np.broadcast_to(T0, (M, k, k)))
+    taken = np.zeros(ncand, dtype=bool)
+    picks, gain, reason, first, nans = [], [], 0, 0.0, 0
+    with np.errstate(all="ignore"):
+        for t in range(m):
+            score = sensor_dopt_scores_host(Z, E)
+            if t == 0:
+                nans = int((~np.isfinite(score)).sum())
+            ok = np.isfinite(score) & ~taken
+            if not ok.any():
+                reason = 2
+                break
+            x = int(np.argmax(np.where(ok, score, -np.inf)))   # (the first maximum)
+            if t == 0:
+                first = score[x]
+            if score[x] <= rel_tol * first:
+                reason = 1
+                break
+            picks.append(x)
+            gain.append(score[x])
+            taken[x] = True
+            sensor_dopt_update_host(Z, T, E[x])
+    gain = np.array(gain, dtype=np.float64)
+    live = M - int((st != 0).sum())
+    info = np.cumsum(gain) / (2.0 * live) if live else np.zeros(len(gain))
+    return SensorDesign(np.array(picks, dtype=np.int64), gain, info, np.sqrt(np.einsum("jab,jab->ja", T, T)), DOPT_STOPS[reason], st, nans)
+
+
+def _check_dopt_limits(n, k, m):
+    for name, v in (("n", n), ("k", k), ("m", m)):
+        if not 1 <= v <= DOPT_LIMITS[name]:
+            raise ValueError(f"the device design (rom_sensor_dopt) needs 1 <= {name} <= {DOPT_LIMITS[name]}, got {name} = {v}: "
+                             "use device=False (sensor_dopt_host)")
+
+
+def sensor_dopt_device(ctx, Ahat, bhat, theta, E, m, sigma, prior_cov, rel_tol=0.0) -> SensorDesign:
+    """``sensor_dopt_host`` on the device of ``ctx`` (``rom_sensor_dopt_init``, ``rom_sensor_dopt``): the same arguments and the same
+    tuple.  The m steps run without host involvement."""
+    Ahat, bhat, E = np.asarray(Ahat, dtype=np.float64), np.asarray(bhat, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    k, n = Ahat.shape[0], Ahat.shape[1]
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1, k)
+    E = E.reshape(-1, n)
+    M, ncand = len(theta), len(E)
+    _check_dopt_limits(n, k, int(m))
+    T0 = sensor_prior_factor(prior_cov, k)
+    lay = ctx.sensor_dopt_layout(n, k)
+    STATE, _ = ctx.sensor_dopt_init(n, k, ctx.upload(Ahat), ctx.upload(bhat), ctx.upload(theta), 0, k, M, T0, sigma)
+    picks, gain, info = ctx.sensor_dopt(n, k, STATE, 0, M, ctx.upload(E), 0, n, ncand, m, rel_tol=rel_tol)
+    rows = STATE.download(M * lay["entry"]).reshape(M, lay["entry"])
+    T = rows[:, lay["t_offset"]:lay["t_offset"] + lay["kp"] ** 2].reshape(M, lay["kp"], lay["kp"])[:, :k, :k]
+    st = rows[:, lay["status_offset"]].astype(np.int64)
+    live = M - int((st != 0).sum())
+    information = np.cumsum(gain) / (2.0 * live) if live else np.zeros(len(gain))
+    return SensorDesign(picks, gain, information, np.sqrt(np.einsum("jab,jab->ja", T, T)), DOPT_STOPS[info["stop_reason"]], st,
+                        info["nan_candidates"])
+
+
+def select_sensors_parameters(sm, basis, a_library, candidates, m, sigma, **kw) -> SensorDesign:
+    """``ParameterLibrary(sm, basis, a_library).select_sensors(candidates, m, sigma, **kw)``: D-optimal sensors for estimating the
+    parameters, averaged over ``a_library``."""
+    return ParameterLibrary(sm, basis, a_library).select_sensors(candidates, m, sigma, **kw)

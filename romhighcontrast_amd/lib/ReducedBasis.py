@@ -446,6 +446,13 @@ class BaseReducedBasis:
         """Greedy PBDW sensor selection for this basis (``select_sensors_pbdw``; mode, beta_target, rel_tol as there)."""
         return select_sensors_pbdw(sm, self.basis, candidates, m, **kw)
 
+    def select_sensors_parameters(self, sm: SolutionsManager, candidates: np.ndarray, m: int, a_library, sigma, **kw):
+        """Greedy D-optimal sensor selection for estimating the PARAMETERS with this basis, averaged over ``a_library`` under
+        measurement noise ``sigma`` (``inverse.select_sensors_parameters``; prior_cov, weights, subset, rel_tol, device as in
+        ``ParameterLibrary.select_sensors``).  Returns a ``SensorDesign``."""
+        from ..inverse import select_sensors_parameters
+        return select_sensors_parameters(sm, self.basis, a_library, candidates, m, sigma, **kw)
+
     def error_curves(self, sm: SolutionsManager, true_solutions, a=None, n_max=None):
         """Absolute H^1_0 errors of ``projection`` (and, with the snapshots' parameters ``a``, of ``forward_modeling``)
         on the sub-bases ``self[:n]`` for every n = 0 .. n_max (default: all rows) in one device call; see
