@@ -105,17 +105,26 @@ __global__ void k_factor_panel(FemDev f, const double* __restrict__ a, int j, in
 __global__ void k_backsolve(FemDev f);
 __global__ void k_edge_transform(FemDev f, int Mc);
 __global__ void k_extend(FemDev f, const double* __restrict__ a, int Mc, double* __restrict__ U, long long row0, const int* __restrict__ blocks, int pw_log2);
-// Descriptors of up to X128_BLOCKS blocks for one k_extend128 launch, passed BY VALUE: kernel arguments are read
-// with scalar loads in one batch, whereas f.lr_blocks[z] -> f.sides[b] -> fields compiled into a chain of 14
-// dependent vector loads (each with its own s_waitcnt vmcnt(0)) at the head of every workgroup.
-struct X128Args {
-  int blocks[X128_BLOCKS];
-  BlockSide sides[X128_BLOCKS];
+// What a tile workgroup of k_extend128 reads of its launch, BY VALUE and as the FIRST argument: one batch of scalar loads from
+// the head of the kernel argument segment, issued before any branch (FemDev, a later argument, serves only the workgroups
+// of the folded expansion).  Kernel arguments and the tile's record (X128Tile, rom_fem_plan.h: one more scalar load, its
+// address formed from this struct alone) are all a workgroup reads before its first operand request -- no chain of
+// dependent loads, as f.lr_blocks[z] -> f.sides[b] -> fields once was (14 vector loads, each with its own wait).
+struct X128Head {
+  const X128Tile* plan;  // records of this launch's blocks: [blockIdx.z][tile]
+  const double* y;       // FemDev::y, Gs, W
+  const double* Gs;
+  const double* W;
+  double* U;
+  long long row0, dim;
+  int n1, N, ntile;  // ntile: tiles per block in this tiling
+  int nGp, sblk0, nc, ncb, Mc;
+  int with_expand, sys_fast, wave_skip;
+  int gx, gy;  // the grid's extents in x and y (for the start stagger: no hidden argument is read)
 };
 
 template <bool FLAT>
-__global__ void k_extend128(FemDev f, X128Args xa, const double* __restrict__ a, int Mc, double* __restrict__ U, long long row0, int with_expand, int sys_fast,
-                            int wave_skip);
+__global__ void k_extend128(X128Head h, FemDev f);
 // 4 doubles from an address that is only 8-byte aligned (pointer may be null -> zeros)
 __device__ inline void load4_any(const double* __restrict__ p, double v[4]) {
   if (p) {

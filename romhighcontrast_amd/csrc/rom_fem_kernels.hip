@@ -1820,22 +1820,40 @@ __global__ __launch_bounds__(256) void k_extend(FemDev f, const double* __restri
 // reads conflict free.  Rows that do not exist (systems >= Mc, vertices behind the end of the mesh row / the block) are
 // clamped to the last one that does: their products are not stored.
 constexpr int X128_SLOT = 4 * 128 * 64;  // bytes
-static_assert(sizeof(FemDev) + sizeof(X128Args) + 64 <= 4096, "k_extend128's arguments must fit the kernel argument segment");
 
 // FLAT: the 128 vertices of a tile are consecutive in the block's row-major vertex numbering instead of lying in
 // one mesh row -- no padding when n1 is not close to a multiple of 128 (n1 = 170: 226 tiles per block instead of
 // 340); a pair of adjacent vertices may then straddle two mesh rows and is stored as two 8-byte halves.
 template <bool FLAT>
-__global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, const double* __restrict__ a, int Mc,
-                                                      double* __restrict__ U, long long row0, int with_expand,
-                                                      int sys_fast, int wave_skip) {
+__global__ __launch_bounds__(512, 2) void k_extend128(X128Head h, FemDev f) {
   __shared__ __align__(16) char lds_bytes[2 * X128_SLOT];  // two chunk slots = 65,536 B: two workgroups per CU
   __shared__ double scs[128];                               // h^2 / a_b of the workgroup's systems
   double* const lds = reinterpret_cast<double*>(lds_bytes);
-  const int n1 = f.n1, N = f.N;
-  const int nct = (n1 + 127) / 128;
+// (dev build -DROMHC_X128_STAMPS: cycle stamps of the workgroup's phases, taken by every wave and stored by wave 0 in place of
+// the tile's first vertex of its first seven systems -- tools/dev/gpu_x128_stamps.py)
+#ifdef ROMHC_X128_STAMPS
+  unsigned long long x_stamp[5];
+#define X_STAMP(i) x_stamp[i] = __builtin_readcyclecounter()
+  X_STAMP(0);
+  x_stamp[1] = x_stamp[2] = x_stamp[0];
+#else
+#define X_STAMP(i)
+#endif
+  // ---- the head: what stands between a workgroup's entry and its first operand request.  While it runs the workgroup holds
+  // half of the CU's LDS and wave slots with nothing in flight, and every scalar load it waits for is a round trip through a
+  // memory system that the neighbours' stores keep busy (entry -> first request was 17 k cycles of a 45 k-cycle life when the
+  // head read FemDev and a BlockSide in six dependent rounds and walked the skip thresholds itself: profiles/x128_head.json).
+  // So: ONE round for X128Head, read here before any branch, one for the tile's record, then the first chunk's requests;
+  // whatever else the tile needs is set up under their latency.
+  const int n1 = h.n1, N = h.N, ntile = h.ntile, Mc = h.Mc, nGp = h.nGp;
+  const int with_expand = h.with_expand, sys_fast = h.sys_fast, gx = h.gx, gy = h.gy;
+  const X128Tile* const plan = h.plan;
+  const double* const y = h.y;
+  const double* const Gs = h.Gs;
+  const double* const W = h.W;
+  // (the operands of an asm statement are in registers when it is reached: the whole batch is requested here, ahead of the branches)
+  asm volatile("" ::"s"(n1), "s"(ntile), "s"(Mc), "s"(nGp), "s"(with_expand), "s"(sys_fast), "s"(gx), "s"(gy), "s"(plan), "s"(y), "s"(Gs), "s"(W));
   const int nvert = n1 * n1;
-  const int ntile = FLAT ? (nvert + 127) / 128 : n1 * nct;
   // Workgroup order.  Classic (sys_fast = 0): grid (tiles, system groups, blocks) -- consecutive workgroups walk the
   // vertex tiles of ONE system group: they share the interface vectors (small) and each reads its own slab of the tables.
   // sys_fast = number of system groups: 1-D grid in x, the system group varies fastest -- the workgroups in flight at
@@ -1852,7 +1870,7 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
     const int unit = int(blockIdx.x) / (8 * ngy), r = int(blockIdx.x) % (8 * ngy);
     bx = unit * 8 + (r & 7); by = r >> 3;
   } else {
-    bx = int(blockIdx.x); by = int(blockIdx.y); ngy = int(gridDim.y);
+    bx = int(blockIdx.x); by = int(blockIdx.y); ngy = gy;
   }
   if (bx >= ntile + with_expand) return;  // (padding of the last unit)
   if (bx >= ntile) {
@@ -1862,24 +1880,31 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
     const int nx = f.n1p / 64, ny = (Mc + 63) / 64;
     const int item = (bx - ntile) + with_expand * (by + ngy * blockIdx.z);
     if (threadIdx.x >= 256) return;  // (the expansion is written for four waves)
-    if (item < nx * ny * (f.nexp + 1)) expand_tile(f, Mc, U, row0, lds, item % nx, (item / nx) % ny, item / (nx * ny));
+    if (item < nx * ny * (f.nexp + 1)) expand_tile(f, Mc, h.U, h.row0, lds, item % nx, (item / nx) % ny, item / (nx * ny));
     return;
   }
   const int bz = blockIdx.z;
+  // (the planner's tables are written once, before any launch: constant address space, so that the uniform address makes
+  // these scalar loads whatever the kernel stores elsewhere)
+  typedef const unsigned __attribute__((address_space(4))) * ConstWords;
+  X128Tile rec;
+  {
+    const ConstWords src = (ConstWords)(plan + (bz * ntile + bx));
+    unsigned* const dst = reinterpret_cast<unsigned*>(&rec);
+#pragma unroll
+    for (int i = 0; i < int(sizeof(X128Tile) / 4); ++i) dst[i] = src[i];
+  }
   {
     // Two workgroups share a CU; started together they run in lockstep (both loading / multiplying, then both in
     // the epilogue).  The second half of the first round starts one MFMA phase late (about 64 cycles per MFMA)
     // so that the phases of the two interleave: measured 274 -> 245 us at 256x256 / 2x2 / 1024 systems.
     // Placement only affects speed.
-    const unsigned lin = __builtin_amdgcn_readfirstlane(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * bz));
+    const unsigned lin = __builtin_amdgcn_readfirstlane(blockIdx.x + unsigned(gx) * (blockIdx.y + unsigned(gy) * bz));
     if (lin >= 256u && lin < 512u)
       for (int i = 0; i < 2; ++i) __builtin_amdgcn_s_sleep(127);  // 2 x 127 x 64 cycles
   }
-  const int b = xa.blocks[bz];
-  const int p = b / f.ncb, q = b % f.ncb;
-  const BlockSide sd = xa.sides[bz];  // by value and read without branches below: one batch of scalar loads
-  const int iv = bx / nct + 1;           // mesh row (1-based interior index)       (!FLAT)
-  const int jv0 = 128 * (bx % nct) + 1;  // first vertex of the tile                (!FLAT)
+  const int iv = rec.row;                // mesh row (1-based interior index)       (!FLAT)
+  const int jv0 = rec.col;               // first vertex of the tile                (!FLAT)
   const int vt0 = 128 * bx;              // first vertex of the tile, block-local   (FLAT)
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wr = w >> 2, wc = w & 3;
   // The wave's 32 vertices are column wcv of the tile.  Waves w and w + 4 share a SIMD; with per-wave skipping the
@@ -1891,24 +1916,6 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   const int wcv = X128_MIRROR && wr ? 3 - wc : wc;
   constexpr int NJ = 2;  // 16-vertex column blocks per wave (wave tile 64 x 32)
   const int fr = lane & 15, kq = lane >> 4;
-  double my_sc = 0.0;  // h^2 / a_b of system threadIdx.x: requested now, parked in LDS after the k loop
-  if (threadIdx.x < 128) {
-    const int m = by * 128 + threadIdx.x;
-    if (m < Mc) my_sc = f.y[size_t(m) * f.nGp + f.sblk0 + b];
-  }
-  // everything the epilogue needs from memory is fetched before the first store: a load after a store would
-  // make its s_waitcnt vmcnt wait for the stores as well (one counter, in order)
-  double w_own[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    if (FLAT) {
-      const int v = vt0 + wcv * (16 * NJ) + j * 16 + fr;
-      w_own[j] = v < nvert ? f.W[v] : 0.0;
-    } else {
-      const int jj = jv0 + wcv * (16 * NJ) + j * 16 + fr;  // 1-based
-      w_own[j] = jj <= n1 ? f.W[(iv - 1) * n1 + (jj - 1)] : 0.0;
-    }
-  }
   // K runs over the sides' rank + 1 coefficients in segments of 8: the tables are padded to 16 per side, but only
   // ceil((rank + 1) / 8) segments of a side hold anything -- the second half of a side's last chunk is handed to the
   // next side (7-17 % fewer MFMAs where rank + 1 is just above a multiple of 16; products with the zero padding add
@@ -1916,55 +1923,22 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   // The directions of a side are ordered so that the ones that die fastest with the distance from the side come first
   // (rom_fem_plan.hip, rotate_to_echelon): at the tile's distance the first sk segments of the side's table are exact
   // zeros (k_mask_table) and the walk starts behind them.  The distance of a tile = that of its nearest vertex; a tile
-  // that walks more than it needs adds zeros, so every tiling gives the same bits.  Scalar code (the thresholds are
-  // kernel arguments).
+  // that walks more than it needs adds zeros, so every tiling gives the same bits.
   // A wave owns 32 of the tile's 128 vertices and is farther from the sides than the tile: from its own distances it gets
   // its own counts wsk >= sk (x128_skip_counts, rom_fem_plan.h) and multiplies only the halves of the walk that hold a
-  // segment >= wsk of its side -- bit h of `live`, built here once per tile.  The DMA walk stays the tile's.
-  int tsk[4], wsk[4];
-  const bool has_vertices = x128_skip_counts<FLAT>(n1, N, bx, wcv, sd.s[0], sd.s[1], sd.s[2], sd.s[3], tsk, wsk);
-  const int sk0 = tsk[0], sk1 = tsk[1], sk2 = tsk[2], sk3 = tsk[3];
-  const int cnt0 = x128_segs(sd.s[0]) - sk0, cnt1 = x128_segs(sd.s[1]) - sk1;
-  const int cnt2 = x128_segs(sd.s[2]) - sk2, cnt3 = x128_segs(sd.s[3]) - sk3;
+  // segment >= wsk of its side -- bit h of `live`.  The DMA walk stays the tile's.  All of this is the planner's work
+  // (x128_tile_plan, rom_fem_plan.h): the record holds the tile's walk and the four wave columns' masks.
+  const int cnt0 = rec.cnt[0], cnt1 = rec.cnt[1], cnt2 = rec.cnt[2], cnt3 = rec.cnt[3];
   const int nseg = cnt0 + cnt1 + cnt2 + cnt3;
   const int tot = (nseg + 1) / 2;
   // (wave_skip = 0, ROMHC_NO_EXT_WAVE_SKIP: every wave multiplies every half of the tile's walk, the odd last one included,
   // which is then fetched from the zero page; so does a walk too long for the mask)
-  const bool per_wave = wave_skip != 0 && nseg < 64;
-  long long live = -1;  // shifted down two bits per chunk, arithmetically
-  if (per_wave) {
-    unsigned long long m = 0;
-    int h0 = 0;
-#define X_LIVE(S_, CNT_)                                                                                           \
-  do { /* the side's halves h0 .. h0 + CNT_ - 1 hold its segments sk .. : live from wsk on */                      \
-    m |= ((1ull << (CNT_)) - (1ull << (wsk[S_] - tsk[S_]))) << h0;                                                  \
-    h0 += (CNT_);                                                                                                  \
-  } while (0)
-    X_LIVE(0, cnt0);
-    X_LIVE(1, cnt1);
-    X_LIVE(2, cnt2);
-    X_LIVE(3, cnt3);
-#undef X_LIVE
-    live = (long long)x128_uniform(has_vertices ? m : 0ull);  // (scalar: the k loop branches on its bits)
-  }
-  // ---- fragment addressing: lane (fr, kq) reads row fr (+ 16 i) at k = 4 kki + kq: half kki >> 1, unit
-  // (2 (kki & 1) + (kq >> 1)) ^ (fr >> 2), byte (kq & 1) * 8
-  const unsigned fx = unsigned((kq >> 1) ^ (fr >> 2));
-  const unsigned fa0 = unsigned(fr * 64) + (fx << 4) + unsigned(kq & 1) * 8u;
-  const unsigned fa1 = unsigned(fr * 64) + ((fx ^ 2u) << 4) + unsigned(kq & 1) * 8u;
-#define X_FRAGS(SLOT_, KKI_, AF_, BF_)                                                                             \
-  do {                                                                                                             \
-    const char* pf_ = lds_bytes + (SLOT_) * X128_SLOT + (((KKI_)&1) ? fa1 : fa0);                                  \
-    const char* pa_ = pf_ + ((KKI_) >> 1) * 8192 + wr * 4096;                                                      \
-    const char* pb_ = pf_ + 16384 + ((KKI_) >> 1) * 8192 + wcv * (1024 * NJ);                                     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) AF_[i_] = *reinterpret_cast<const double*>(pa_ + i_ * 1024);  \
-    _Pragma("unroll") for (int i_ = 0; i_ < NJ; ++i_) BF_[i_] = *reinterpret_cast<const double*>(pb_ + i_ * 1024); \
-  } while (0)
+  const bool per_wave = h.wave_skip != 0 && nseg < 64;
   // ---- DMA addressing: wave w of the fetching half takes rows 32 (w & 3) .. + 31 of both operands, 16 rows of one half
   // per instruction: lane -> row 32 (w & 3) + 16 g + (lane >> 2), stored unit lane & 3 = logical unit (lane & 3) ^ ((lane >> 4) & 3)
   const unsigned lds0 = unsigned(size_t((__attribute__((address_space(3))) char*)lds_bytes));
   const unsigned du16 = unsigned(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
-  const unsigned ybytes_row = unsigned(f.nGp) * 8u;
+  const unsigned ybytes_row = unsigned(nGp) * 8u;
   const int m0 = by * 128;
   unsigned voA[2];             // lane offsets behind ybytes + first system + side block
   int vi[2], vj[2];            // the lanes' vertices (1-based) in the wave's two B row groups
@@ -1973,19 +1947,20 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
     const int rl = 32 * (w & 3) + 16 * g + (lane >> 2);
     voA[g] = unsigned(max(0, min(rl, Mc - 1 - m0))) * ybytes_row + du16;
     if (FLAT) {
-      const int v = min(vt0 + rl, nvert - 1);
-      vi[g] = v / n1 + 1;
-      vj[g] = v % n1 + 1;
+      // vertex min(vt0 + rl, nvert - 1) = row-major (rec.row, jl); a tile spans at most two mesh rows of 128 vertices or more
+      const int jl = rec.col + min(rl, nvert - 1 - vt0);
+      const int up = n1 >= 128 ? (jl >= n1 ? 1 : 0) : jl / n1;
+      vi[g] = rec.row + up + 1;
+      vj[g] = jl - up * n1 + 1;
     } else {
       vi[g] = iv;
       vj[g] = min(jv0 + rl, n1);
     }
   }
-  const char* const ybase = reinterpret_cast<const char*>(f.y) + size_t(min(m0, Mc - 1)) * ybytes_row;
-  const char* const gsbase = reinterpret_cast<const char*>(f.Gs);
+  const char* const ybase = reinterpret_cast<const char*>(y) + size_t(min(m0, Mc - 1)) * ybytes_row;
+  const char* const gsbase = reinterpret_cast<const char*>(Gs);
   const size_t seg_stride = size_t(n1) * n1 * 64;  // bytes between the K segments of a table
-  const char* const zbase = reinterpret_cast<const char*>(f.W + size_t(n1) * n1);  // EXT_ZERO_PAGE doubles of zeros
-  const unsigned voZ = unsigned(lane) * 16u;
+  const char* const zbase = reinterpret_cast<const char*>(W + size_t(n1) * n1);  // EXT_ZERO_PAGE doubles of zeros
   // the walk over the segments (uniform): side, segments left in it, its two running pointers; lanes: table rows
   int c_side = -1, c_left = 0, c_segs = nseg;
   const char* pA = zbase;
@@ -1997,15 +1972,13 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
       ++c_side;                                                                                                    \
       c_left = c_side == 0 ? cnt0 : c_side == 1 ? cnt1 : c_side == 2 ? cnt2 : cnt3;                                \
     } while (c_left == 0 && c_side < 3);                                                                           \
-    const int off_ = c_side == 0 ? sd.s[0].off : c_side == 1 ? sd.s[1].off : c_side == 2 ? sd.s[2].off : sd.s[3].off; \
-    const int gseg_ = c_side == 0 ? sd.s[0].gseg : c_side == 1 ? sd.s[1].gseg : c_side == 2 ? sd.s[2].gseg : sd.s[3].gseg; \
     /* row of the side's segment-major table (k_repack_table) = ci i + cj j + k0, i / j the 1-based interior indices: */ \
     /* side 0: n1 (i - 1) + (j - 1); 1: n1 (n1 - i) + (j - 1); 2: n1 (i - 1) + (j - 1); 3: n1 (i - 1) + (n1 - j)  */     \
     const int ci_ = c_side == 1 ? -n1 : n1, cj_ = c_side == 3 ? -1 : 1;                                             \
     const int k0_ = c_side == 1 ? n1 * n1 - 1 : c_side == 3 ? -n1 + n1 : -n1 - 1;                                   \
-    const int sk_ = c_side == 0 ? sk0 : c_side == 1 ? sk1 : c_side == 2 ? sk2 : sk3; /* segments skipped */        \
-    pA = ybase + size_t(off_) * 8 + size_t(sk_) * 64;                                                              \
-    pB = gsbase + size_t(gseg_) * 8 + size_t(sk_) * seg_stride;                                                    \
+    /* the side's first walked segment (behind the ones the tile skips): the record has both offsets */           \
+    pA = ybase + (c_side == 0 ? rec.offA[0] : c_side == 1 ? rec.offA[1] : c_side == 2 ? rec.offA[2] : rec.offA[3]); \
+    pB = gsbase + (c_side == 0 ? rec.offB[0] : c_side == 1 ? rec.offB[1] : c_side == 2 ? rec.offB[2] : rec.offB[3]); \
     voB[0] = unsigned(ci_ * vi[0] + cj_ * vj[0] + k0_) * 64u + du16;                                               \
     voB[1] = unsigned(ci_ * vi[1] + cj_ * vj[1] + k0_) * 64u + du16;                                               \
   } while (0)
@@ -2029,11 +2002,55 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
       --c_segs;                                                                                                    \
       if (--c_left == 0 && c_segs > 0) X_NEXT_SIDE();                                                              \
     } else if ((MINE_) && !per_wave) { /* zeros: the odd half of the last chunk (per_wave: nobody reads it) */    \
+      unsigned voZ = threadIdx.x; /* lane * 16, formed here: a rare path need not hold a register through the k loop */ \
+      asm volatile("" : "+v"(voZ));                                                                                \
+      voZ = (voZ & 63u) * 16u;                                                                                     \
       X_DMA(sb_, zbase, voZ);                                                                                      \
       X_DMA(sb_ + 1024, zbase, voZ);                                                                               \
       X_DMA(sb_ + 16384, zbase, voZ);                                                                              \
       X_DMA(sb_ + 16384 + 1024, zbase, voZ);                                                                       \
     }                                                                                                              \
+  } while (0)
+  if (tot > 0) {
+    X_NEXT_SIDE();
+    X_ISSUE_HALF(0, 0, w < 4);
+    X_ISSUE_HALF(0, 1, w < 4);
+  }
+  X_STAMP(1);  // the first chunk is requested (wave 0 fetches)
+  // ---- under the first chunk's latency: everything else the tile needs
+  double my_sc = 0.0;  // h^2 / a_b of system threadIdx.x: requested now, parked in LDS after the k loop
+  if (threadIdx.x < 128) {
+    const int m = by * 128 + threadIdx.x;
+    if (m < Mc) my_sc = y[size_t(m) * nGp + h.sblk0 + rec.block];
+  }
+  // everything the epilogue needs from memory is fetched before the first store: a load after a store would
+  // make its s_waitcnt vmcnt wait for the stores as well (one counter, in order)
+  double w_own[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    if (FLAT) {
+      const int v = vt0 + wcv * (16 * NJ) + j * 16 + fr;
+      w_own[j] = v < nvert ? W[v] : 0.0;
+    } else {
+      const int jj = jv0 + wcv * (16 * NJ) + j * 16 + fr;  // 1-based
+      w_own[j] = jj <= n1 ? W[(iv - 1) * n1 + (jj - 1)] : 0.0;
+    }
+  }
+  // the wave column's mask, shifted down two bits per chunk, arithmetically (scalar: the k loop branches on its bits)
+  long long live = -1;
+  if (per_wave) live = (long long)x128_uniform(wcv == 0 ? rec.live[0] : wcv == 1 ? rec.live[1] : wcv == 2 ? rec.live[2] : rec.live[3]);
+  // ---- fragment addressing: lane (fr, kq) reads row fr (+ 16 i) at k = 4 kki + kq: half kki >> 1, unit
+  // (2 (kki & 1) + (kq >> 1)) ^ (fr >> 2), byte (kq & 1) * 8
+  const unsigned fx = unsigned((kq >> 1) ^ (fr >> 2));
+  const unsigned fa0 = unsigned(fr * 64) + (fx << 4) + unsigned(kq & 1) * 8u;
+  const unsigned fa1 = unsigned(fr * 64) + ((fx ^ 2u) << 4) + unsigned(kq & 1) * 8u;
+#define X_FRAGS(SLOT_, KKI_, AF_, BF_)                                                                             \
+  do {                                                                                                             \
+    const char* pf_ = lds_bytes + (SLOT_) * X128_SLOT + (((KKI_)&1) ? fa1 : fa0);                                  \
+    const char* pa_ = pf_ + ((KKI_) >> 1) * 8192 + wr * 4096;                                                      \
+    const char* pb_ = pf_ + 16384 + ((KKI_) >> 1) * 8192 + wcv * (1024 * NJ);                                     \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) AF_[i_] = *reinterpret_cast<const double*>(pa_ + i_ * 1024);  \
+    _Pragma("unroll") for (int i_ = 0; i_ < NJ; ++i_) BF_[i_] = *reinterpret_cast<const double*>(pb_ + i_ * 1024); \
   } while (0)
   d4_t acc[4][NJ];
 #pragma unroll
@@ -2041,10 +2058,8 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
   if (tot > 0) {
-    X_NEXT_SIDE();
-    X_ISSUE_HALF(0, 0, w < 4);
-    X_ISSUE_HALF(0, 1, w < 4);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    X_STAMP(2);
     double af[2][4], bf[2][NJ];
 #define X_MFMAS(PB_)                                                                                               \
   do {                                                                                                             \
@@ -2104,6 +2119,7 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   // makes full progress (tools/mfma_store_overlap.hip, `waves`); letting the stores go first shortens that phase
   // (C2: 0.234 -> 0.220 ms; the other way round, priority to the k loop: 0.243 ms; priority to the prologue as
   // well: 0.237 ms; profiles/r02_extend128_wave_priority_ab.txt).
+  X_STAMP(3);  // the k loop is done
   __builtin_amdgcn_s_setprio(ROMHC_EPI_PRIO);
   if (threadIdx.x < 128) scs[threadIdx.x] = my_sc;
   __syncthreads();
@@ -2118,7 +2134,8 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
   long long d1[NHP] = {};  // (FLAT) second vertex - first vertex, bytes
   unsigned long long k16[NHP], k8[NHP], k8b[NHP];
   {
-    char* const rowp = reinterpret_cast<char*>(U) + size_t(row0 + m0 + wr * 64 + kq) * size_t(f.dim) * 8;
+    const int p = rec.block / h.ncb, q = rec.block % h.ncb;
+    char* const rowp = reinterpret_cast<char*>(h.U) + size_t(h.row0 + m0 + wr * 64 + kq) * size_t(h.dim) * 8;
 #pragma unroll
     for (int hp = 0; hp < NHP; ++hp) {  // pair hp of column blocks: (0,1) and (2,3); even lanes take the first, odd the second
       const int t = wcv * (16 * NJ) + (2 * hp + (odd ? 1 : 0)) * 16 + fr - (odd ? 1 : 0);  // first of the two vertices, tile-local
@@ -2126,13 +2143,13 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
       bool ok0, ok1;
       if (FLAT) {
         const int v = vt0 + t, i0 = v / n1, j0 = v - i0 * n1;
-        off0 = (long long)(p * N + i0) * f.nc + q * N + j0;
-        off1 = j0 + 1 < n1 ? off0 + 1 : (long long)(p * N + i0 + 1) * f.nc + q * N;
+        off0 = (long long)(p * N + i0) * h.nc + q * N + j0;
+        off1 = j0 + 1 < n1 ? off0 + 1 : (long long)(p * N + i0 + 1) * h.nc + q * N;
         ok0 = v < nvert;
         ok1 = v + 1 < nvert;
       } else {
         const int jcol = jv0 + t;  // 1-based
-        off0 = (long long)(p * N + iv - 1) * f.nc + q * N - 1 + jcol;
+        off0 = (long long)(p * N + iv - 1) * h.nc + q * N - 1 + jcol;
         off1 = off0 + 1;
         ok0 = jcol <= n1;
         ok1 = jcol + 1 <= n1;
@@ -2145,7 +2162,7 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
       d1[hp] = (off1 - off0) * 8;
     }
   }
-  const long long step = 4ll * f.dim * 8;          // four rows down
+  const long long step = 4ll * h.dim * 8;          // four rows down
   const bool full = m0 + 128 <= Mc;                // all systems of the tile exist
   const int mrow = m0 + wr * 64 + kq;              // the lane's first system
 #pragma unroll
@@ -2176,9 +2193,23 @@ __global__ __launch_bounds__(512, 2) void k_extend128(FemDev f, X128Args xa, con
         sp[hp] += step;
       }
     }
+#ifdef ROMHC_X128_STAMPS
+  X_STAMP(4);  // the last store is issued
+  if (threadIdx.x < 64) {
+    unsigned hwid, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the wave's own rows are out before the stamps replace seven of their values)
+    // system m0 + k, the tile's first vertex (lane 0's first store): 0 the entry stamp (far above any solution value: how the reader finds the tiles), 1 .. 4 cycles since entry, 5 HW_ID, 6 XCC_ID
+    char* const first = const_cast<char*>(x128_uniform(sp[0] - 16 * step));
+    const double val = lane == 0 ? double(x_stamp[0]) : lane < 5 ? double(x_stamp[lane < 5 ? lane : 0] - x_stamp[0]) : lane == 5 ? double(hwid) : double(xcc);
+    if (lane < 7 && m0 + lane < Mc) *reinterpret_cast<double*>(first + size_t(lane) * size_t(h.dim) * 8) = val;
+  }
+#endif
+#undef X_STAMP
 }
-template __global__ void k_extend128<false>(FemDev, X128Args, const double*, int, double*, long long, int, int, int);
-template __global__ void k_extend128<true>(FemDev, X128Args, const double*, int, double*, long long, int, int, int);
+template __global__ void k_extend128<false>(X128Head, FemDev);
+template __global__ void k_extend128<true>(X128Head, FemDev);
 
 // interface values that k_expand does not write: cross points and the edges recovered node by node
 __global__ void k_scatter_interface(FemDev f, int Mc, double* __restrict__ U, long long row0) {

@@ -17,7 +17,7 @@ constexpr int DENSE_GROUPS_MAX = 8;    // closed-form edges whose coefficient bl
 constexpr int EXT_ZERO_PAGE = 256;  // doubles of zeros behind FemDev::W (target of the lanes of k_extend128 that have nothing to load)
 constexpr int EXT_THRESHOLDS = 7;   // distance thresholds of a compressed side (ExtSide::thr): K segments k_extend128 can skip
 constexpr long double EXT_TRUNC_CUT = 1e-18L;  // a table column is dropped where its bound is below this share of the largest
-constexpr int X128_BLOCKS = 16;     // blocks whose descriptors one k_extend128 launch takes by value (X128Args, rom_fem_dev.h)
+constexpr int X128_BLOCKS = 16;     // blocks one k_extend128 launch extends (grid z)
 
 // row of H0 that holds the extension from side s evaluated at interior vertex (i,j), 1-based
 __host__ __device__ inline int h0_row(int s, int i, int j, int N, int n1) {
@@ -103,6 +103,49 @@ __host__ __device__ inline bool x128_skip_counts(int n1, int N, int tile, int wc
   return has;
 }
 
+// What a workgroup of k_extend128 needs to know about its (lr block, tile) before it can request its first operand bytes,
+// and its waves' share of the walk: all of it depends on the geometry alone, so the planner works it out once (x128_tile_plan
+// below, with the functions above) and the workgroup fetches it with one scalar load instead of walking the thresholds itself.
+struct alignas(32) X128Tile {
+  unsigned char cnt[4];        // K segments walked per side (x128_segs - tsk); a side with 0 is passed over
+  int block;                   // the block (row-major, as in BlockSide / FemDev::sides)
+  unsigned offA[4];            // first walked segment of the side's [z_f, 1/s_f] block: bytes from the system's interface vector
+  unsigned long long offB[4];  // ... of the side's segment-major table: bytes from FemDev::Gs
+  unsigned long long live[4];  // per wave column: bit h = the column multiplies half h of the walk (0: it has no vertex at all);
+                               // all ones where the walk is too long for the mask (64 segments or more)
+  int row, col;                // the tile's first vertex: mesh row and column, 1-based (iv, jv0); FLAT: 0-based
+};
+static_assert(sizeof(X128Tile) == 96, "three 32-byte scalar loads");
+
+template <bool FLAT>
+inline X128Tile x128_tile_plan(int n1, int N, int block, int tile, const BlockSide& sd) {
+  X128Tile t{};
+  t.block = block;
+  const int nct = (n1 + 127) / 128;
+  t.row = FLAT ? 128 * tile / n1 : tile / nct + 1;
+  t.col = FLAT ? 128 * tile % n1 : 128 * (tile % nct) + 1;
+  int tsk[4], wsk[4][4], nseg = 0;
+  bool has[4];
+  for (int wc = 0; wc < 4; ++wc) has[wc] = x128_skip_counts<FLAT>(n1, N, tile, wc, sd.s[0], sd.s[1], sd.s[2], sd.s[3], tsk, wsk[wc]);
+  const size_t seg_stride = size_t(n1) * n1 * 64;  // bytes between the K segments of a table
+  for (int s = 0; s < 4; ++s) {
+    t.cnt[s] = (unsigned char)(x128_segs(sd.s[s]) - tsk[s]);
+    t.offA[s] = unsigned(sd.s[s].off) * 8u + unsigned(tsk[s]) * 64u;
+    t.offB[s] = size_t(sd.s[s].gseg) * 8 + size_t(tsk[s]) * seg_stride;
+    nseg += t.cnt[s];
+  }
+  for (int wc = 0; wc < 4; ++wc) {
+    unsigned long long m = 0;
+    int h0 = 0;
+    for (int s = 0; s < 4 && nseg < 64; ++s) {  // the side's halves h0 .. h0 + cnt - 1 hold its segments tsk .. : live from wsk on
+      m |= ((1ull << t.cnt[s]) - (1ull << (wsk[wc][s] - tsk[s]))) << h0;
+      h0 += t.cnt[s];
+    }
+    t.live[wc] = nseg >= 64 ? ~0ull : has[wc] ? m : 0ull;
+  }
+  return t;
+}
+
 // what rom_fem_create reads from the environment for the planner (ROMHC_NO_PREELIM, ROMHC_NO_COMPRESS,
 // ROMHC_NO_LOWRANK_EXT, ROMHC_NO_EXT_LR, ROMHC_VERBOSE, ROMHC_COMPRESS_TOL, ROMHC_NO_EXT_TRUNC)
 struct FemSwitches {
@@ -129,6 +172,9 @@ struct FemPlan {
   std::vector<ExpEdge> exps;
   std::vector<CoefGroup> groups;
   std::vector<BlockSide> sides;
+  // k_extend128's per-tile records, [position in lr_blocks][tile], for its two tilings: mesh rows (n1 * ceil(n1 / 128) tiles
+  // per block) and FLAT (ceil(n1^2 / 128))
+  std::vector<X128Tile> x128_row, x128_flat;
   // inputs of the device-side builds: G + off = A0 * Bh^T (rows x rp), Gs + gsoff = k_repack_table(G + goff); A0 from Qp, rho
   // Rotated basis (entry non-empty): Bh[k] is zero in front of mode entry[k]; rows at distance d from the side need only
   // the K segments from seg0[d] on (thr: the same as thresholds, ExtSide::thr) -- the others hold columns bounded by `cut`

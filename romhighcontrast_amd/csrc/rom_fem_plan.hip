@@ -1323,6 +1323,15 @@ void split_blocks(bool no_ext_lr, FemPlan& p) {
   }
 }
 
+// the per-tile records of k_extend128 (X128Tile, rom_fem_plan.h), both tilings
+void x128_tiles(FemPlan& p) {
+  const int n1 = p.n1, t_row = n1 * ((n1 + 127) / 128), t_flat = (n1 * n1 + 127) / 128;
+  for (int b : p.lr_blocks) {
+    for (int t = 0; t < t_row; ++t) p.x128_row.push_back(x128_tile_plan<false>(n1, p.N, b, t, p.sides[b]));
+    for (int t = 0; t < t_flat; ++t) p.x128_flat.push_back(x128_tile_plan<true>(n1, p.N, b, t, p.sides[b]));
+  }
+}
+
 // ---- every ROMHC_VERBOSE line ---------------------------------------------------------------------------------------
 void report(const FemPlan& p, const Compression& c) {
   {
@@ -1461,6 +1470,7 @@ int rom_fem_plan(int nrb, int ncb, int N, const FemSwitches& sw, FemPlan* out, s
   extension_sides(t, el, c, L, goff, p);
   if (p.gtotal >= (1ll << 31) || p.gstotal >= (1ll << 31)) return fail("rom_fem_create: extension tables too large");
   split_blocks(sw.no_ext_lr, p);
+  x128_tiles(p);
   phase.next("end");
   if (sw.verbose) report(p, c);
   // ---- work accounting of this algorithm, per snapshot solve ------------------------------------------------

@@ -168,7 +168,7 @@ extern "C" int rom_fem_create(rom_ctx* ctx, int nrb, int ncb, int N, rom_fem** o
   f->n_lr_blocks = int(p.lr_blocks.size()); f->n_gen_blocks = int(p.gen_blocks.size()); f->lr_nch = p.lr_nch;
   f->nscat = int(p.scat.size()); f->ext_flops = p.ext_flops; f->flops_solve = p.flops_solve; f->bytes_solve = p.bytes_solve;
   f->desc = p.desc; f->slot_of = p.slot_of; f->kptr = p.kptr; f->kpair = p.kpair; f->colptr = p.colptr; f->colrow = p.colrow;
-  f->colti = p.colti; f->diag_slot = p.diag_slot; f->sides = p.sides; f->ranks = p.ranks; f->lr_blocks_host = p.lr_blocks;
+  f->colti = p.colti; f->diag_slot = p.diag_slot; f->sides = p.sides; f->ranks = p.ranks;
 #define ROM_UPLOAD(member, vec) ROM_TRY(upload(ctx->stream, f->tables, &f->member, p.vec))
   ROM_UPLOAD(d_pool, pool);         ROM_UPLOAD(d_terms, terms);           ROM_UPLOAD(d_desc, desc);
   ROM_UPLOAD(d_alist, alist);       ROM_UPLOAD(d_aoff, aoff);             ROM_UPLOAD(d_pairs, pairs);
@@ -184,7 +184,8 @@ extern "C" int rom_fem_create(rom_ctx* ctx, int nrb, int ncb, int N, rom_fem** o
   ROM_UPLOAD(d_kptr, kptr);         ROM_UPLOAD(d_kpair, kpair);           ROM_UPLOAD(d_colptr, colptr);
   ROM_UPLOAD(d_colrow, colrow);     ROM_UPLOAD(d_colti, colti);           ROM_UPLOAD(d_sides, sides);
   ROM_UPLOAD(d_vmap, vmap);         ROM_UPLOAD(d_scat, scat);             ROM_UPLOAD(d_lr_blocks, lr_blocks);
-  ROM_UPLOAD(d_gen_blocks, gen_blocks); ROM_UPLOAD(d_epos, epos);
+  ROM_UPLOAD(d_gen_blocks, gen_blocks); ROM_UPLOAD(d_epos, epos);         ROM_UPLOAD(d_x128_row, x128_row);
+  ROM_UPLOAD(d_x128_flat, x128_flat);
 #undef ROM_UPLOAD
   ROM_TRY(build_extension_tables(f, p));
   if (f->fused1)  // (the attribute belongs to the kernel as loaded on this device; setting it again is harmless)

@@ -206,21 +206,24 @@ static int enqueue_solve(rom_fem* f, const FemDev& d, const double* am, int Mc, 
         ROM_PROF(ctx, nm[0], fl_ext * f->n_lr_blocks, 8.0 * Mc * double(f->n_lr_blocks) * nij);
         if (wide) {
           const int items = (f->n1p / 64) * ((Mc + 63) / 64) * (f->nexp + 1);  // workgroups of the folded expansion
-          // block descriptors travel as kernel arguments, X128_BLOCKS per launch; the folded expansion rides in the first
+          // X128_BLOCKS blocks per launch, each workgroup finds its tile's record at [z0 + blockIdx.z][tile]; the folded expansion
+          // rides in the first launch
+          X128Head hd;
+          memset(&hd, 0, sizeof(hd));
+          hd.y = d.y; hd.Gs = d.Gs; hd.W = d.W; hd.U = U; hd.row0 = row; hd.dim = d.dim;
+          hd.n1 = d.n1; hd.N = d.N; hd.ntile = t128;
+          hd.nGp = d.nGp; hd.sblk0 = d.sblk0; hd.nc = d.nc; hd.ncb = d.ncb; hd.Mc = Mc;
+          hd.sys_fast = sys_fast;
+          hd.wave_skip = f->sw_no_ext_wave_skip ? 0 : 1;  // every wave multiplies only the K segments its own vertices need
           for (int z0 = 0; z0 < f->n_lr_blocks; z0 += X128_BLOCKS) {
             const int nz = std::min(X128_BLOCKS, f->n_lr_blocks - z0);
-            X128Args xa;
-            memset(&xa, 0, sizeof(xa));
-            for (int z = 0; z < nz; ++z) {
-              xa.blocks[z] = f->lr_blocks_host[z0 + z];
-              xa.sides[z] = f->sides[xa.blocks[z]];
-            }
             const int extra = fold_expand && z0 == 0 ? (items + mt * nz - 1) / (mt * nz) : 0;
-            const int wave_skip = f->sw_no_ext_wave_skip ? 0 : 1;  // every wave multiplies only the K segments its own vertices need
             const int nx = sys_fast < 0 ? (t128 + extra + 7) / 8 * 8 : t128 + extra;
             dim3 grid(sys_fast ? nx * mt : nx, sys_fast ? 1 : mt, nz);
-            if (flat) k_extend128<true><<<grid, 512, 0, st>>>(d, xa, am, Mc, U, row, extra, sys_fast, wave_skip);
-            else k_extend128<false><<<grid, 512, 0, st>>>(d, xa, am, Mc, U, row, extra, sys_fast, wave_skip);
+            hd.plan = (flat ? f->d_x128_flat : f->d_x128_row) + size_t(z0) * t128;
+            hd.with_expand = extra; hd.gx = int(grid.x); hd.gy = int(grid.y);
+            if (flat) k_extend128<true><<<grid, 512, 0, st>>>(hd, d);
+            else k_extend128<false><<<grid, 512, 0, st>>>(hd, d);
           }
         } else {
           dim3 grid(f->n1 * ((f->n1 + 63) / 64), (Mc + 63) / 64, f->n_lr_blocks);

@@ -174,6 +174,7 @@ struct DenseGroup {
   int voff[4], vblk[4], vu0[4], vu1[4];
 };
 
+struct X128Tile;
 struct BlockSide {
   ExtSide s[4];
 };
@@ -310,7 +311,9 @@ struct rom_fem {
   int nrhs = 0;
   BlockSide* d_sides = nullptr;  // nrb*ncb
   int* d_lr_blocks = nullptr;    // blocks whose sides are all in compressed form (k_extend_lr)
-  std::vector<int> lr_blocks_host;  // the same list on the host (k_extend128 gets its descriptors as kernel arguments)
+  // k_extend128's per-tile records (X128Tile, rom_fem_plan.h), [position in lr_blocks][tile], in its two tilings
+  X128Tile* d_x128_row = nullptr;
+  X128Tile* d_x128_flat = nullptr;
   int* d_gen_blocks = nullptr;   // the others (k_extend)
   int n_lr_blocks = 0, n_gen_blocks = 0, lr_nch = 0;
   int* d_vmap = nullptr;         // interface position -> global dof (or -1), size nGp
